@@ -10,20 +10,34 @@ Workload (BASELINE.json configs[2] / [4]): one full HdGan stage-2 G+D training s
 (trainer/HdTrainer.py:705-751: G fwd, Reg fwd, STN, D fwd, all losses, backward through D/STN/Reg/G,
 Adam on R and G, second G fwd, 2x D fwd+bwd, Adam on D) on synthetic paired 512x512 slices already
 resident in HBM, 16 slices per GPU, bf16 storage/MFMA with fp32 accumulation (weak scaling over N).
-Prints ONE JSON line on rank 0: paired slices/s (whole job), the roofline of the dominant kernel family
+
+A plain run sets up, warms up, times the K steps and prints ONE JSON line on rank 0: paired slices/s (whole job) and
+`ms_per_step`, the wall time of one timed step.  `--dump-outputs DIR` then also writes what the last timed step computed
+(loss terms, output images, updated weights; a fixed, seeded sample of each large array) as DIR/<name>.npy; the inputs and
+initial weights are seeded, and the timed step runs the warp backward's scatter (the Hd and Reg steps' one order-dependent
+kernel) in 64-bit fixed point (`ops.DETERMINISTIC`) rather than float atomics, so every run with the same arguments computes the
+same bits and two builds can be compared output for output.  (With float atomics, Adam's early steps amplify the summation order:
+after 7 steps the Hd outputs of two runs differed by ~1e-1 rel-L2.  The fixed-point scatter costs ~0.35 ms of the ~49 ms step;
+train.py keeps the float atomics unless CTG_DETERMINISTIC=1, and the line's `config.warp_scatter` names the mode timed.  Lines
+recorded before this switch (BENCH_r01-r06) timed the float-atomic scatter, with per-kernel HIP events in the timed steps.)
+
+`--full` adds everything else to the line: the roofline of the dominant kernel family
 (the three kernels of the 256->256 3x3 convs of the residual blocks -- forward, backward-data with its fused
 epilogue, weight gradient -- each timed live with HIP events on its launch stream inside the timed steps), the HBM side of
 the roofline (`roofline.hbm`: the InstanceNorm elementwise kernels on those 256-channel maps and Reg's 32-channel
 full-resolution convs, timed the same way, GB/s against 8 TB/s), the CPU baseline (the oracle's torch-CPU restatement of
 the same step on a bounded sample, timed on this box's host cores), the second half of BASELINE.json's metric -- the
 generator output's rel-L2 against that CPU oracle in the timed precision (`gen_rel_l2`) -- and, at N=1, a `parity_mode`
-leg: the same step timed again in the split-bf16 mode ("bf16x3"), the fastest mode inside the north_star's 1e-3.
+leg: the same step timed again in the split-bf16 mode ("bf16x3"), the fastest mode inside the north_star's 1e-3 (and its
+bf16-backward form "bf16x3f", `parity_mode_bf16_backward`).  Without `--full`, `roofline`, `cpu_baseline`, `gen_rel_l2` and
+`tolerance_met` are null and the two parity legs are absent from the line and from `config`.
 """
 from __future__ import annotations
 
 import argparse
 import json
 import os
+import random
 import sys
 import time
 
@@ -195,6 +209,49 @@ def gen_rel_l2(ref, dev):
     #  ops.conv_in_fusable; the two forms differ by less than the last printed digit here.  No bounded wait may have run out.)
     assert ops.nie_failures() == 0
     return float((got - want).norm() / want.norm())
+
+
+WARP_SCATTER = ("64-bit fixed point (ops.DETERMINISTIC): every run with the same arguments computes the same bits; train.py's "
+                "default is float atomics, ~0.35 ms/step faster on the Hd step, whose results vary with the summation order")
+DUMP_SAMPLE = 1 << 20          # elements kept of an array larger than this (4 MB in float32)
+DUMP_LIMIT = 64 << 20          # bytes written by --dump-outputs in all
+
+
+def dump_outputs(dirpath, trainer, extra):
+    """What the last timed step handed its caller, as DIR/<name>.npy: the scalar loss terms of `trainer.last` as float64
+    (`loss_<term>`), its image tensors as float32 (`<name>`, logical (B, C, H, W)), the parameters of each network after the
+    step's optimiser updates flattened into one float32 vector (`params_<attribute>`), and the tensors of `extra` (the generator
+    output of the forward-only workload).  An array of more than DUMP_SAMPLE elements is written as a fixed, seeded sample of
+    DUMP_SAMPLE of its flattened elements (the same indices in every run of the same shape)."""
+    import numpy as np
+    arrays = {}
+    last = dict(getattr(trainer, "last", None) or {})
+    for k, v in sorted(last.items()):
+        if torch.is_tensor(v):
+            if v.dim() == 0:
+                arrays["loss_" + k] = v.detach().double().cpu().numpy()
+            else:
+                arrays[k] = v.detach().float().cpu().numpy()
+    if trainer is not None:
+        for k, m in sorted(vars(trainer).items()):
+            if isinstance(m, torch.nn.Module):
+                ps = [p.detach().float().reshape(-1) for p in m.parameters()]
+                if ps:
+                    arrays["params_" + k] = torch.cat(ps).cpu().numpy()
+    for k, v in sorted(extra.items()):
+        arrays[k] = v.detach().float().cpu().numpy()
+    if not arrays:
+        raise RuntimeError("--dump-outputs: the timed step left nothing to write")
+    for k, a in arrays.items():
+        if a.size > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_SAMPLE, replace=False))
+            arrays[k] = a.reshape(-1)[idx]
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT:      # checked before anything is written: no partial DIR
+        raise RuntimeError("--dump-outputs: %d bytes, more than %d" % (total, DUMP_LIMIT))
+    os.makedirs(dirpath, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(dirpath, k + ".npy"), a)
 
 
 def spawn_ranks(n: int) -> int:
@@ -377,9 +434,14 @@ def main():
     ap.add_argument("--batch", type=int, default=None, help="paired slices per GPU (default 16; 8 for gen/cyc)")
     ap.add_argument("--size", type=int, default=512)
     ap.add_argument("--dtype", choices=["bf16", "fp32", "bf16x3", "bf16x3f"], default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-events", action="store_true")
-    ap.add_argument("--no-parity-mode", action="store_true", help="skip the bf16x3 leg of the default Hd run")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: CPU baseline and generator rel-L2 vs the CPU oracle, "
+                         "per-kernel roofline, and (N=1, Hd, bf16) the bf16x3 / bf16x3f legs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and gen_rel_l2")
+    ap.add_argument("--no-kernel-events", action="store_true", help="with --full: skip the per-kernel roofline")
+    ap.add_argument("--no-parity-mode", action="store_true", help="with --full: skip the bf16x3 / bf16x3f legs of the Hd run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, <= 64 MB in all)")
     args = ap.parse_args()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(spawn_ranks(args.gpus))
@@ -388,6 +450,10 @@ def main():
     from cta_gan_amd import _lib, dp, nets, ops, synth
     from cta_gan_amd.trainer import Cyc_Trainer, Hd_Trainer_x2, P2p_Trainer, Reg_Trainer
     _lib.load()   # no HIP library -> no benchmark
+    # the timed path computes the same bits in every run (what --dump-outputs compares): the warp backward's scatter, the step's
+    # one order-dependent kernel, in 64-bit fixed point (the CTG_DETERMINISTIC=1 mode of ops.py) instead of the float atomics that
+    # train.py runs by default -- ~0.35 ms of the ~49 ms Hd step.  `config.warp_scatter` says so in the result line.
+    ops.DETERMINISTIC = True
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs an MI355X")
     try:
@@ -410,16 +476,19 @@ def main():
     # ---- CPU leg first (rank 0, N=1 only), so the GPU timing is not disturbed afterwards: the oracle's step timed on the host
     # cores (`cpu_baseline`) and its generator output on two synthetic slices (the reference of `gen_rel_l2`)
     cpu = gen_ref = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args.workload, size)
         gen_ref = gen_reference(size)
 
-    def run_leg(mode, steps, warmup):
+    def run_leg(mode, steps, warmup, dump_dir=None):
         """`warmup` untimed + `steps` timed steps of the workload in compute mode `mode`; returns (elapsed seconds of the timed
-        steps (max over ranks), kernel events, workload description, generator rel-L2 vs the CPU oracle or None)."""
+        steps (max over ranks), kernel events, workload description, generator rel-L2 vs the CPU oracle or None).  With
+        `dump_dir`, rank 0 then writes what the last timed step computed there (`dump_outputs`)."""
         nets.set_default_compute_dtype(MODES[mode])
         l2 = gen_rel_l2(gen_ref, dev) if gen_ref is not None else None
         torch.manual_seed(42)      # identical replicas (the trainers also broadcast rank 0's weights); data differs per rank
+        random.seed(42)            # the CycleGan replay buffers draw from Python's generator
+        tr, out = None, {}
         if args.workload == "hd":
             cfg = dict(YAML_HD, size=size, batchSize=per_gpu)
             tr = Hd_Trainer_x2(cfg)
@@ -446,7 +515,7 @@ def main():
 
             def step():
                 with torch.no_grad():
-                    G(x)
+                    out["fake_B"] = G(x)
             wl = "HdGan generator-only forward, %d %dx%d slices/GPU" % (per_gpu, size, size)
 
         for _ in range(warmup):
@@ -454,7 +523,7 @@ def main():
         torch.cuda.synchronize()
         dp.barrier()
         torch.cuda.synchronize()
-        if not args.no_kernel_events and rank == 0:
+        if args.full and not args.no_kernel_events and rank == 0:
             ops.KERNEL_EVENTS = {}            # kernel -> (start, end) HIP events around sampled launches of the timed kernels
             ops.KERNEL_BYTES.clear()
             ops._event_count.clear()
@@ -492,6 +561,8 @@ def main():
                                 "barrier excluded); `gradsync_stream_wait`: HIP events around every bucket's wait() in "
                                 "GradSync.finish() on the optimiser's stream = what the step loses to collectives that did not "
                                 "finish under the backward; `gradsync_host_wait`: the host thread's time in those waits"}
+        if dump_dir is not None and rank == 0:
+            dump_outputs(dump_dir, tr, out)
         return elapsed, events, dict(ops.KERNEL_BYTES), wl, l2, per_rank
 
     def mfma_roofline(events, mode):
@@ -589,7 +660,7 @@ def main():
 
     TOL = 1e-3      # north_star: generator output within 1e-3 rel-L2 of the CPU reference
 
-    elapsed, events, nbytes, wl, l2, per_rank = run_leg(dtype_name, args.steps, args.warmup)
+    elapsed, events, nbytes, wl, l2, per_rank = run_leg(dtype_name, args.steps, args.warmup, args.dump_outputs)
     line = None
     if rank == 0:
         value, step_tflops, step_tflops_exec = leg_numbers(dtype_name, args.steps, elapsed)
@@ -608,7 +679,8 @@ def main():
                 "config": {"workload": wl, "per_gpu_batch": per_gpu, "global_batch": per_gpu * world, "size": size,
                            "parallelism": "dp%d" % world if world > 1 else "single",
                            "step_tflops_algorithmic": round(step_tflops, 2),
-                           "step_tflops_executed": round(step_tflops_exec, 2)},
+                           "step_tflops_executed": round(step_tflops_exec, 2),
+                           "warp_scatter": WARP_SCATTER},
                 "step_frac": round(step_tflops_exec / PEAK_TFLOPS[dtype_name], 4),      # executed work / dense peak
                 "rccl_ranks": dp.world_size(), "dp_backend": dp.backend_name(),
                 "rank_cores": None if cores is None else "rank 0 pinned to %d cores (%d..%d): %s" % (len(cores), cores[0], cores[-1], PIN_HOW),
@@ -617,7 +689,7 @@ def main():
 
     # ---- parity-mode leg (N=1, the Hd step in bf16): the same step again in the split-bf16 mode, the fastest one whose
     # generator output is inside the north_star's 1e-3 of the fp32 CPU reference
-    if world == 1 and args.workload == "hd" and dtype_name == "bf16" and not args.no_parity_mode:
+    if args.full and world == 1 and args.workload == "hd" and dtype_name == "bf16" and not args.no_parity_mode:
         import gc
         gc.collect()
         torch.cuda.empty_cache()

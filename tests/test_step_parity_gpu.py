@@ -346,7 +346,22 @@ def test_frozen_discriminator_gets_no_weight_gradient_work():
 
 
 # --------------------------------------------------------------------------------------------- trajectory
-def test_hd_trajectory_5_steps_vs_reference(golden_dir):
+@pytest.fixture
+def deterministic_scatter():
+    """`ops.DETERMINISTIC` for one test.  The fp32 trajectories run with it: with the float-atomic scatter the step-3 deviation
+    from the reference spreads over 0.9-2.1e-2 from run to run, across the 2e-2 bound of TRAJ_TOL, while the fixed-point
+    scatter gives one repeatable trajectory (1.4e-2 at step 3, eagerly and from the captured graph alike).  That 1.4e-2 is one
+    fixed draw from the same spread: a change that reorders any sum of the step moves it within that spread, and the headroom to
+    2e-2 is what such a change has.  The float-atomic path keeps its five-step check in test_side_stream_equals_single_stream
+    (two float-atomic trajectories within 2 x TRAJ_TOL of each other) and its one-step checks against the goldens."""
+    from cta_gan_amd import ops
+    saved = ops.DETERMINISTIC
+    ops.DETERMINISTIC = True
+    yield
+    ops.DETERMINISTIC = saved
+
+
+def test_hd_trajectory_5_steps_vs_reference(golden_dir, deterministic_scatter):
     """Five consecutive stage-2 steps of the product trainer (fp32 mode) against the five steps the imported reference
     networks took (tests/golden/hd_traj5_stage2_256.npz): weight-pack invalidation after each Adam step, Adam moments and
     bias corrections, the side stream's ordering against the next step.  Loss terms of step i <= TRAJ_TOL[i] (see the
@@ -367,7 +382,7 @@ def test_hd_trajectory_5_steps_vs_reference(golden_dir):
         worst, rel_l2(tr.last["fake_B"].cpu().numpy()[:, :, ::8, ::8], want["fake_last_sub"])))
 
 
-def test_hd_trajectory_hip_graph_replays_vs_reference(golden_dir):
+def test_hd_trajectory_hip_graph_replays_vs_reference(golden_dir, deterministic_scatter):
     """The same five steps with `config['hip_graph']`: steps 1-3 run eagerly (warm-up), steps 4-5 are replays of the
     captured graph (device-side Adam step counter).  Same bound."""
     want = np.load(os.path.join(golden_dir, "hd_traj5_stage2_256.npz"))

@@ -23,9 +23,9 @@ FLAGS = ["-O3", "-fPIC", "-std=c++17", "--offload-arch=" + ARCH, "-fno-gpu-rdc",
 # compiler folds splats, half-selects and negations into those instructions' op_sel / op_sel_hi / neg modifiers, and the
 # broadcast form returned wrong products beside certain neighbours on the card ("the packed-fp32 modifier
 # hazard"; cause unknown).  With the feature off neither instruction selection nor the SLP vectoriser can form them; a
-# kernel that wants packed arithmetic writes it as inline assembly on whole register pairs (csrc/conv_cout1.hip:
-# c1_pk_fma -- the assembler still accepts the mnemonic), and tests/test_isa_gate.py disassembles the library and fails on
-# any v_pk_*_f32 that carries a modifier.  (clang applies -target-feature to the host pass too, which prints "not a
+# kernel that wants packed arithmetic writes it as inline assembly on whole register pairs and switches the feature back on for
+# itself with a target attribute (csrc/conv_cout1.hip: C1_PK_F32, c1_pk_fma -- with the feature off the assembler refuses the
+# mnemonic too), and tests/test_isa_gate.py disassembles the library and fails on any v_pk_*_f32 that carries a modifier.  (clang applies -target-feature to the host pass too, which prints "not a
 # recognized feature for this target (ignoring feature)": harmless.)  CTG_BUILD_PK_F32=all (or a comma list of sources)
 # leaves the feature on: the developer A/B of what the switch costs.
 NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]

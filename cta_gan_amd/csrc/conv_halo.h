@@ -17,6 +17,7 @@
 #include <stdlib.h>
 #include <type_traits>
 #include "common.h"
+#include "conv_dispatch.h"      // host side: tap windows, band plans, tile choices, the CTG_* switches
 
 struct ConvArgs {
     const void* x;
@@ -919,7 +920,7 @@ static int launch_halo_cfg(const ConvArgs& a, hipStream_t st, int* tiles_out = n
                 occ = 1;
             occ_dev[dev] = occ;
         }
-        static const int share = getenv("CTG_NIE_SHARE") && atoi(getenv("CTG_NIE_SHARE")) > 0 ? atoi(getenv("CTG_NIE_SHARE")) : 2;
+        const int share = ctg_knobs().nie_share > 0 ? ctg_knobs().nie_share : 2;
         if ((long)tiles * ntn * share > (long)occ_dev[dev] * ctg_cu_count()) return 2;      // not served: nothing launched
     }
     dim3 grid(tiles * ntn, a.B);
@@ -946,10 +947,8 @@ static int launch_halo_t(const ConvArgs& a, int out_f32, hipStream_t st, int* ti
                     // 8-row tiles -- 35.6 KB of LDS and 88 registers, so FOUR workgroups share a CU instead of three; what hides a
                     // short workgroup's serial chain is the number of workgroups in flight (887 -> 782 us; bf16 / 128-channel
                     // tiles, where the 8-row form stays at two workgroups per CU: 256 -> 274 us, not used)
-                    static const bool th8c_off = getenv("CTG_NO_MC_TH8") != nullptr;      // A/B switch
-                    if (a.ncls == 4 && !th8c_off) return launch_halo_cfg<T, bfpair_t, 64, 4, 1, 8, 1, 8, false, 0, false, true>(a, st, tiles_out);
-                    static const bool th8_64_off = getenv("CTG_NO_TH8_64") != nullptr;      // A/B switch (both modes)
-                    if (!th8_64_off && a.ncls <= 1 && a.Hs >= 16)      // (as for bf16 below: bf16x3 +0.45 %)
+                    if (a.ncls == 4 && !ctg_knobs().no_mc_th8) return launch_halo_cfg<T, bfpair_t, 64, 4, 1, 8, 1, 8, false, 0, false, true>(a, st, tiles_out);
+                    if (!ctg_knobs().no_th8_64 && a.ncls <= 1 && a.Hs >= 16)      // (as for bf16 below: bf16x3 +0.45 %)
                         return launch_halo_cfg<T, bfpair_t, 64, 4, 1, 8, 1, 8, false, 0, false, true>(a, st, tiles_out);
                     return launch_halo_cfg<T, bfpair_t, 64, 4, 1, 8, 1, 16, false, 0, false, true>(a, st, tiles_out);
                 }
@@ -975,16 +974,9 @@ static int launch_halo_t(const ConvArgs& a, int out_f32, hipStream_t st, int* ti
             if constexpr (sizeof(T) == 2) return launch_halo_cfg<T, float, 128, 4, 2, KCH, 1>(a, st, tiles_out);
             return -1;
         }
-        // small batches (the reference ships batchSize 1): 16x16-pixel tiles leave most of the 512 workgroup slots of the
-        // chip empty (128^2 x B=1 = 128 workgroups); 8x16-pixel tiles double the workgroups at the same bytes per FLOP
-        if constexpr (sizeof(T) == 2) {
-            static const bool th8_off = getenv("CTG_NO_TH8") != nullptr;
-            static const long th8_wgs = getenv("CTG_TH8_WGS") ? atol(getenv("CTG_TH8_WGS")) : 384;   // A/B knob
-            // (the merged parity-class launch has four workgroups per spatial tile and no 8-row instantiation: it keeps 16x16)
-            const long wgs = (long)((a.Hs + 15) / 16) * ((a.Ws + HALO_W - 1) / HALO_W) * ((a.Cout + 127) / 128) * a.B *
-                             (a.ncls == 4 ? 4 : 1);
-            if (!th8_off && a.ncls != 4 && wgs < th8_wgs && a.Hs >= 16)     // (ctg_conv_igemm's nie_tiles check mirrors this choice)
-                return launch_halo_cfg<T, T, 128, 4, 2, KCH, 1, 8>(a, st, tiles_out);
+        if constexpr (sizeof(T) == 2) {      // small grids: 8-row tiles
+            static_assert(HALO_W == 16, "halo_th8 counts 16-column tiles");
+            if (halo_th8(a.Hs, a.Ws, a.Cout, a.B, a.ncls)) return launch_halo_cfg<T, T, 128, 4, 2, KCH, 1, 8>(a, st, tiles_out);
         }
         return launch_halo_cfg<T, T, 128, 4, 2, KCH, 1>(a, st, tiles_out);
     }
@@ -997,9 +989,8 @@ static int launch_halo_t(const ConvArgs& a, int out_f32, hipStream_t st, int* ti
             // 64-channel tiles (Reg's 64 -> 64 layers at 256^2 and below: thousands of workgroups of 18 tap steps each) on 8-row
             // tiles: 39 KB of LDS instead of 57.5, so four workgroups share a CU instead of two -- what hides a short workgroup's
             // serial chain is the number of workgroups in flight (bf16 step +0.9 %)
-            static const bool th8_64_off = getenv("CTG_NO_TH8_64") != nullptr;      // A/B switch
             // (also the merged parity classes of the PatchGAN's 128 -> 64 backward-data: 132 -> 108 us)
-            if (!th8_64_off && (a.ncls <= 1 || a.ncls == 4) && a.Hs >= 16) return launch_halo_cfg<T, T, 64, 4, 1, KCH, 1, 8>(a, st, tiles_out);
+            if (!ctg_knobs().no_th8_64 && (a.ncls <= 1 || a.ncls == 4) && a.Hs >= 16) return launch_halo_cfg<T, T, 64, 4, 1, KCH, 1, 8>(a, st, tiles_out);
         }
         return launch_halo_cfg<T, T, 64, 4, 1, KCH, 1>(a, st, tiles_out);
     }

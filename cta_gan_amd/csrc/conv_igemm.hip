@@ -42,6 +42,11 @@ __device__ __attribute__((aligned(16))) unsigned g_zero_chunk[4];  // source of 
 #ifndef CTG_BIG_TILE
 #define CTG_BIG_TILE 1
 #endif
+// M tile of the gather kernel: 256 rows (x 128 channels, 8 waves, 3-stage LDS-DMA ring) for the wide bf16 layers at scale -- the
+// residual-block convs -- and 128 everywhere else.  launch_t launches by it and ctg_conv_igemm counts its moments slabs by it.
+static inline int gather_bm(bool bf16, bool k8, int omode, int Cout, long pixels) {
+    return (bf16 && k8 && omode == 0 && Cout > 64 && pixels >= 4096 && CTG_BIG_TILE && !ctg_knobs().no_big_tile) ? 256 : 128;
+}
 
 // sub-grid pixel of linear index m.  frame mode enumerates only the 1-pixel frame of the grid -- the part of a padded-grid
 // backward-data pass that the 16x16-tiled halo kernel would serve with 17 ragged tiles of 81 -- EDGE BY EDGE, each edge padded to a
@@ -504,8 +509,7 @@ static int launch_t(const ConvArgs& a, int out_f32, hipStream_t st) {
             if (out_f32 == 2) {
                 // (the 1-pixel frame of a padded grid: few pixels, long K -- narrower N tiles double the workgroups in flight)
                 // (launches of a few workgroups: the 3-stage ring, as on the bf16 path below)
-                static const bool ring_off_p = getenv("CTG_NO_SMALL_RING") != nullptr;
-                const bool small_p = !ring_off_p && (long)((grid_pixels(a) + 127) / 128) * ((a.Cout + 63) / 64) * a.B <= 1024;
+                const bool small_p = !ctg_knobs().no_small_ring && (long)((grid_pixels(a) + 127) / 128) * ((a.Cout + 63) / 64) * a.B <= 1024;
                 if (a.Cout > 64 && a.frame)
                     return small_p ? launch_cfg<T, bfpair_t, 128, 64, 4, 1, 8, 3, true>(a, st) : launch_cfg<T, bfpair_t, 128, 64, 4, 1, 8, 2, true>(a, st);
                 // (the 256x128 three-stage ring tile of the bf16 path measured no faster here: 119.0 vs 118.5 ms per step)
@@ -528,17 +532,13 @@ static int launch_t(const ConvArgs& a, int out_f32, hipStream_t st) {
             if constexpr (sizeof(T) == 2) return launch_cfg<T, float, 128, 128, 2, 2, KCH, 2>(a, st);
             return CTG_EINVAL;
         }
-        // wide layers at scale (the residual-block convs): 256x128 tile, 8 waves, 3-stage LDS-DMA ring
-        static const bool big_off = getenv("CTG_NO_BIG_TILE") != nullptr;
-        if (sizeof(T) == 2 && KCH == 8 && grid_pixels(a) >= 4096 && CTG_BIG_TILE && !big_off)
-            return launch_cfg<T, T, 256, 128, 4, 2, 8, 3>(a, st);
+        if (gather_bm(sizeof(T) == 2, KCH == 8, 0, a.Cout, grid_pixels(a)) == 256) return launch_cfg<T, T, 256, 128, 4, 2, 8, 3>(a, st);
         // the 1-pixel frame of a padded grid: few pixels, long K -- narrower N tiles double the workgroups in flight
-        static const bool frame64 = getenv("CTG_FRAME_BN128") == nullptr;
+        const bool frame64 = !ctg_knobs().frame_bn128;
         // A launch of a few workgroups is a serial chain of K steps: with the 2-stage form every step pays a whole global -> LDS
         // latency (its __syncthreads drains the loads it has just issued); the 3-stage ring keeps two steps of loads in flight
         // across the barrier (round 6: the frame launches and the U-Net's 4^2 ... 16^2 levels)
-        static const bool ring_off = getenv("CTG_NO_SMALL_RING") != nullptr;      // A/B switch
-        const bool small = sizeof(T) == 2 && !ring_off &&
+        const bool small = sizeof(T) == 2 && !ctg_knobs().no_small_ring &&
                            (long)((grid_pixels(a) + 127) / 128) * ((a.Cout + 63) / 64) * a.B <= 1024;
         if (a.frame && frame64) {
             if constexpr (sizeof(T) == 2) if (small) return launch_cfg<T, T, 128, 64, 4, 1, KCH, 3>(a, st);
@@ -553,8 +553,7 @@ static int launch_t(const ConvArgs& a, int out_f32, hipStream_t st) {
             return CTG_EINVAL;
         }
         if constexpr (sizeof(T) == 2) {
-            static const bool ring_off64 = getenv("CTG_NO_SMALL_RING") != nullptr;
-            if (!ring_off64 && (long)((grid_pixels(a) + 127) / 128) * a.B <= 512) return launch_cfg<T, T, 128, 64, 4, 1, KCH, 3>(a, st);
+            if (!ctg_knobs().no_small_ring && (long)((grid_pixels(a) + 127) / 128) * a.B <= 512) return launch_cfg<T, T, 128, 64, 4, 1, KCH, 3>(a, st);
         }
         return launch_cfg<T, T, 128, 64, 4, 1, KCH, 2>(a, st);
     }
@@ -662,25 +661,16 @@ extern "C" int ctg_conv_igemm(int dtype, int out_f32, const void* x, const void*
         // whose workgroups (spatial tiles x channel tiles: the groups of a sample are interleaved in dispatch order) are resident at
         // once whatever else runs -- checked against the kernel's real occupancy in launch_halo_cfg (CTG_NIE_SHARE launches, default
         // two -- streams, processes on one card -- can wait at the same time without starving each other).  Anything else: 2.
-        int dymin = 127, dymax = -128, dxmin = 127, dxmax = -128;
-        for (int t = 0; t < ntaps; ++t) {
-            const int dy = (a.taps[t] & 0xff) - 64, dx = ((a.taps[t] >> 8) & 0xff) - 64;
-            dymin = dy < dymin ? dy : dymin; dymax = dy > dymax ? dy : dymax;
-            dxmin = dx < dxmin ? dx : dxmin; dxmax = dx > dxmax ? dx : dxmax;
-        }
-        const int kh = dymax - dymin + 1, kw = dxmax - dxmin + 1;
-        long tiles = (long)((Hs + 15) / 16) * ((Ws + 15) / 16);
-        {   // the 8-row tile variant launch_halo_t picks for small bf16 grids: twice the tiles per sample
-            static const bool th8_off = getenv("CTG_NO_TH8") != nullptr;
-            static const long th8_wgs = getenv("CTG_TH8_WGS") ? atol(getenv("CTG_TH8_WGS")) : 384;
-            if (!pair && !th8_off && tiles * ((Cout + 127) / 128) * B < th8_wgs) tiles = (long)((Hs + 7) / 8) * ((Ws + 15) / 16);
-        }
-        static const bool nie_off = getenv("CTG_NO_NIE") != nullptr;
-        if (nie_off || dtype != DT_BF16 || out_f32 || !k8 || Cout % 128 || bias != nullptr || act != ACT_NONE || fold != nullptr ||
+        const TapWindow win = tap_window(a.taps, ntaps);
+        const int kh = win.kh(), kw = win.kw();
+        // spatial tiles per sample: the 8-row tiles launch_halo_t picks for small bf16 grids are twice as many
+        const int th = (!pair && halo_th8(Hs, Ws, Cout, B, 1)) ? 8 : 16;
+        const long tiles = (long)((Hs + th - 1) / th) * ((Ws + 15) / 16);
+        if (ctg_knobs().no_nie || dtype != DT_BF16 || out_f32 || !k8 || Cout % 128 || bias != nullptr || act != ACT_NONE || fold != nullptr ||
             a.bstats != nullptr || frame || os != 1 || is != 1 || oy0 || ox0 || Ho != Hs || Wo != Ws || Hs < 16 || Ws < 16 ||
             ntaps != kh * kw || ntaps < 2 || kw != 3 || kh > 3 ||
             stats_part == nullptr || stats_slabs_out == nullptr ||
-            (long)Hi * Wi * x_ld >= (1L << 31) || getenv("CTG_NO_HALO") != nullptr)
+            (long)Hi * Wi * x_ld >= (1L << 31) || ctg_knobs().no_halo)
             return 2;
         if (epi->nie_act != ACT_NONE && epi->nie_act != ACT_RELU && epi->nie_act != ACT_LRELU) return CTG_EINVAL;
         if (epi->nie_tiles != (int)tiles || ((uintptr_t)epi->nie_sync & 7)) return CTG_EINVAL;
@@ -703,22 +693,21 @@ extern "C" int ctg_conv_igemm(int dtype, int out_f32, const void* x, const void*
     // layers (Model/HdGan.py:124-131) in bf16 -- the generator's 3x3 ones have their sliding-window kernels below -- and every
     // stride-2 conv of the split-pair mode, which has none
     {
-        static const bool s2d_off = getenv("CTG_NO_S2D") != nullptr;      // A/B switch
         const int cslice = pair ? 32 : 64;
-        if (!s2d_off && dtype == DT_BF16 && is == 2 && os == 1 && !frame && !fused && pad_mode == PAD_ZERO && oy0 == 0 && ox0 == 0 &&
+        if (!ctg_knobs().no_s2d && dtype == DT_BF16 && is == 2 && os == 1 && !frame && !fused && pad_mode == PAD_ZERO && oy0 == 0 && ox0 == 0 &&
             Ho == Hs && Wo == Ws && Hs >= 16 && Ws >= 16 && Cin % cslice == 0 && Cout > 32 && (pair ? !out_f32 : (ntaps == 16 && !out_f32)) &&
             (long)Hi * Wi * x_ld < (1L << 31)) {
             ConvArgs b = a;
-            int cnt[4] = {0, 0, 0, 0}, amin = 127, amax = -128, bmin = 127, bmax = -128;
+            int cnt[4] = {0, 0, 0, 0};
             int ph_of[64], ay[64], ax[64];
+            TapWindow win;      // of the polyphase slices: floor(d / 2)
             for (int t = 0; t < ntaps; ++t) {
-                const int dy = (a.taps[t] & 0xff) - 64, dx = ((a.taps[t] >> 8) & 0xff) - 64;
+                const int dy = tap_dy(a.taps[t]), dx = tap_dx(a.taps[t]);
                 const int fy = dy >= 0 ? dy / 2 : -((1 - dy) / 2), fx = dx >= 0 ? dx / 2 : -((1 - dx) / 2);      // floor(d / 2)
                 ay[t] = fy; ax[t] = fx;
                 ph_of[t] = (dy - 2 * fy) * 2 + (dx - 2 * fx);
                 ++cnt[ph_of[t]];
-                amin = fy < amin ? fy : amin; amax = fy > amax ? fy : amax;
-                bmin = fx < bmin ? fx : bmin; bmax = fx > bmax ? fx : bmax;
+                win.add(fy, fx);
             }
             int nph = 0, t0 = 0;
             for (int q = 0; q < 4; ++q) {
@@ -729,7 +718,7 @@ extern "C" int ctg_conv_igemm(int dtype, int out_f32, const void* x, const void*
                 ++nph;
             }
             b.ncls = nph; b.s2d = 1;
-            b.kh = amax - amin + 1; b.kw = bmax - bmin + 1; b.dy0 = amin; b.dx0 = bmin;
+            b.kh = win.kh(); b.kw = win.kw(); b.dy0 = win.dy0(); b.dx0 = win.dx0();
             int ntile = 0;
             const bool want_stats = stats_part != nullptr && stats_slabs_out != nullptr && bias == nullptr && act == ACT_NONE;
             b.stats = want_stats ? stats_part : nullptr;
@@ -742,18 +731,12 @@ extern "C" int ctg_conv_igemm(int dtype, int out_f32, const void* x, const void*
     }
     // ---- stride-1 convs whose taps form a full kh x kw window: halo-resident kernel (conv_halo.h)
     {
-        int dymin = 127, dymax = -128, dxmin = 127, dxmax = -128;
-        for (int t = 0; t < ntaps; ++t) {
-            const int dy = (a.taps[t] & 0xff) - 64, dx = ((a.taps[t] >> 8) & 0xff) - 64;
-            dymin = dy < dymin ? dy : dymin; dymax = dy > dymax ? dy : dymax;
-            dxmin = dx < dxmin ? dx : dxmin; dxmax = dx > dxmax ? dx : dxmax;
-        }
-        a.kh = dymax - dymin + 1; a.kw = dxmax - dxmin + 1; a.dy0 = dymin; a.dx0 = dxmin;
-        static const bool halo_off = getenv("CTG_NO_HALO") != nullptr;
+        const TapWindow win = tap_window(a.taps, ntaps);
+        a.kh = win.kh(); a.kw = win.kw(); a.dy0 = win.dy0(); a.dx0 = win.dx0();
         // full window; a single tap only as one parity class of a transposed conv (os == 2), where the other
         // classes run here too
         const bool window = ntaps == a.kh * a.kw && (ntaps > 1 || os == 2);
-        if (!halo_off && !frame && window && is == 1 && (os == 1 || os == 2) && Hs >= 16 && Ws >= 16 &&
+        if (!ctg_knobs().no_halo && !frame && window && is == 1 && (os == 1 || os == 2) && Hs >= 16 && Ws >= 16 &&
             (long)Hi * Wi * x_ld < (1L << 31)) {
             // fused InstanceNorm moments: only meaningful without bias/activation and for one N-partition layout
             int ntile = 0;
@@ -788,9 +771,7 @@ extern "C" int ctg_conv_igemm(int dtype, int out_f32, const void* x, const void*
     int mtiles = 0;
     if (stats_part != nullptr && stats_slabs_out != nullptr && bias == nullptr && act == ACT_NONE &&
         Cout > 16 && os == 1 && !frame && Hs == Ho && Ws == Wo && oy0 == 0 && ox0 == 0) {
-        const int bm = pair ? 128
-                     : (Cout > 64 && dtype == DT_BF16 && !out_f32 && k8 && (long)Hs * Ws >= 4096 && CTG_BIG_TILE &&
-                        getenv("CTG_NO_BIG_TILE") == nullptr) ? 256 : 128;   // mirrors the tile launch_t picks
+        const int bm = gather_bm(dtype == DT_BF16, k8, omode, Cout, (long)Hs * Ws);      // (this branch has no frame: grid_pixels = Hs * Ws)
         mtiles = (Hs * Ws + bm - 1) / bm;
         const long bound = (long)((Hs + 7) / 8) * ((Ws + 15) / 16);      // what the caller sized the buffer for
         if (mtiles <= bound) a.stats = stats_part;
@@ -828,8 +809,7 @@ extern "C" int ctg_conv_igemm_classes(int dtype, const void* x, const void* w, v
     if (((uintptr_t)x & 15) || ((uintptr_t)w & 15) || ((uintptr_t)y & 15)) return CTG_EINVAL;
     const int bn = Cout > 64 ? 128 : Cout > 32 ? 64 : Cout > 16 ? 32 : 16;
     if (w_npad < ((Cout + bn - 1) / bn) * bn) return CTG_EINVAL;
-    static const bool off = getenv("CTG_NO_HALO") != nullptr || getenv("CTG_NO_CLASS_MERGE") != nullptr;
-    if (off || Hs < 16 || Ws < 16 || Cout <= 16 || (long)Hi * Wi * x_ld >= (1L << 31)) return 2;
+    if (ctg_knobs().no_halo || ctg_knobs().no_class_merge || Hs < 16 || Ws < 16 || Cout <= 16 || (long)Hi * Wi * x_ld >= (1L << 31)) return 2;
     ConvArgs a;
     a.stats = nullptr;
     a.nie_sync = nullptr; a.nie_act = ACT_NONE; a.nie_budget = 0;
@@ -853,22 +833,20 @@ extern "C" int ctg_conv_igemm_classes(int dtype, const void* x, const void* w, v
         const int nt = cls_ntaps[q];
         if (nt < 1 || t0 + nt > 64) return nt < 1 ? 2 : CTG_EINVAL;
         if ((Hs - 1) * 2 + cls_oy0[q] >= Ho || (Ws - 1) * 2 + cls_ox0[q] >= Wo || cls_oy0[q] < 0 || cls_ox0[q] < 0) return CTG_EINVAL;
-        int dymin = 127, dymax = -128, dxmin = 127, dxmax = -128;
         for (int t = 0; t < nt; ++t) {
             const int tw = taps_host[t0 + t];
-            const int dy = (tw & 0xff) - 64, dx = ((tw >> 8) & 0xff) - 64;
+            const int dy = tap_dy(tw), dx = tap_dx(tw);
             if (pad_mode == PAD_REFLECT) {
                 const int ymax = (Hs - 1) + dy, xmax = (Ws - 1) + dx;
                 if (-dy >= Hi || ymax - (Hi - 1) >= Hi || -dx >= Wi || xmax - (Wi - 1) >= Wi) return CTG_EINVAL;
             }
-            dymin = dy < dymin ? dy : dymin; dymax = dy > dymax ? dy : dymax;
-            dxmin = dx < dxmin ? dx : dxmin; dxmax = dx > dxmax ? dx : dxmax;
             a.taps[t0 + t] = tw;
         }
-        const int kh = dymax - dymin + 1, kw = dxmax - dxmin + 1;
+        const TapWindow win = tap_window(taps_host + t0, nt);
+        const int kh = win.kh(), kw = win.kw();
         if (nt != kh * kw) return 2;                 // not a full window: the gather kernel's business
         a.c_ntaps[q] = nt; a.c_tap0[q] = t0; a.c_oy0[q] = cls_oy0[q]; a.c_ox0[q] = cls_ox0[q];
-        a.c_kh[q] = kh; a.c_kw[q] = kw; a.c_dy0[q] = dymin; a.c_dx0[q] = dxmin;
+        a.c_kh[q] = kh; a.c_kw[q] = kw; a.c_dy0[q] = win.dy0(); a.c_dx0[q] = win.dx0();
         kh_max = kh > kh_max ? kh : kh_max;
         kw_max = kw > kw_max ? kw : kw_max;
         t0 += nt;

@@ -17,6 +17,7 @@
 // input gradient is "a 7x7 conv of the 1-channel output gradient with the flipped weights" on the padded grid.
 #include <stdlib.h>
 #include "common.h"
+#include "ctg_knobs.h"
 
 struct SmallArgs {
     const float* s0;
@@ -456,7 +457,7 @@ static int launch_small(SmallArgs& a, hipStream_t st, int* tiles_out) {
     a.ntiles = tiles;
     if (tiles_out != nullptr) *tiles_out = tiles;
     // persistent workgroups: about three per CU over the whole batch, each sweeping a run of tiles of one sample
-    static const int wg_total = getenv("CTG_SMALL_WGS") ? atoi(getenv("CTG_SMALL_WGS")) : 768;
+    const int wg_total = ctg_knobs().small_wgs;
     int gx = (wg_total + a.B - 1) / a.B;
     if (gx > tiles) gx = tiles;
     hipLaunchKernelGGL((conv_small_kernel<T, KPAD, BN, PO, X3, KXW>), dim3(gx, a.B), dim3(256), smem, st, a);

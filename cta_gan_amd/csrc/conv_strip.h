@@ -431,38 +431,24 @@ __global__ __launch_bounds__(256, 2) void conv_strip32p_kernel(const StripArgs a
 
 // returns -1 when the shape is not served here
 static int launch_strip32(const ConvArgs& a, hipStream_t st, int* tiles_out, bool pair) {
-    static const bool off = getenv("CTG_NO_STRIP") != nullptr;       // A/B switch (scripts/ab.sh)
-    if (off || a.Cin != (pair ? 64 : 32) || a.Cout != 32 || a.kh != 3 || a.kw != 3 || a.ntaps != 9 || a.is != 1 || a.os != 1 || a.ncls > 1 ||
+    if (ctg_knobs().no_strip || a.Cin != (pair ? 64 : 32) || a.Cout != 32 || a.kh != 3 || a.kw != 3 || a.ntaps != 9 || a.is != 1 || a.os != 1 || a.ncls > 1 ||
         a.oy0 != 0 || a.ox0 != 0 || a.Ho != a.Hs || a.Wo != a.Ws || a.Hi != a.Hs || a.Wi != a.Ws || a.res != nullptr ||
         a.fold != nullptr || a.dy0 != -1 || a.dx0 != -1 || a.act > ACT_LRELU)
         return -1;
     if ((long)a.B * a.Hs * a.Ws < (1L << 20) || a.Hs < 32 || a.Ws < 32 || (a.y_ld & 3) || (a.x_ld & 7)) return -1;   // large maps only
     if (pair && (long)a.Hs * a.Ws * a.x_ld >= (1L << 31)) return -1;
-    // tap order: forward (dy ascending, dx fastest) or flipped
-    bool fwd = true, flip = true;
-    for (int t = 0; t < 9; ++t) {
-        const int dy = (a.taps[t] & 0xff) - 64, dx = ((a.taps[t] >> 8) & 0xff) - 64;
-        fwd = fwd && dy == t / 3 - 1 && dx == t % 3 - 1;
-        flip = flip && dy == 1 - t / 3 && dx == 1 - t % 3;
-    }
-    if (!fwd && !flip) return -1;
+    const bool fwd = taps_3x3(a.taps, false);      // tap order: forward or flipped
+    if (!fwd && !taps_3x3(a.taps, true)) return -1;
     StripArgs s;
     s.x = (const bf16_t*)a.x; s.w = (const bf16_t*)a.w; s.y = (bf16_t*)a.y; s.bias = a.bias; s.stats = a.stats;
     s.B = a.B; s.H = a.Hs; s.W = a.Ws; s.x_ld = a.x_ld; s.y_ld = a.y_ld; s.w_tap_stride = a.w_tap_stride;
     s.pad_mode = a.pad_mode; s.act = a.act;
     s.x_lo = a.pair_lo; s.y_lo = a.y_ld / 2;
     s.nstrips = (a.Ws + 15) / 16;
-    // bands: one band per wave; as many waves as the chip holds at three per SIMD (one dispatch round, no tail), bands >= 32 rows
-    static const int band_env = getenv("CTG_STRIP_BAND") ? atoi(getenv("CTG_STRIP_BAND")) : 0;      // A/B knob
-    const int n_cu = ctg_cu_count();
-    const long cap = (long)n_cu * 4 * (pair ? 2 : 3);       // (split-pair: two waves per SIMD)
-    long nb = cap / ((long)a.B * s.nstrips);
-    if (nb < 1) nb = 1;
-    int band = (int)((a.Hs + nb - 1) / nb);
-    if (band < 32) band = 32;
-    if (band_env >= 8) band = band_env;
-    s.band_rows = band;
-    s.nbands = (a.Hs + band - 1) / band;
+    // bands: one band per wave; as many waves as the chip holds at three per SIMD (split-pair: two), bands >= 32 rows
+    const BandPlan bp = band_plan(a.Hs, 32, (long)ctg_cu_count() * 4 * (pair ? 2 : 3), (long)a.B * s.nstrips, ctg_knobs().strip_band);
+    s.band_rows = bp.band_rows;
+    s.nbands = bp.nbands;
     for (int t = 0; t < 9; ++t) s.widx[t] = a.taps[t] >> 16;
     const long waves = (long)a.B * s.nbands * s.nstrips;
     if (tiles_out != nullptr) *tiles_out = s.nbands * s.nstrips;

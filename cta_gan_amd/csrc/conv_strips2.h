@@ -203,39 +203,21 @@ __global__ __launch_bounds__(256, 2) void conv_strips2_64_128_kernel(const Strip
 
 // returns -1 when the launch is not this kernel's shape: a = the ConvArgs ctg_conv_igemm built (one stride-2 3x3 window)
 static int launch_strips2(const ConvArgs& a, float* stats, hipStream_t st, int* slabs_out) {
-    static const bool off = getenv("CTG_NO_STRIPS2") != nullptr;     // A/B switch (scripts/ab.sh)
-    if (off || a.ncls != 1 || a.Cin != 64 || a.Cout != 128 || a.os != 1 || a.is != 2 || a.oy0 || a.ox0 || a.frame ||
+    if (ctg_knobs().no_strips2 || a.ncls != 1 || a.Cin != 64 || a.Cout != 128 || a.os != 1 || a.is != 2 || a.oy0 || a.ox0 || a.frame ||
         a.bias != nullptr || a.act != ACT_NONE || a.pad_mode != PAD_ZERO || a.res != nullptr || a.fold != nullptr ||
         a.Hs != a.Ho || a.Ws != a.Wo || a.Hi != 2 * a.Ho || a.Wi != 2 * a.Wo || (a.Wo & 15) || a.Ho < 8 || (a.x_ld & 7) || (a.y_ld & 7) ||
         a.ntaps != 9)
         return -1;
     if ((long)a.B * a.Ho * a.Wo < (1L << 18) || (long)a.Hi * a.Wi * a.x_ld >= (1L << 30)) return -1;
-    for (int t = 0; t < 9; ++t) {    // Conv2d(k=3, s=2, p=1): tap t = (ky, kx) reads input (2 oy + ky - 1, 2 ox + kx - 1), weight t
-        const int tw = a.taps[t];
-        if ((tw & 0xff) - 64 != t / 3 - 1 || ((tw >> 8) & 0xff) - 64 != t % 3 - 1 || (tw >> 16) != t) return -1;
-    }
+    if (!taps_conv3x3_s2(a.taps)) return -1;
     StripS2Args s;
     s.x = (const bf16_t*)a.x; s.w = (const bf16_t*)a.w; s.y = (bf16_t*)a.y; s.stats = stats;
     s.B = a.B; s.Ho = a.Ho; s.Wo = a.Wo; s.x_ld = a.x_ld; s.y_ld = a.y_ld; s.w_tap_stride = a.w_tap_stride;
     s.nstrips = a.Wo / 16;
-    const int n_cu = ctg_cu_count();
-    static const int band_env = getenv("CTG_STRIPS2_BAND") ? atoi(getenv("CTG_STRIPS2_BAND")) : 0;     // A/B knob
     // two workgroups per CU are resident (registers): bands so that the grid fills the chip once
-    long nb = (2L * n_cu) / ((long)a.B * s.nstrips);
-    if (nb < 1) nb = 1;
-    int band = (int)((a.Ho + nb - 1) / nb);
-    if (band < 8) band = 8;
-    if (band_env >= 8) band = band_env;      // (the caller sized the moments buffer for >= 8-row bands)
-    s.band_rows = band;
-    s.nbands = (a.Ho + band - 1) / band;
-    // the caller sized the moments buffer for ceil(Ho / 8) x ceil(Wo / 16) slabs per sample
+    const BandPlan bp = band_plan(a.Ho, 8, 2L * ctg_cu_count(), (long)a.B * s.nstrips, ctg_knobs().strips2_band);
+    s.band_rows = bp.band_rows;
+    s.nbands = bp.nbands;
     if (stats != nullptr && slabs_out != nullptr) *slabs_out = s.nbands * s.nstrips;
-    static unsigned long long attr_mask = 0;       // per device
-    {
-        const int rc = ctg_lds_attr_once((const void*)conv_strips2_64_128_kernel, STRIPS_SMEM, &attr_mask);
-        if (rc != CTG_OK) return rc;
-    }
-    const dim3 grid((unsigned)((long)a.B * s.nbands * s.nstrips));
-    hipLaunchKernelGGL(conv_strips2_64_128_kernel, grid, dim3(256), STRIPS_SMEM, st, s);
-    return ctg_launch_status();
+    return launch_lds<conv_strips2_64_128_kernel>(dim3((unsigned)((long)a.B * s.nbands * s.nstrips)), dim3(256), STRIPS_SMEM, st, s);
 }

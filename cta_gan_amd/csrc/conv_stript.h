@@ -269,47 +269,21 @@ __global__ __launch_bounds__(256, 2) void conv_stript_128_64_kernel(const StripT
 
 // returns -1 when the launch is not this kernel's shape: a = the ConvArgs ctg_conv_igemm_classes built (4 classes)
 static int launch_stript(const ConvArgs& a, hipStream_t st, int* tiles_out) {
-    static const bool off = getenv("CTG_NO_STRIPT") != nullptr;      // A/B switch (scripts/ab.sh)
-    if (off || a.ncls != 4 || a.Cin != 128 || a.Cout != 64 || a.os != 2 || a.is != 1 || a.bias != nullptr || a.act != ACT_NONE ||
+    if (ctg_knobs().no_stript || a.ncls != 4 || a.Cin != 128 || a.Cout != 64 || a.os != 2 || a.is != 1 || a.bias != nullptr || a.act != ACT_NONE ||
         a.pad_mode != PAD_ZERO || a.Hs != a.Hi || a.Ws != a.Wi || a.Ho != 2 * a.Hi || a.Wo != 2 * a.Wi || (a.x_ld & 7) || (a.y_ld & 7))
         return -1;
     if ((long)a.B * a.Hi * a.Wi < (1L << 18) || a.Hi < 16 || a.Wi < 16) return -1;
-    // the class / tap structure of ConvTranspose2d(k=3, s=2, p=1, output_padding=1): engine._convT_classes(3, 1)
-    static const int want_n[4] = {1, 2, 2, 4}, want_oy[4] = {0, 0, 1, 1}, want_ox[4] = {0, 1, 0, 1};
-    static const int want_t[9][3] = {{0, 0, 4}, {0, 1, 3}, {0, 0, 5}, {1, 0, 1}, {0, 0, 7}, {1, 1, 0}, {1, 0, 2}, {0, 1, 6}, {0, 0, 8}};
-    int t = 0;
-    for (int q = 0; q < 4; ++q) {
-        if (a.c_ntaps[q] != want_n[q] || a.c_oy0[q] != want_oy[q] || a.c_ox0[q] != want_ox[q] || a.c_tap0[q] != t) return -1;
-        for (int k = 0; k < want_n[q]; ++k, ++t) {
-            const int tw = a.taps[t];
-            if ((tw & 0xff) - 64 != want_t[t][0] || ((tw >> 8) & 0xff) - 64 != want_t[t][1] || (tw >> 16) != want_t[t][2]) return -1;
-        }
-    }
+    if (!taps_convT3x3_classes(a.c_ntaps, a.c_oy0, a.c_ox0, a.c_tap0, a.taps)) return -1;
     StripTArgs s;
     s.x = (const bf16_t*)a.x; s.w = (const bf16_t*)a.w; s.y = (bf16_t*)a.y; s.stats = a.stats;
     s.B = a.B; s.Hi = a.Hi; s.Wi = a.Wi; s.x_ld = a.x_ld; s.y_ld = a.y_ld; s.w_tap_stride = a.w_tap_stride;
     s.nstrips = (a.Wi + 15) / 16;
-    static const int xcd_env = getenv("CTG_STRIPT_XCD") ? atoi(getenv("CTG_STRIPT_XCD")) : 1;      // A/B knob
-    s.xcd = xcd_env;
-    const int n_cu = ctg_cu_count();
-    static const int band_env = getenv("CTG_STRIPT_BAND") ? atoi(getenv("CTG_STRIPT_BAND")) : 0;      // A/B knob
+    s.xcd = ctg_knobs().stript_xcd;
     // two workgroups per CU are resident (registers): bands so that the grid fills the chip once (measured at B = 16, 256^2:
     // 1 / 2 / 4 / 8 bands per strip 240 / 205 / 222 / 232 us)
-    long nb = (2L * n_cu) / ((long)a.B * s.nstrips);
-    if (nb < 1) nb = 1;
-    int band = (int)((a.Hi + nb - 1) / nb);
-    if (band < 16) band = 16;
-    if (band_env >= 8) band = band_env;      // (the caller sized the moments buffer for >= 8-row bands)
-    s.band_rows = band;
-    s.nbands = (a.Hi + band - 1) / band;
+    const BandPlan bp = band_plan(a.Hi, 16, 2L * ctg_cu_count(), (long)a.B * s.nstrips, ctg_knobs().stript_band);
+    s.band_rows = bp.band_rows;
+    s.nbands = bp.nbands;
     if (tiles_out != nullptr) *tiles_out = s.nbands * s.nstrips;
-    const int smem = STRIPT_SMEM;
-    static unsigned long long attr_mask = 0;       // per device
-    {
-        const int rc = ctg_lds_attr_once((const void*)conv_stript_128_64_kernel, smem, &attr_mask);
-        if (rc != CTG_OK) return rc;
-    }
-    const dim3 grid((unsigned)((long)a.B * s.nbands * s.nstrips));
-    hipLaunchKernelGGL(conv_stript_128_64_kernel, grid, dim3(256), smem, st, s);
-    return ctg_launch_status();
+    return launch_lds<conv_stript_128_64_kernel>(dim3((unsigned)((long)a.B * s.nbands * s.nstrips)), dim3(256), STRIPT_SMEM, st, s);
 }

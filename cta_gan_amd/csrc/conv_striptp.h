@@ -440,49 +440,22 @@ __global__ __launch_bounds__(512, 1) void conv_striptp_128_64_kernel(const Strip
 // returns -1 when the launch is not this kernel's shape: a = the ConvArgs ctg_conv_igemm_classes built for a split-pair launch
 // (4 classes; a.Cin = 2 x the channel count, a.pair_lo = the input's plane distance)
 static int launch_striptp(const ConvArgs& a, hipStream_t st, int* tiles_out) {
-    static const bool off = getenv("CTG_NO_STRIPTP") != nullptr;      // A/B switch
-    if (off || a.ncls != 4 || a.pair_lo == 0 || a.Cin != 256 || a.Cout != 64 || a.os != 2 || a.is != 1 || a.bias != nullptr ||
+    if (ctg_knobs().no_striptp || a.ncls != 4 || a.pair_lo == 0 || a.Cin != 256 || a.Cout != 64 || a.os != 2 || a.is != 1 || a.bias != nullptr ||
         a.act != ACT_NONE || a.pad_mode != PAD_ZERO || a.Hs != a.Hi || a.Ws != a.Wi || a.Ho != 2 * a.Hi || a.Wo != 2 * a.Wi ||
         (a.x_ld & 15) || (a.y_ld & 15) || a.x_ld < 256 || a.y_ld < 128)
         return -1;
     if ((long)a.B * a.Hi * a.Wi < (1L << 18) || a.Hi < 16 || a.Wi < 16) return -1;
-    // the class / tap structure of ConvTranspose2d(k=3, s=2, p=1, output_padding=1): engine._convT_classes(3, 1)
-    static const int want_n[4] = {1, 2, 2, 4}, want_oy[4] = {0, 0, 1, 1}, want_ox[4] = {0, 1, 0, 1};
-    static const int want_t[9][3] = {{0, 0, 4}, {0, 1, 3}, {0, 0, 5}, {1, 0, 1}, {0, 0, 7}, {1, 1, 0}, {1, 0, 2}, {0, 1, 6}, {0, 0, 8}};
-    int t = 0;
-    for (int q = 0; q < 4; ++q) {
-        if (a.c_ntaps[q] != want_n[q] || a.c_oy0[q] != want_oy[q] || a.c_ox0[q] != want_ox[q] || a.c_tap0[q] != t) return -1;
-        for (int k = 0; k < want_n[q]; ++k, ++t) {
-            const int tw = a.taps[t];
-            if ((tw & 0xff) - 64 != want_t[t][0] || ((tw >> 8) & 0xff) - 64 != want_t[t][1] || (tw >> 16) != want_t[t][2]) return -1;
-        }
-    }
+    if (!taps_convT3x3_classes(a.c_ntaps, a.c_oy0, a.c_ox0, a.c_tap0, a.taps)) return -1;
     StripTPArgs s;
     s.x = (const bf16_t*)a.x; s.w = (const bf16_t*)a.w; s.y = (bf16_t*)a.y; s.stats = a.stats;
     s.B = a.B; s.Hi = a.Hi; s.Wi = a.Wi; s.x_ld = a.x_ld; s.y_ld = a.y_ld; s.w_tap_stride = a.w_tap_stride;
     s.x_lo = a.pair_lo; s.y_lo = a.y_ld / 2;
     s.nstrips = (a.Wi + 15) / 16;
-    static const int xcd_env = getenv("CTG_STRIPT_XCD") ? atoi(getenv("CTG_STRIPT_XCD")) : 1;      // A/B knob
-    s.xcd = xcd_env;
-    const int n_cu = ctg_cu_count();
-    static const int band_env = getenv("CTG_STRIPTP_BAND") ? atoi(getenv("CTG_STRIPTP_BAND")) : 0;      // A/B knob
-    static const int wgs_per_cu = getenv("CTG_STRIPTP_WGS") ? atoi(getenv("CTG_STRIPTP_WGS")) : 1;      // A/B knob
-    // one 8-wave workgroup per CU is resident (registers): bands so that the grid fills the chip once
-    long nb = ((long)wgs_per_cu * n_cu) / ((long)a.B * s.nstrips);
-    if (nb < 1) nb = 1;
-    int band = (int)((a.Hi + nb - 1) / nb);
-    if (band < 16) band = 16;
-    if (band_env >= 8) band = band_env;      // (the caller sized the moments buffer for >= 8-row bands, 4 slots per 8 x 16 tile)
-    s.band_rows = band;
-    s.nbands = (a.Hi + band - 1) / band;
+    s.xcd = ctg_knobs().stript_xcd;
+    // one 8-wave workgroup per CU is resident (registers; CTG_STRIPTP_WGS: A/B knob): bands so that the grid fills the chip once
+    const BandPlan bp = band_plan(a.Hi, 16, (long)ctg_knobs().striptp_wgs * ctg_cu_count(), (long)a.B * s.nstrips, ctg_knobs().striptp_band);
+    s.band_rows = bp.band_rows;
+    s.nbands = bp.nbands;
     if (tiles_out != nullptr) *tiles_out = 2 * s.nbands * s.nstrips;
-    const int smem = STRIPTP_SMEM;
-    static unsigned long long attr_mask = 0;       // per device
-    {
-        const int rc = ctg_lds_attr_once((const void*)conv_striptp_128_64_kernel, smem, &attr_mask);
-        if (rc != CTG_OK) return rc;
-    }
-    const dim3 grid((unsigned)((long)a.B * s.nbands * s.nstrips));
-    hipLaunchKernelGGL(conv_striptp_128_64_kernel, grid, dim3(512), smem, st, s);
-    return ctg_launch_status();
+    return launch_lds<conv_striptp_128_64_kernel>(dim3((unsigned)((long)a.B * s.nbands * s.nstrips)), dim3(512), STRIPTP_SMEM, st, s);
 }

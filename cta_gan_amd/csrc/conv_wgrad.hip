@@ -17,7 +17,7 @@
 //         K order inside a 32-pixel step is permuted identically for A and B
 //   fp32: ds_read_b32 (one float per lane is exactly the 16x16x4 operand)
 #include <stdlib.h>
-#include "common.h"
+#include "conv_dispatch.h"      // common.h + the host-side tap-window helpers and the CTG_* switches
 
 struct WgradArgs {
     const void* g;
@@ -879,8 +879,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_s2m_kernel(const WgHaloArgs
 
 // -1: shape not served (the caller launches the four polyphase components one by one)
 static int launch_wg_s2m(const WgHaloArgs& a, hipStream_t st) {
-    static const bool off = getenv("CTG_NO_WG_S2M") != nullptr;      // A/B switch
-    if (off || a.Mc % 64 || a.Nc % 64 || a.phase_split) return -1;
+    if (ctg_knobs().no_wg_s2m || a.Mc % 64 || a.Nc % 64 || a.phase_split) return -1;
     constexpr int BM = 64, BN = 64;
     constexpr int smem = (2 * WGH_TH * WGH_TW * (BM / 8) + 2 * ((((WGH_TH + 1) * (WGH_TW + 1) * (BN / 8)) + 63) & ~63)) * 16;
     static_assert(smem <= 80 * 1024, "two workgroups per CU");
@@ -998,45 +997,37 @@ extern "C" int ctg_conv_wgrad(int dtype, const void* g, const void* x, float* pa
     hipStream_t st = (hipStream_t)stream;
     // split-pair operands on a small grid: one workgroup per sweep (3 x the partials: return value 3 tells the caller)
     const int bm_ = Mc % 64 == 0 ? 64 : Mc % 32 == 0 ? 32 : 16, bn_ = Nc % 64 == 0 ? 64 : 32;
-    static const bool nosplit = getenv("CTG_NO_WG_PHASE_SPLIT") != nullptr;      // A/B switch
-    const int split = (pair && !nosplit && (long)(Mc / bm_) * (Nc / bn_) * B * a.sps < 384) ? 1 : 0;
+    const int split = (pair && !ctg_knobs().no_wg_phase_split && (long)(Mc / bm_) * (Nc / bn_) * B * a.sps < 384) ? 1 : 0;
     // ---- bf16, stride 1, full kh x kw tap window in row-major order: halo-resident kernel
     // (a single tap -- the 1x1 convs of the registration U-Net -- is a 1x1 "window": same kernel, no halo overlap)
-    if (dtype == DT_BF16 && is == 1 && Hs >= WGH_TH && Ws >= WGH_TW && getenv("CTG_NO_HALO") == nullptr &&
-        (ntaps > 1 || getenv("CTG_NO_WG_1TAP") == nullptr) &&
+    if (dtype == DT_BF16 && is == 1 && Hs >= WGH_TH && Ws >= WGH_TW && !ctg_knobs().no_halo &&
+        (ntaps > 1 || !ctg_knobs().no_wg_1tap) &&
         (long)Hi * Wi * x_ld < (1L << 31) && (long)Hs * Ws * g_ld < (1L << 31)) {
-        int dymin = 127, dymax = -128, dxmin = 127, dxmax = -128;
-        for (int t = 0; t < ntaps; ++t) {
-            const int dy = (a.taps[t] & 0xff) - 64, dx = ((a.taps[t] >> 8) & 0xff) - 64;
-            dymin = dy < dymin ? dy : dymin; dymax = dy > dymax ? dy : dymax;
-            dxmin = dx < dxmin ? dx : dxmin; dxmax = dx > dxmax ? dx : dxmax;
-        }
-        const int kh = dymax - dymin + 1, kw = dxmax - dxmin + 1;
+        const TapWindow win = tap_window(a.taps, ntaps);
+        const int kh = win.kh(), kw = win.kw();
         bool rowmajor = ntaps == kh * kw;
-        for (int t = 0; rowmajor && t < ntaps; ++t) {
-            const int dy = (a.taps[t] & 0xff) - 64, dx = ((a.taps[t] >> 8) & 0xff) - 64;
-            rowmajor = (dy == dymin + t / kw) && (dx == dxmin + t % kw);
-        }
+        for (int t = 0; rowmajor && t < ntaps; ++t)
+            rowmajor = (tap_dy(a.taps[t]) == win.dy0() + t / kw) && (tap_dx(a.taps[t]) == win.dx0() + t % kw);
         if (rowmajor) {
             WgHaloArgs h;
             h.g = g; h.x = x; h.part = part;
             h.B = B; h.Hs = Hs; h.Ws = Ws; h.Mc = Mc; h.g_ld = g_ld;
             h.Hi = Hi; h.Wi = Wi; h.Nc = Nc; h.x_ld = x_ld;
             h.pad_mode = pad_mode; h.sps = a.sps; h.ntaps = ntaps;
-            h.kw = kw; h.khb = (kh * kw <= 9 || Mc == 16) ? kh : 1; h.dy0 = dymin; h.dx0 = dxmin;
-            h.prefetch = getenv("CTG_WG_NOPREFETCH") == nullptr;
-            h.xcd = getenv("CTG_WG_NOXCD") == nullptr;
+            h.kw = kw; h.khb = (kh * kw <= 9 || Mc == 16) ? kh : 1; h.dy0 = win.dy0(); h.dx0 = win.dx0();
+            h.prefetch = !ctg_knobs().wg_noprefetch;
+            h.xcd = !ctg_knobs().wg_noxcd;
             h.is = 1; h.py = 0; h.px = 0; h.gtaps = ntaps;
             h.phases = pair ? 3 : 1; h.g_lo = g_ld / 2; h.x_lo = x_ld / 2; h.phase_split = split;
-            { static const int nr = getenv("CTG_WG_NO_REUSE") != nullptr; h.no_reuse = nr; }
+            h.no_reuse = ctg_knobs().wg_no_reuse;
             for (int t = 0; t < ntaps; ++t) h.tmap[t] = t;
             const int rc = launch_wgh_any(h, st);
             if (rc != -1) return (rc == 0 && split) ? 3 : rc;
         }
     }
     // ---- bf16, input stride 2: one halo launch per polyphase component of X (each a small stride-1 window)
-    if (dtype == DT_BF16 && is == 2 && Hs >= WGH_TH && Ws >= WGH_TW && getenv("CTG_NO_HALO") == nullptr &&
-        getenv("CTG_NO_WG_S2") == nullptr && (long)Hi * Wi * x_ld < (1L << 31) && (long)Hs * Ws * g_ld < (1L << 31) &&
+    if (dtype == DT_BF16 && is == 2 && Hs >= WGH_TH && Ws >= WGH_TW && !ctg_knobs().no_halo &&
+        !ctg_knobs().no_wg_s2 && (long)Hi * Wi * x_ld < (1L << 31) && (long)Hs * Ws * g_ld < (1L << 31) &&
         pad_mode == PAD_ZERO) {
         WgHaloArgs ph[4];
         bool ok = true;
@@ -1044,33 +1035,32 @@ extern "C" int ctg_conv_wgrad(int dtype, const void* g, const void* x, float* pa
         for (int p = 0; p < 4 && ok; ++p) {
             const int py = p >> 1, px = p & 1;
             WgHaloArgs& h = ph[nph];
-            int cnt = 0, dymin = 127, dymax = -128, dxmin = 127, dxmax = -128;
+            int cnt = 0;
+            TapWindow win;      // in phase coordinates
             for (int t = 0; t < ntaps; ++t) {
-                const int dy = (a.taps[t] & 0xff) - 64, dx = ((a.taps[t] >> 8) & 0xff) - 64;
+                const int dy = tap_dy(a.taps[t]), dx = tap_dx(a.taps[t]);
                 if (((dy & 1) != py) || ((dx & 1) != px)) continue;
-                const int qy = (dy - py) / 2, qx = (dx - px) / 2;       // exact: dy - py is even
-                dymin = qy < dymin ? qy : dymin; dymax = qy > dymax ? qy : dymax;
-                dxmin = qx < dxmin ? qx : dxmin; dxmax = qx > dxmax ? qx : dxmax;
+                win.add((dy - py) / 2, (dx - px) / 2);       // exact: dy - py is even
                 h.tmap[cnt++] = t;
             }
             if (cnt == 0) continue;
-            const int kh = dymax - dymin + 1, kw = dxmax - dxmin + 1;
+            const int kh = win.kh(), kw = win.kw();
             ok = cnt == kh * kw;
             for (int i = 0; ok && i < cnt; ++i) {   // row-major full window in phase coordinates
                 const int tw = a.taps[h.tmap[i]];
-                const int qy = (((tw & 0xff) - 64) - py) / 2, qx = ((((tw >> 8) & 0xff) - 64) - px) / 2;
-                ok = (qy == dymin + i / kw) && (qx == dxmin + i % kw);
+                const int qy = (tap_dy(tw) - py) / 2, qx = (tap_dx(tw) - px) / 2;
+                ok = (qy == win.dy0() + i / kw) && (qx == win.dx0() + i % kw);
             }
             h.g = g; h.x = x; h.part = part;
             h.B = B; h.Hs = Hs; h.Ws = Ws; h.Mc = Mc; h.g_ld = g_ld;
             h.Hi = Hi; h.Wi = Wi; h.Nc = Nc; h.x_ld = x_ld;
             h.pad_mode = pad_mode; h.sps = a.sps; h.ntaps = cnt; h.gtaps = ntaps;
-            h.kw = kw; h.khb = kh; h.dy0 = dymin; h.dx0 = dxmin;
+            h.kw = kw; h.khb = kh; h.dy0 = win.dy0(); h.dx0 = win.dx0();
             h.is = 2; h.py = py; h.px = px;
             h.phases = pair ? 3 : 1; h.g_lo = g_ld / 2; h.x_lo = x_ld / 2; h.phase_split = split;
-            { static const int nr = getenv("CTG_WG_NO_REUSE") != nullptr; h.no_reuse = nr; }
-            h.prefetch = getenv("CTG_WG_NOPREFETCH") == nullptr;
-            h.xcd = getenv("CTG_WG_NOXCD") == nullptr;
+            h.no_reuse = ctg_knobs().wg_no_reuse;
+            h.prefetch = !ctg_knobs().wg_noprefetch;
+            h.xcd = !ctg_knobs().wg_noxcd;
             // every configuration this phase needs must exist before anything is launched
             const int bm = h.Mc % 64 == 0 ? 64 : h.Mc % 32 == 0 ? 32 : 16, bn = h.Nc % 64 == 0 ? 64 : 32;
             ok = ok && bm >= 32 && !(bm == 32 && bn == 32) && (cnt == 1 || cnt == 2 || cnt == 4) && kw <= 2 && kh <= 2;
@@ -1079,12 +1069,7 @@ extern "C" int ctg_conv_wgrad(int dtype, const void* g, const void* x, float* pa
         }
         if (ok && covered == ntaps && ntaps == 9 && nph == 4 && !split) {
             // a stride-2 3x3 window in row-major order: all four polyphase components in ONE launch (G fetched once per tile)
-            bool std33 = true;
-            for (int t = 0; t < 9; ++t) {
-                const int dy = (a.taps[t] & 0xff) - 64, dx = ((a.taps[t] >> 8) & 0xff) - 64;
-                std33 = std33 && dy == t / 3 - 1 && dx == t % 3 - 1;
-            }
-            if (std33) {
+            if (taps_3x3(a.taps, false)) {
                 WgHaloArgs h = ph[0];
                 h.ntaps = 9; h.gtaps = 9; h.kw = 2; h.khb = 2; h.dy0 = -1; h.dx0 = -1; h.py = 0; h.px = 0;
                 const int rc = launch_wg_s2m(h, st);

@@ -14,6 +14,7 @@
 // fold_load(), which adds the mirrored border rows/columns back onto the
 // interior (the transpose of nn.ReflectionPad2d), so no separate pass exists.
 #include "common.h"
+#include "ctg_knobs.h"
 
 // IN_EPS: common.h
 #define MAX_SLABS 128
@@ -516,7 +517,7 @@ static inline dim3 pix_grid(int dtype, int B, int HW, int C) {
     const int pl = 256 / cpp;
     // 16 pixels per lane; fewer while that leaves the chip under ~2048 workgroups (small batches: a lane's trips are dependent
     // loads, and 128 workgroups of 16 trips each were latency-bound at 18 us for 17 MB)
-    static const bool no_smallb = getenv("CTG_NO_SMALLB") != nullptr;      // A/B switch
+    const bool no_smallb = ctg_knobs().no_smallb;      // A/B switch
     int per = 16;
     if (!no_smallb) while (per > 2 && (((long)HW + pl * per - 1) / (pl * per)) * B < 2048) per >>= 1;
     long bx = ((long)HW + pl * per - 1) / (pl * per);

@@ -59,7 +59,7 @@ class Tape:
 # ----------------------------------------------------------------------------- gradient plumbing
 # Developer experiment ("split forward, bf16 backward"): numerically emulate a backward whose gradient tensors
 # are stored in bf16 and whose backward-data convs use the bf16 half of the weights, inside the split-pair mode and with its kernels
-# (so the cost is unchanged; only the arithmetic is what the cheaper backward would compute).  1 = gradients only, 2 = also w_lo = 0.
+# (so the cost is unchanged; only the arithmetic is what the cheaper backward would compute).  Any non-zero value switches it on.
 _EMU_BF16_BWD = int(os.environ.get("CTG_EMU_BF16_BWD", "0") or 0)
 
 

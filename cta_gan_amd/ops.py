@@ -33,6 +33,27 @@ def epc(dtype) -> int:
 DT_PAIR = 2
 DT_MIX = 3
 
+# ---- developer switches (scripts/README.md has the table): every CTG_* variable this module reads at import, one line each; the
+# comments that explain a switch stand next to the code it gates.  None changes what a default run computes.  Read at call time
+# instead, because tests and scripts flip them inside a running process: CTG_NO_COUT1, CTG_CORR_3RUN, CTG_NO_TAIL7, CTG_NO_SMALLCIN.
+_env = os.environ.get
+_NO_NIE = bool(_env("CTG_NO_NIE"))                          # conv + InstanceNorm in one launch: off (also read by csrc/ctg_knobs.h)
+NIE_POISON = bool(_env("CTG_NIE_POISON"))                   # fill the moment buffer of a fused launch with NaNs first (tests)
+NIE_MAX_WGS = int(_env("CTG_NIE_MAX_WGS", "1024"))          # most workgroups of a fused launch, bf16
+NIE_MAX_WGS_PAIR = int(_env("CTG_NIE_MAX_WGS_PAIR", "2048"))     # ... split pair
+NIE_BUDGET = int(_env("CTG_NIE_BUDGET", "0"))               # polls before a waiting workgroup gives up (0: the library's 2^22, ~1 s); tests shrink it
+NIE_SHARE = max(1, int(_env("CTG_NIE_SHARE", "2") or 2))    # fused launches that may wait at the same time (also csrc/ctg_knobs.h)
+_TH8_WGS = 0 if _env("CTG_NO_TH8") is not None else int(_env("CTG_TH8_WGS", "384"))      # 8-row halo tiles below this many workgroups (csrc/conv_dispatch.h: halo_th8)
+_NO_HALO = bool(_env("CTG_NO_HALO"))                        # no halo-resident kernels (also csrc/ctg_knobs.h) ...
+_NO_EPI_FUSE = bool(_env("CTG_NO_EPI_FUSE"))                # ... or only no residual / fold epilogues on them
+_NO_WG_GROUPS_FIX = bool(_env("CTG_NO_WG_GROUPS_FIX"))      # weight gradient: A/B switches of the slab-count fixes
+_WG_S2_FIX = not _env("CTG_NO_WG_S2_FIX")
+_WG_FIX_BELOW = int(_env("CTG_WG_FIX_BELOW", "512"))        # (256: the first form of the fix)
+_NO_SMALLB = bool(_env("CTG_NO_SMALLB"))                    # small-batch slab counts off (also csrc/norm_act.hip: pix_grid)
+_FIN_FUSE = bool(_env("CTG_FIN_FUSE"))                      # finalize fused into the elementwise kernels (round-3 experiment)
+_NO_KXW = bool(_env("CTG_NO_KXW"))                          # first-layer convs without the kx-window weight layout
+DETERMINISTIC = bool(_env("CTG_DETERMINISTIC"))             # warp backward in 64-bit fixed point (bench.py / tests assign it)
+
 
 def dtc(t) -> int:
     """dtype code of an activation tensor for the C ABI: 0 fp32, 1 bf16, 2 split pair (see PAIR)."""
@@ -306,21 +327,13 @@ class ConvEpilogue(ctypes.Structure):
 # InstanceNorm in the conv epilogue (ctg_conv_epilogue.nie_*): monotonic arrival counters, one buffer per (device, stream, group
 # size), zeroed once and owned by the kernels afterwards
 _NIE_SYNC = {}
-_NO_NIE = bool(os.environ.get("CTG_NO_NIE"))      # A/B switch
 NIE_GROUPS = 4096
-
-
-NIE_POISON = bool(os.environ.get("CTG_NIE_POISON"))      # fill the moment buffer of a fused launch with NaNs first (tests)
-NIE_MAX_WGS = int(os.environ.get("CTG_NIE_MAX_WGS", "1024"))
-NIE_MAX_WGS_PAIR = int(os.environ.get("CTG_NIE_MAX_WGS_PAIR", "2048"))
-NIE_BUDGET = int(os.environ.get("CTG_NIE_BUDGET", "0"))      # polls before a waiting workgroup gives up (0: the library's 2^22, ~1 s); tests shrink it
-# launches that may wait for their groups at the same time (streams of this process, processes sharing the card); mirrors the
+# NIE_SHARE: launches that may wait for their groups at the same time (streams of this process, processes sharing the card); mirrors the
 # library's residency test (csrc/conv_halo.h launch_halo_cfg reads the same variable and the kernel's real occupancy).  Default 2:
 # the trainers issue these launches from ONE stream (the D step's no-grad generator forward), so one is in flight per process; two
 # leaves room for a second process on the card and keeps the 8-row-tile launches of batch sizes 1-2 (256 workgroups per sample)
 # fusable.  More tenants per card: CTG_NIE_SHARE=<n> (a launch that cannot be guaranteed runs unfused; one that is starved anyway
 # ends in nie_check's RuntimeError, not in silent NaNs).
-NIE_SHARE = max(1, int(os.environ.get("CTG_NIE_SHARE", "2") or 2))
 NIE_SLOTS = 512                                               # 2 workgroups of the 128-channel-tile kernel per CU x 256 CUs
 
 
@@ -425,16 +438,23 @@ def conv_in_fusable(x, cin, cout, k, stride, hs, ws):
         and _nie_sync(x.device, tiles) is not None
 
 
-_TH8_WGS = 0 if os.environ.get("CTG_NO_TH8") is not None else int(os.environ.get("CTG_TH8_WGS", "384"))
-
-
 def _nie_tiles(x, cout, hs, ws):
     """Workgroups per statistics group = spatial tiles per sample of the halo kernel: 16x16 pixels, 8x16 for the small bf16 grids
-    csrc/conv_halo.h (launch_halo_t) serves with its 8-row variant."""
+    csrc/conv_halo.h (launch_halo_t) serves with its 8-row variant: the rule is halo_th8 of csrc/conv_dispatch.h, and
+    ctg_conv_igemm answers a count that differs from its own with CTG_EINVAL."""
     tiles = ((hs + 15) // 16) * ((ws + 15) // 16)
     if not is_pair(x) and tiles * ((cout + 127) // 128) * x.shape[0] < _TH8_WGS:
-        tiles = ((hs + 7) // 8) * ((ws + 15) // 16)
+        tiles = moments_slabs(hs, ws)
     return tiles
+
+
+def moments_slabs(hs, ws):
+    """Most partial-moment slabs per sample a conv launch on an hs x ws grid writes (one class of a merged parity-class launch):
+    one per 8 x 16 pixels.  Every kernel stays within it: the halo kernel's tiles are 8 or 16 rows of 16 columns
+    (csrc/conv_halo.h, launch_halo_cfg), the strip kernels' bands are >= 8 rows of one 16-column strip (csrc/conv_dispatch.h,
+    band_plan), and the gather kernel emits moments only while its M tiles are no more than this (csrc/conv_igemm.hip,
+    ctg_conv_igemm: `bound`)."""
+    return ((hs + 7) // 8) * ((ws + 15) // 16)
 
 
 def conv_igemm(x, w_packed, w_npad, y, bias, cout, hs, ws, oy0, ox0, os_, is_, pad_mode, act, taps, want_stats=False,
@@ -478,7 +498,7 @@ def conv_igemm(x, w_packed, w_npad, y, bias, cout, hs, ws, oy0, ox0, os_, is_, p
         tkey = "fwd_in" if in_fuse is not None else "fwd" if (res is None and fold is None) else "bwd_data"
     part, slabs = None, ctypes.c_int(0)
     if want_stats and bias is None and act == ACT_NONE and cout > 16:
-        part = torch.empty(b * ((hs + 7) // 8) * ((ws + 15) // 16) * cout * 2, dtype=torch.float32, device=x.device)
+        part = torch.empty(b * moments_slabs(hs, ws) * cout * 2, dtype=torch.float32, device=x.device)
     epi = None
     nie_out = None
     if in_fuse is not None:
@@ -496,7 +516,7 @@ def conv_igemm(x, w_packed, w_npad, y, bias, cout, hs, ws, oy0, ox0, os_, is_, p
             zb, zh, zw, zc, z_ld = _nhwc(z)
             assert (zb, zh, zw, zc) == (b, hs, ws, cout) and z.dtype == y.dtype == torch.bfloat16 and not want_stats
             assert is_pair(z) == pair_in
-            part = torch.empty(b * ((hs + 7) // 8) * ((ws + 15) // 16) * cout * 2, dtype=torch.float32, device=x.device)   # sized for 8-row tiles
+            part = torch.empty(b * moments_slabs(hs, ws) * cout * 2, dtype=torch.float32, device=x.device)
             epi.bz, epi.bmean, epi.brstd, epi.bstats, epi.bz_ld, epi.bact = _p(z), _p(mean), _p(rstd), _p(part), z_ld, zact
     tbytes = None
     if KERNEL_EVENTS is not None and tkey is None and cin0 == 32 and cout == 32 and len(taps) == 9 and not frame \
@@ -558,7 +578,7 @@ def conv_igemm_classes(x, w_packed, w_npad, y, bias, cout, hs, ws, classes, pad_
     i4 = ctypes.c_int * 4
     part, slabs = None, ctypes.c_int(0)
     if want_stats and bias is None and act == ACT_NONE:
-        part = torch.empty(b * 4 * ((hs + 7) // 8) * ((ws + 15) // 16) * cout * 2, dtype=torch.float32, device=x.device)      # (8-row tiles possible)
+        part = torch.empty(b * 4 * moments_slabs(hs, ws) * cout * 2, dtype=torch.float32, device=x.device)
     tkey = tbytes = None
     if KERNEL_EVENTS is not None and cin == 128 and cout == 64 and len(taps) == 9 and bias is None and hs * ws >= 256 * 256:
         # the 128 -> 64 channel stride-2 transposed conv (u2 forward, d1 backward-data) on csrc/conv_stript.h: in + out once
@@ -587,7 +607,7 @@ def conv_igemm_classes(x, w_packed, w_npad, y, bias, cout, hs, ws, classes, pad_
 def conv_fusable(cout, hs, ws):
     """Launches whose epilogue can take `res` / `fold`: the shapes ctg_conv_igemm hands to the halo-resident kernel
     (full-window stride-1 taps are the caller's business)."""
-    return cout > 16 and hs >= 16 and ws >= 16 and not os.environ.get("CTG_NO_HALO") and not os.environ.get("CTG_NO_EPI_FUSE")
+    return cout > 16 and hs >= 16 and ws >= 16 and not _NO_HALO and not _NO_EPI_FUSE
 
 
 def weight_pack(master, dtype, ntaps, nreal, kreal, npad, kpad, sn, sk, stp):
@@ -621,11 +641,6 @@ def weight_pack_multi(jobs):
         lg(*[j[7] for j in jobs]), lg(*[j[8] for j in jobs]), lg(*[j[9] for j in jobs]),
         it(*[j[3] for j in jobs]), it(*[j[4] for j in jobs]), it(*[j[2] for j in jobs]),
         it(*[j[5] for j in jobs]), it(*[j[6] for j in jobs]), _stream()), "ctg_weight_pack_multi")
-
-
-_NO_WG_GROUPS_FIX = bool(os.environ.get("CTG_NO_WG_GROUPS_FIX"))      # A/B switch
-_WG_S2_FIX = not os.environ.get("CTG_NO_WG_S2_FIX")      # A/B switch
-_WG_FIX_BELOW = int(os.environ.get("CTG_WG_FIX_BELOW", "512"))      # A/B knob (256: the first form of the fix)
 
 
 def conv_wgrad(g, x, taps, is_, pad_mode, dst, mreal, nreal, sm, sn, stp, accumulate=False, target_blocks=768,
@@ -729,9 +744,6 @@ def wgrad_reduce_multi(jobs):
 
 
 # ---------------------------------------------------------------------------- norm / elementwise
-_NO_SMALLB = bool(os.environ.get("CTG_NO_SMALLB"))     # A/B switch (also read by csrc/norm_act.hip: pix_grid)
-
-
 def _nslabs(b, hw):
     if b < 16 and not _NO_SMALLB:
         # small batches (the reference's yaml ships batchSize 1): 64-pixel slabs, up to 128 per sample.  At B = 4 the 64 slabs x 4
@@ -781,7 +793,6 @@ FUSED_MAX_SLABS = 128      # csrc/norm_act.hip: partial counts the elementwise k
 # (interleaved A/B, B=16): 53.00 / 53.14 / 53.01 ms with it against 52.81 / 53.04 / 52.86 without -- the prologue has to be
 # amortised over a (sample, 64-channel group) strip, and 128-byte-per-pixel accesses stream at 4.2 TB/s where the full 512-byte
 # pixels of the plain kernels reach 5.2; what the ~100 saved launches per step gain, the slower passes lose.  CTG_FIN_FUSE=1.
-_FIN_FUSE = bool(os.environ.get("CTG_FIN_FUSE"))
 
 
 def fin_fusable(nslabs):
@@ -997,9 +1008,6 @@ def im2col_pack(s0, s1, k, stride, pad, pad_mode, dtype, kpad):
     _lib.check(lib.ctg_im2col_pack(dtc(out), _p(s0), _p(s1), cin, b, hi, wi, k, k, stride, pad, pad_mode, _p(out),
                                    ho, wo, kpad, _stream()), "ctg_im2col_pack")
     return out
-
-
-_NO_KXW = bool(os.environ.get("CTG_NO_KXW"))      # A/B switch
 
 
 def kxw_ok(cin, cout, k, stride, dtype):
@@ -1247,7 +1255,6 @@ def warp_fwd(src, flow):
 # Deterministic mode (tests / debugging; CTG_DETERMINISTIC=1 or ops.DETERMINISTIC = True): the one order-dependent kernel of the
 # step -- the float-atomic scatter of the warp backward (trainer/transformer.py:29, grid_sample's backward) -- runs in 64-bit
 # fixed point, so two runs of a step are bit-identical.  ~3 extra passes over 1-channel maps; off by default.
-DETERMINISTIC = bool(os.environ.get("CTG_DETERMINISTIC"))
 
 
 def warp_bwd(src, flow, gout, need_src, need_flow):

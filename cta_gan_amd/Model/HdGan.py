@@ -209,10 +209,14 @@ class DataPrefetcher:
     host).  The reference defines it and never uses it: its loop does three synchronous copies per step
     (trainer/HdTrainer.py:708-711).  Here the trainers' `train()` consume it, and the copy really is asynchronous: every
     tensor goes through one of TWO page-locked staging buffers per key (a pageable source makes `non_blocking=True` a
-    synchronous staged copy), so the H2D of batch i+1 runs on the copy stream while batch i trains."""
+    synchronous staged copy), so the H2D of batch i+1 runs on the copy stream while batch i trains.
+    `transform` (an extension; default None: nothing changes): a callable dict batch -> dict batch of device tensors that runs on
+    the copy stream right behind the H2D copies, inside the (start, end) events -- the trainers pass the `noise_level`
+    augmentation (trainer/augment.py), which then hides behind the previous step just as the copy does."""
 
-    def __init__(self, loader, device="cuda:0"):
+    def __init__(self, loader, device="cuda:0", transform=None):
         self.loader = iter(loader)
+        self.transform = transform
         self.device = torch.device(device)
         self.stream = torch.cuda.Stream(device=self.device)
         self._stage = [{}, {}]          # key -> pinned tensor, per slot
@@ -252,6 +256,8 @@ class DataPrefetcher:
             start.record()
             for k, h in host.items():
                 self.batch[k] = h.to(device=self.device, non_blocking=True)
+            if self.transform is not None:
+                self.batch = self.transform(self.batch)
             end.record()
         self._done[slot] = end
         self.copy_events = (start, end)

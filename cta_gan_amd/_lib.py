@@ -76,6 +76,8 @@ SIGNATURES = {
     "ctg_conv_cout1_wgrad": "ippipiiiiiiiiip",
     "ctg_hu_to_inputs": "pffpplp",
     "ctg_resize_nearest": "piiipiip",
+    "ctg_affine_nearest": "ppiiifpiip",
+    "ctg_hu_affine_inputs": "ppiiifffppiip",
     "ctg_adam_step": "ipppppffffipp",
     "ctg_adam_tick": "pffp",
 }
@@ -84,7 +86,7 @@ DIAG_SIGNATURES = {
     "ctg_lds_canary": "iipip",
 }
 _CT = {"i": _I, "l": _L, "p": _P, "f": _F, "d": ctypes.c_double}
-ABI_VERSION = 11      # CTG_ABI_VERSION of include/ctagan_hip.h this table was written against
+ABI_VERSION = 12      # CTG_ABI_VERSION of include/ctagan_hip.h this table was written against
 
 _lib = None
 

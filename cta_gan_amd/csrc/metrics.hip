@@ -7,6 +7,7 @@
 // reference's float32 operation order with explicitly rounded operations (no FMA contraction), so the masks --
 // which hang on exact comparisons (== 0, >= 0.3) -- are identical; the reductions accumulate in fp64.
 #include "common.h"
+#include "input_arith.h"
 
 #define MET_NSUM 20   // per (x, y) pair: n_m, sum|d|_m, sum d^2_m, sum|d|, sum d^2, sx, sy, sxx, syy, sxy
 
@@ -292,18 +293,9 @@ extern "C" int ctg_ssim(const float* fake, const float* real, const float* wc, c
 __global__ __launch_bounds__(256) void hu_to_inputs_kernel(const short* __restrict__ hu, double wmin, double dfac,
                                                            float* __restrict__ win, float* __restrict__ full, long n) {
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-        const double d1 = (double)hu[i];
-        // image1: CT window -> 8-bit levels -> [-1, 1]
-        double t = trunc((d1 - wmin) * dfac);
-        t = t > 255.0 ? 255.0 : t;
-        t = t < 0.0 ? 0.0 : t;
-        t = t / 255.0;
-        win[i] = (float)((t - 0.5) / 0.5);
-        // image2: full 12-bit range -> [-1, 1]
-        double f = d1 + 1024.0;
-        f = f < 0.0 ? 0.0 : f;
-        f = f / 4095.0;
-        full[i] = (float)((f - 0.5) / 0.5);
+        const short v = hu[i];
+        win[i] = hu_windowed(v, wmin, dfac);
+        full[i] = hu_fullrange(v);
     }
 }
 
@@ -313,9 +305,7 @@ __global__ __launch_bounds__(256) void resize_nearest_kernel(const float* __rest
     const int total = Ho * Wo;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
         const int oy = i / Wo, ox = i - oy * Wo;
-        int iy = (int)floorf(__fmul_rn((float)oy, sh)), ix = (int)floorf(__fmul_rn((float)ox, sw));
-        iy = iy < Hi - 1 ? iy : Hi - 1;
-        ix = ix < Wi - 1 ? ix : Wi - 1;
+        const int iy = nearest_src_index(oy, sh, Hi), ix = nearest_src_index(ox, sw, Wi);
         dst[(size_t)n * total + i] = src[((size_t)n * Hi + iy) * Wi + ix];
     }
 }
@@ -323,11 +313,10 @@ __global__ __launch_bounds__(256) void resize_nearest_kernel(const float* __rest
 extern "C" int ctg_hu_to_inputs(const short* hu, float wc, float ww, float* win, float* full, long n, void* stream) {
     CTG_ENTER();
     if (hu == nullptr || win == nullptr || full == nullptr || n < 1 || ww <= 0.f) return CTG_EINVAL;
-    const double c = (double)wc, w = (double)ww;
-    const double wmin = (2.0 * c - w) / 2.0 + 0.5, wmax = (2.0 * c + w) / 2.0 + 0.5;
+    double wmin, dfac;
+    hu_window_params(wc, ww, &wmin, &dfac);
     const int blocks = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
-    hipLaunchKernelGGL(hu_to_inputs_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, hu, wmin,
-                       255.0 / (wmax - wmin), win, full, n);
+    hipLaunchKernelGGL(hu_to_inputs_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, hu, wmin, dfac, win, full, n);
     return ctg_launch_status();
 }
 

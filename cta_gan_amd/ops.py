@@ -1506,3 +1506,48 @@ def resize_nearest(x, size):
     out = torch.empty(xs.shape[:-2] + (ho, wo), dtype=torch.float32, device=xs.device)
     _lib.check(lib.ctg_resize_nearest(_p(xs), b, hi, wi, _p(out), ho, wo, _stream()), "ctg_resize_nearest")
     return out
+
+
+def _coef_table(coef, planes, device, what):
+    if not torch.is_tensor(coef) or not coef.is_cuda:
+        raise RuntimeError("%s: the coefficient table must be a GPU int32 tensor (no CPU fallback)" % what)
+    if coef.dtype != torch.int32 or coef.numel() != planes * 6 or coef.device != device:
+        raise RuntimeError("%s: coefficient table of %d x 6 int32 on %s expected, got %s %s on %s"
+                           % (what, planes, device, tuple(coef.shape), coef.dtype, coef.device))
+    return coef.contiguous()
+
+
+def affine_nearest(x, coef, size, fill):
+    """RandomAffine's warp (PIL Image.transform(AFFINE, NEAREST) on a float image: its 16.16 fixed-point loop) followed by the
+    nearest Resize to `size`, one gather launch (csrc/augment.hip).  x: (..., H, W) fp32 planes on the GPU; coef: GPU int32
+    (planes, 6), each plane's `trainer.augment.fixed_coefficients`; pixels whose source lies outside the plane become `fill`."""
+    lib = _lib.load()
+    if not x.is_cuda:
+        raise RuntimeError("affine_nearest: CPU tensors are not supported (no CPU fallback)")
+    xs = x.float().contiguous()
+    hi, wi = xs.shape[-2:]
+    ho, wo = int(size[0]), int(size[1])
+    n = xs.numel() // max(hi * wi, 1)
+    c = _coef_table(coef, n, xs.device, "affine_nearest")
+    out = torch.empty(xs.shape[:-2] + (max(ho, 0), max(wo, 0)), dtype=torch.float32, device=xs.device)
+    _lib.check(lib.ctg_affine_nearest(_p(xs), _p(c), n, hi, wi, float(fill), _p(out), ho, wo, _stream()), "ctg_affine_nearest")
+    return out
+
+
+def hu_affine_inputs(hu, coef, size, wc=50.0, ww=400.0, fill=-1.0):
+    """`hu_to_inputs` -> RandomAffine's warp -> nearest Resize to `size` in one launch on raw HU: (..., H, W) int16 on the GPU ->
+    (windowed, full-range), both fp32 (..., size[0], size[1]).  coef: GPU int32 (planes, 2, 6): [:, 0] the windowed image's
+    coefficients, [:, 1] the full-range image's (the reference draws them independently, trainer/datasets.py:218-232)."""
+    lib = _lib.load()
+    if not hu.is_cuda:
+        raise RuntimeError("hu_affine_inputs: CPU tensors are not supported (no CPU fallback)")
+    h = hu.to(torch.int16).contiguous()
+    hi, wi = h.shape[-2:]
+    ho, wo = int(size[0]), int(size[1])
+    b = h.numel() // max(hi * wi, 1)
+    c = _coef_table(coef, 2 * b, h.device, "hu_affine_inputs")
+    win = torch.empty(h.shape[:-2] + (max(ho, 0), max(wo, 0)), dtype=torch.float32, device=h.device)
+    full = torch.empty_like(win)
+    _lib.check(lib.ctg_hu_affine_inputs(_p(h), _p(c), b, hi, wi, float(wc), float(ww), float(fill), _p(win), _p(full), ho, wo,
+                                        _stream()), "ctg_hu_affine_inputs")
+    return win, full

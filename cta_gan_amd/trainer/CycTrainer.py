@@ -10,6 +10,7 @@ from .. import dp, optim, synth
 from ..Model.CycleGan import Discriminator, Generator
 from ..nets import l1_loss
 from . import HdTrainer as _hd
+from .augment import NoiseAugmenter
 from .HdTrainer import run_epoch_steps, _frozen, resume_epoch, run_test_loop, save_epoch, validate_if_due, side_branch, synced_losses
 from .utils import ReplayBuffer
 
@@ -31,6 +32,8 @@ class Cyc_Trainer:
         self.fake_A_buffer = ReplayBuffer()
         self.fake_B_buffer = ReplayBuffer()
         self.last = {}
+        # the loaders' RandomAffine (`noise_level`; absent or 0: none), applied by train() to host batches only
+        self.augment = NoiseAugmenter(config.get("noise_level", 0), config["size"], seed=config.get("seed", 0))
 
     def update_learning_rate(self):
         """CycTrainer.py:117-126 (only D_B and G decay; D_A is left out there too)."""
@@ -114,7 +117,8 @@ class Cyc_Trainer:
                 self.synthetic_batch(i) for i in range(self.config.get("synthetic_steps", 4)))
             if dataloader is not None:
                 # host batches: pinned, double-buffered H2D on a copy stream, one batch ahead of the step that trains
-                it = DataPrefetcher(it, device=self.device)
+                # ... and, at noise_level > 0, the loaders' RandomAffine behind each copy on that stream (trainer/augment.py)
+                it = DataPrefetcher(it, device=self.device, transform=self.augment if self.augment.level > 0 else None)
             run_epoch_steps(self, it)
             val = validate_if_due(self, epoch, dataloader, val_dataloader, ("A", "B"))      # CycTrainer.py:203-226
             save_epoch(self, epoch, self._ckpt_files(), self._ckpt_optimizers(), val=val)

@@ -14,6 +14,7 @@ from ..Model.HdGan import DataPrefetcher
 from .. import dp, ops, optim, synth
 from ..Model.HdGan import Discriminator, Discriminator_m, GANLoss, Generator
 from ..nets import add_scalars, l1_loss, masked_l1_loss
+from .augment import NoiseAugmenter
 from .reg import Reg
 from .transformer import Transformer_2D
 from .utils import smooothing_loss
@@ -239,6 +240,8 @@ class _HdBase:
         self.optimizer_G = optim.Adam(self.netG_A2B.parameters(), lr=config["lr"], betas=(0.5, 0.999), capturable=cap)
         self.criterionGAN = GANLoss()
         self.last = {}
+        # the loaders' RandomAffine (`noise_level`; absent or 0: none), applied by train() to host batches only
+        self.augment = NoiseAugmenter(config.get("noise_level", 0), config["size"], seed=config.get("seed", 0))
         self._graph = None      # (CUDAGraph, static batch) once captured (config['hip_graph'])
         import weakref
         ops.NIE_ON_FAILURE.append(weakref.WeakMethod(self._drop_graph))
@@ -438,7 +441,8 @@ class _HdBase:
                 self.synthetic_batch(i) for i in range(self.config.get("synthetic_steps", 4)))
             if dataloader is not None:
                 # host batches: pinned, double-buffered H2D on a copy stream, one batch ahead of the step that trains
-                it = DataPrefetcher(it, device=self.device)
+                # ... and, at noise_level > 0, the loaders' RandomAffine behind each copy on that stream (trainer/augment.py)
+                it = DataPrefetcher(it, device=self.device, transform=self.augment if self.augment.level > 0 else None)
             run_epoch_steps(self, it)
             val = validate_if_due(self, epoch, dataloader, val_dataloader, self._val_keys)
             save_epoch(self, epoch, self._ckpt_files(), self._ckpt_optimizers(), val=val, val_suffix=self._val_suffix)

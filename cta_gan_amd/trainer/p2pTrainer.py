@@ -8,6 +8,7 @@ from ..Model.HdGan import DataPrefetcher
 from .. import dp, optim, synth
 from ..Model.CycleGan import Discriminator, Generator
 from ..nets import l1_loss
+from .augment import NoiseAugmenter
 from .HdTrainer import run_epoch_steps, _frozen, resume_epoch, run_test_loop, save_epoch, validate_if_due, synced_losses
 
 
@@ -22,6 +23,8 @@ class P2p_Trainer:
         self.optimizer_D_B = optim.Adam(self.netD_B.parameters(), lr=config["lr"], betas=(0.5, 0.999))
         self.optimizer_G = optim.Adam(self.netG_A2B.parameters(), lr=config["lr"], betas=(0.5, 0.999))
         self.last = {}
+        # the loaders' RandomAffine (`noise_level`; absent or 0: none), applied by train() to host batches only
+        self.augment = NoiseAugmenter(config.get("noise_level", 0), config["size"], seed=config.get("seed", 0))
 
     def update_learning_rate(self):
         """p2pTrainer.py:107-116."""
@@ -85,7 +88,8 @@ class P2p_Trainer:
                 self.synthetic_batch(i) for i in range(self.config.get("synthetic_steps", 4)))
             if dataloader is not None:
                 # host batches: pinned, double-buffered H2D on a copy stream, one batch ahead of the step that trains
-                it = DataPrefetcher(it, device=self.device)
+                # ... and, at noise_level > 0, the loaders' RandomAffine behind each copy on that stream (trainer/augment.py)
+                it = DataPrefetcher(it, device=self.device, transform=self.augment if self.augment.level > 0 else None)
             run_epoch_steps(self, it)
             val = validate_if_due(self, epoch, dataloader, val_dataloader, ("A", "B"))      # p2pTrainer.py:153-174
             save_epoch(self, epoch, self._ckpt_files(), self._ckpt_optimizers(), val=val)

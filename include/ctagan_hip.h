@@ -41,7 +41,7 @@ extern "C" {
 /* Bumped whenever the signature or the meaning of an existing entry point changes: a binding compares it with the value it
  * was written against before it makes any other call (cta_gan_amd/_lib.py does), so a stale library is an error, not a
  * mis-typed call. */
-#define CTG_ABI_VERSION 11
+#define CTG_ABI_VERSION 12
 int ctg_abi_version(void);
 
 /* ---- convolution: forward / backward-data / transposed, as one gather-GEMM ----
@@ -345,6 +345,22 @@ int ctg_window_metrics(const float* fake, const float* real, const float* wc, co
  * full-range image, both in [-1, 1]; Resize = F.interpolate(mode="nearest") (trainer/utils.py:13-32) on B planes. */
 int ctg_hu_to_inputs(const short* hu, float wc, float ww, float* win, float* full, long n, void* stream);
 int ctg_resize_nearest(const float* src, int B, int Hi, int Wi, float* dst, int Ho, int Wo, void* stream);
+/* training augmentation of every loader (ABI 12; trainer/HdTrainer.py:130-142,641-653, CycTrainer.py:91-99, p2pTrainer.py:81-89,
+ * RegTrainer.py:122-132, applied per image in trainer/datasets.py:103-119,218-232): RandomAffine(degrees, translate, scale,
+ * fillcolor) on a float PIL image -- Image.transform(AFFINE, NEAREST), PIL's 16.16 fixed-point loop -- followed by Resize, as
+ * one gather.  src: N planes [Hi][Wi] fp32; coef: device int32 [N][6] = (A0 .. A5), PIL's fixed-point coefficients of each
+ * plane's inverse matrix (cta_gan_amd/trainer/augment.py: fixed_coefficients); dst [N][Ho][Wo].  Output pixel (oy, ox) reads
+ * the pixel (iy, ix) of the Hi x Wi warped image by ctg_resize_nearest's index rule (the identity for Ho == Hi, Wo == Wi),
+ * and that pixel is src[n][ys][xs] with xs = (A2 + A1 iy + A0 ix) >> 16, ys = (A5 + A4 iy + A3 ix) >> 16 (64-bit, arithmetic
+ * shift) when 0 <= xs < Wi and 0 <= ys < Hi, `fill` otherwise.  Sides 1 .. 32768.
+ * ctg_hu_affine_inputs: the same gather on raw HU, B planes [Hi][Wi] int16 (ctg_hu_to_inputs' input) -> win / full
+ * [B][Ho][Wo], each pixel ctg_hu_to_inputs' value of the source pixel or `fill`; coef [B][2][6]: plane 0 the windowed image's
+ * coefficients, plane 1 the full-range image's (the reference draws them independently).  Equals ctg_hu_to_inputs ->
+ * ctg_affine_nearest -> ctg_resize_nearest bit for bit. */
+int ctg_affine_nearest(const float* src, const int* coef, int N, int Hi, int Wi, float fill, float* dst, int Ho, int Wo,
+                       void* stream);
+int ctg_hu_affine_inputs(const short* hu, const int* coef, int B, int Hi, int Wi, float wc, float ww, float fill, float* win,
+                         float* full, int Ho, int Wo, void* stream);
 
 /* ---- torch.optim.Adam(lr, betas=(0.5, 0.999)) step over `count` fp32 tensors (HdTrainer.py:612-616,738-739,751;
  * CycTrainer.py:67-73,162,178,197).  Host arrays of device pointers; `step` is 1-based. ---- */

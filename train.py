@@ -75,6 +75,11 @@ def main():
     if opts.test:
         trainer.test()
         return
+    if dp.rank() == 0:
+        # train.py has no DICOM loader: it trains on synthetic batches, which are never augmented (only host batches handed to
+        # trainer.train(dataloader) are)
+        print("noise_level: %s (RandomAffine of the training loaders; the synthetic batches of this run are not augmented)"
+              % trainer.augment.level, flush=True)
     trainer.train()
     torch.cuda.synchronize()
     print("done:", {k: float(v.detach()) for k, v in trainer.last.items() if v is not None and v.dim() == 0})

@@ -75,14 +75,16 @@ template <> struct VecOf<bf16_t> { static constexpr int N = 8; };
 template <> struct VecOf<bfpair_t> { static constexpr int N = 8; };
 
 // ---- 16-byte chunk <-> fp32 lanes -----------------------------------------
+// load(p, ld) = unpack(fetch(p, ld)): fetch() only issues the 16-byte request(s) and returns the raw registers, so a
+// kernel can put several chunks' requests in flight before it unpacks (and thereby waits for) the first of them
 template <typename T> struct Chunk;
 template <> struct Chunk<float> {
     static constexpr int N = 4;
     float v[4];
-    __device__ __forceinline__ void load(const float* p) {
-        const f32x4 t = *reinterpret_cast<const f32x4*>(p);
-        v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3];
-    }
+    typedef f32x4 Raw;
+    static __device__ __forceinline__ Raw fetch(const float* p, int) { return *reinterpret_cast<const f32x4*>(p); }
+    __device__ __forceinline__ void unpack(const Raw& t) { v[0] = t[0]; v[1] = t[1]; v[2] = t[2]; v[3] = t[3]; }
+    __device__ __forceinline__ void load(const float* p) { unpack(fetch(p, 0)); }
     __device__ __forceinline__ void store(float* p) const {
         *reinterpret_cast<f32x4*>(p) = f32x4{v[0], v[1], v[2], v[3]};
     }
@@ -94,14 +96,16 @@ template <> struct Chunk<float> {
 template <> struct Chunk<bf16_t> {
     static constexpr int N = 8;
     float v[8];
-    __device__ __forceinline__ void load(const bf16_t* p) {
-        const u32x4 t = *reinterpret_cast<const u32x4*>(p);
+    typedef u32x4 Raw;
+    static __device__ __forceinline__ Raw fetch(const bf16_t* p, int) { return *reinterpret_cast<const u32x4*>(p); }
+    __device__ __forceinline__ void unpack(const Raw& t) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             v[2 * i] = __uint_as_float(t[i] << 16);
             v[2 * i + 1] = __uint_as_float(t[i] & 0xffff0000u);
         }
     }
+    __device__ __forceinline__ void load(const bf16_t* p) { unpack(fetch(p, 0)); }
     __device__ __forceinline__ void store(bf16_t* p) const {
         bf16x8 o;
 #pragma unroll
@@ -119,15 +123,18 @@ template <> struct Chunk<bf16_t> {
 template <> struct Chunk<bfpair_t> {
     static constexpr int N = 8;
     float v[8];
-    __device__ __forceinline__ void load(const bfpair_t* p, int ld) {
-        const u32x4 h = *reinterpret_cast<const u32x4*>(p);
-        const u32x4 l = *reinterpret_cast<const u32x4*>(p + (ld >> 1));
+    struct Raw { u32x4 h, l; };
+    static __device__ __forceinline__ Raw fetch(const bfpair_t* p, int ld) {
+        return Raw{*reinterpret_cast<const u32x4*>(p), *reinterpret_cast<const u32x4*>(p + (ld >> 1))};
+    }
+    __device__ __forceinline__ void unpack(const Raw& t) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            v[2 * i] = __uint_as_float(h[i] << 16) + __uint_as_float(l[i] << 16);
-            v[2 * i + 1] = __uint_as_float(h[i] & 0xffff0000u) + __uint_as_float(l[i] & 0xffff0000u);
+            v[2 * i] = __uint_as_float(t.h[i] << 16) + __uint_as_float(t.l[i] << 16);
+            v[2 * i + 1] = __uint_as_float(t.h[i] & 0xffff0000u) + __uint_as_float(t.l[i] & 0xffff0000u);
         }
     }
+    __device__ __forceinline__ void load(const bfpair_t* p, int ld) { unpack(fetch(p, ld)); }
     __device__ __forceinline__ void store(bfpair_t* p, int ld) const {
         bf16x8 h, l;
 #pragma unroll

@@ -206,9 +206,129 @@ template <typename T> struct ChanParams {
     }
 };
 
+// Compile-time activation of the two kernels below: the host side dispatches ACT_NONE / ACT_RELU / ACT_LRELU once per launch,
+// so the pixel loops carry no branch on `act`.  ACT_RT keeps the runtime switch for ACT_TANH / ACT_SIGMOID (no InstanceNorm of
+// the networks is followed by either).
+#define ACT_RT (-1)
+
+// Both kernels are streaming passes, and what bounds a streaming pass is the number of 16-byte requests a lane has in
+// flight.  A lane therefore takes its next UNR trips of the pixel loop as ONE batch: every load of the batch (x, plus res
+// or dout) is issued before the first value is consumed, as in moments_partial_kernel.  Only whole batches are taken that
+// way; the < UNR trips a lane may have left run one at a time.  (Per-slot predicates with clamped addresses, as
+// moments_partial_kernel has them, put each slot's arithmetic under a branch, and the compiler then sinks the slot's loads
+// into that branch wherever the output is __restrict__: they were issued late and waited for with vmcnt(0).)  The lane ->
+// (pixel, channel chunk) mapping of a trip is unchanged (a wave still touches consecutive addresses) and the addresses
+// advance by one add per trip.  UNR per instantiation comes from the compiler's resource report (InUnr below, LAB_NOTES.md
+// section 11), and the host side never picks a batch longer than the pixels per lane its grid rule yields (pix_grid).
+//
+// Arithmetic is pinned (fp contract off + the one explicit FMA) to the roundings these kernels had when `act` was a
+// run-time switch: with a compile-time ACT_NONE the compiler could otherwise contract (x - mean) * rstd + res, or the
+// product and the hi/lo remainder of a split-pair store, into FMAs and change results in the last bit.
+
+// o = act((v - mean) * rstd)
+template <typename T, int ACT>
+__device__ __forceinline__ void in_fwd_px(Chunk<T>& o, const Chunk<T>& v, const ChanParams<T>& mu,
+                                          const ChanParams<T>& rs, int act) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int e = 0; e < Chunk<T>::N; ++e) {
+        const float xh = (v.v[e] - mu.v[e]) * rs.v[e];
+        if (ACT == ACT_RT) o.v[e] = act_apply(xh, act);
+        else if (ACT == ACT_RELU) o.v[e] = xh > 0.f ? xh : 0.f;
+        else if (ACT == ACT_LRELU) o.v[e] = xh > 0.f ? xh : LRELU_SLOPE * xh;
+        else o.v[e] = xh;
+    }
+}
+
+template <typename T> __device__ __forceinline__ void chunk_add(Chunk<T>& o, const Chunk<T>& r) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int e = 0; e < Chunk<T>::N; ++e) o.v[e] += r.v[e];
+}
+
+// o = rstd * (g - s1 - xhat * s2),  g = gradient * act'(xhat): the inner term is one subtraction and one FMA
+// (-xhat * s2 + (g - s1)); the outer product stays contractible, because a split-pair store takes its lo plane from
+// fma(rstd, inner, -hi)
+template <typename T, typename TX, int ACT>
+__device__ __forceinline__ void in_bwd_px(Chunk<T>& o, const Chunk<TX>& v, const Chunk<T>& g, const ChanParams<T>& mu,
+                                          const ChanParams<T>& rs, const ChanParams<T>& a1, const ChanParams<T>& a2) {
+#pragma unroll
+    for (int e = 0; e < Chunk<T>::N; ++e) {
+        float inner;
+        {
+#pragma clang fp contract(off)
+            const float xh = (v.v[e] - mu.v[e]) * rs.v[e];
+            float gg = g.v[e];
+            if (ACT == ACT_RELU) gg = xh > 0.f ? gg : 0.f;
+            else if (ACT == ACT_LRELU) gg = xh > 0.f ? gg : LRELU_SLOPE * gg;
+            inner = __fmaf_rn(-xh, a2.v[e], gg - a1.v[e]);
+        }
+        o.v[e] = rs.v[e] * inner;
+    }
+}
+
+// longest batch per element type: the largest UNR that keeps every instantiation free of scratch and at >= 4 waves per SIMD
+// (the split-pair types load two planes per operand, so a batch of 2 already has 4-8 requests per lane in flight)
+template <typename T> struct InUnr { static constexpr int FWD = 4, BWD = 4; };
+template <> struct InUnr<bfpair_t> { static constexpr int FWD = 2, BWD = 2; };
+
+template <typename T, int ACT, int UNR, bool RES>
+__device__ __forceinline__ void in_apply_loop(const T* x, int x_ld, const ChanParams<T>& mu, const ChanParams<T>& rs,
+                                              int act, const T* res, int r_ld, T* out, int o_ld, int HW, size_t base,
+                                              int ch, int p0, int pstep) {
+    const T* xp = x + (base + p0) * x_ld + ch;
+    const T* rp = RES ? res + (base + p0) * r_ld + ch : nullptr;
+    T* op = out + (base + p0) * o_ld + ch;
+    const size_t xs = (size_t)pstep * x_ld, rst = (size_t)pstep * r_ld, os = (size_t)pstep * o_ld;
+    int pb = p0;
+    for (; pb + (UNR - 1) * pstep < HW; pb += UNR * pstep) {
+        typename Chunk<T>::Raw vr[UNR], rr[UNR];
+#pragma unroll
+        for (int u = 0; u < UNR; ++u) {
+            vr[u] = Chunk<T>::fetch(xp + u * xs, x_ld);
+            if (RES) rr[u] = Chunk<T>::fetch(rp + u * rst, r_ld);
+        }
+        __builtin_amdgcn_sched_barrier(0);   // every request of the batch is issued before the first wait
+#pragma unroll
+        for (int u = 0; u < UNR; ++u) {
+            Chunk<T> v, o;
+            v.unpack(vr[u]);
+            in_fwd_px<T, ACT>(o, v, mu, rs, act);
+            if (RES) {
+                Chunk<T> r;
+                r.unpack(rr[u]);
+                chunk_add<T>(o, r);
+            }
+            o.store(op + u * os, o_ld);
+            __builtin_amdgcn_sched_barrier(0);   // slot by slot: interleaving the slots' arithmetic only costs registers
+        }
+        xp += UNR * xs;
+        if (RES) rp += UNR * rst;
+        op += UNR * os;
+    }
+    for (; pb < HW; pb += pstep) {           // ragged tail: the lane's last < UNR trips, one at a time
+        Chunk<T> v, o;
+        v.load(xp, x_ld);
+        in_fwd_px<T, ACT>(o, v, mu, rs, act);
+        if (RES) {
+            Chunk<T> r;
+            r.load(rp, r_ld);
+            chunk_add<T>(o, r);
+        }
+        o.store(op, o_ld);
+        xp += xs;
+        if (RES) rp += rst;
+        op += os;
+    }
+}
+
 // out = act((x - mean) * rstd) [+ res]
-// (x, res and out carry no __restrict__: a forward that keeps nothing normalises in place, out == x -- engine.inorm_forward)
-template <typename T>
+// (x, res and out carry no __restrict__: a forward that keeps nothing normalises in place, out == x -- engine.inorm_forward.
+// Batching keeps that legal: a lane stores only to the pixels it has itself loaded in the SAME batch, every load of a batch
+// is issued before its first store, and the lanes of a launch own disjoint (pixel, chunk) addresses -- so no store can land
+// on an address that any lane has yet to read.)
+// RES (a residual is added) is a template parameter like ACT: the plain form needs a third fewer registers than the one with `res`
+template <typename T, int ACT, int UNR, bool RES>
 __global__ __launch_bounds__(256) void in_apply_kernel(const T* x, int x_ld,
                                                        const float* __restrict__ mean,
                                                        const float* __restrict__ rstd, int act,
@@ -222,29 +342,19 @@ __global__ __launch_bounds__(256) void in_apply_kernel(const T* x, int x_ld,
     mu.load(mean + n * C + ch);
     rs.load(rstd + n * C + ch);
     const size_t base = (size_t)n * HW;
-    for (int p = blockIdx.x * PL + pl; p < HW; p += gridDim.x * PL) {
-        Chunk<T> v, o;
-        v.load(x + (base + p) * x_ld + ch, x_ld);
-#pragma unroll
-        for (int e = 0; e < EPC; ++e) o.v[e] = act_apply((v.v[e] - mu.v[e]) * rs.v[e], act);
-        if (res != nullptr) {
-            Chunk<T> r;
-            r.load(res + (base + p) * r_ld + ch, r_ld);
-#pragma unroll
-            for (int e = 0; e < EPC; ++e) o.v[e] += r.v[e];
-        }
-        o.store(out + (base + p) * o_ld + ch, o_ld);
-    }
+    const int p0 = blockIdx.x * PL + pl, pstep = gridDim.x * PL;
+    in_apply_loop<T, ACT, UNR, RES>(x, x_ld, mu, rs, act, res, r_ld, out, o_ld, HW, base, ch, p0, pstep);
 }
 
 // dx = rstd * (g - s1 - xhat * s2),  g = fold(dout) * act'(xhat)
-template <typename T, typename TX = T>
+// (only ReLU / LeakyReLU have a mask here: every other activation is instantiated as ACT_NONE)
+template <typename T, typename TX, int ACT, int UNR>
 __global__ __launch_bounds__(256) void in_bwd_apply_kernel(const TX* __restrict__ x, int x_ld,
                                                            const T* __restrict__ dout, int d_ld, int pad,
                                                            const float* __restrict__ mean,
                                                            const float* __restrict__ rstd,
                                                            const float* __restrict__ s1,
-                                                           const float* __restrict__ s2, int act,
+                                                           const float* __restrict__ s2,
                                                            T* __restrict__ dx, int dx_ld, int H, int W, int C) {
     constexpr int EPC = Chunk<T>::N;
     const int CPP = C / EPC, PL = 256 / CPP;
@@ -257,25 +367,59 @@ __global__ __launch_bounds__(256) void in_bwd_apply_kernel(const TX* __restrict_
     a1.load(s1 + n * C + ch);
     a2.load(s2 + n * C + ch);
     const size_t base = (size_t)n * HW;
-    for (int p = blockIdx.x * PL + pl; p < HW; p += gridDim.x * PL) {
-        Chunk<TX> v;
-        Chunk<T> g, o;
-        v.load(x + (base + p) * x_ld + ch, x_ld);
-        if (pad == 0) {
-            g.load(dout + (base + p) * d_ld + ch, d_ld);
-        } else {
+    const int p0 = blockIdx.x * PL + pl, pstep = gridDim.x * PL;
+    if (pad == 0) {
+        const TX* xp = x + (base + p0) * x_ld + ch;
+        const T* gp = dout + (base + p0) * d_ld + ch;
+        T* op = dx + (base + p0) * dx_ld + ch;
+        const size_t xs = (size_t)pstep * x_ld, gs = (size_t)pstep * d_ld, os = (size_t)pstep * dx_ld;
+        int pb = p0;
+        for (; pb + (UNR - 1) * pstep < HW; pb += UNR * pstep) {
+            typename Chunk<TX>::Raw vr[UNR];
+            typename Chunk<T>::Raw gr[UNR];
+#pragma unroll
+            for (int u = 0; u < UNR; ++u) {
+                vr[u] = Chunk<TX>::fetch(xp + u * xs, x_ld);
+                gr[u] = Chunk<T>::fetch(gp + u * gs, d_ld);
+            }
+            __builtin_amdgcn_sched_barrier(0);   // every request of the batch is issued before the first wait
+#pragma unroll
+            for (int u = 0; u < UNR; ++u) {
+                Chunk<TX> v;
+                Chunk<T> g, o;
+                v.unpack(vr[u]);
+                g.unpack(gr[u]);
+                in_bwd_px<T, TX, ACT>(o, v, g, mu, rs, a1, a2);
+                o.store(op + u * os, dx_ld);
+                __builtin_amdgcn_sched_barrier(0);   // slot by slot: interleaving the slots' arithmetic only costs registers
+            }
+            xp += UNR * xs;
+            gp += UNR * gs;
+            op += UNR * os;
+        }
+        for (; pb < HW; pb += pstep) {       // ragged tail: the lane's last < UNR trips, one at a time
+            Chunk<TX> v;
+            Chunk<T> g, o;
+            v.load(xp, x_ld);
+            g.load(gp, d_ld);
+            in_bwd_px<T, TX, ACT>(o, v, g, mu, rs, a1, a2);
+            o.store(op, dx_ld);
+            xp += xs;
+            gp += gs;
+            op += os;
+        }
+    } else {
+        // gradient on the reflection-padded grid: fold_load issues up to 9 loads per pixel by itself, so this path
+        // stays one pixel per trip
+        for (int p = p0; p < HW; p += pstep) {
+            Chunk<TX> v;
+            Chunk<T> g, o;
+            v.load(x + (base + p) * x_ld + ch, x_ld);
             const int y = p / W;
             fold_load<T>(g, dout, n, y, p - y * W, ch, H, W, pad, d_ld);
+            in_bwd_px<T, TX, ACT>(o, v, g, mu, rs, a1, a2);
+            o.store(dx + (base + p) * dx_ld + ch, dx_ld);
         }
-#pragma unroll
-        for (int e = 0; e < EPC; ++e) {
-            const float xh = (v.v[e] - mu.v[e]) * rs.v[e];
-            float gg = g.v[e];
-            if (act == ACT_RELU) gg = xh > 0.f ? gg : 0.f;
-            else if (act == ACT_LRELU) gg = xh > 0.f ? gg : LRELU_SLOPE * gg;
-            o.v[e] = rs.v[e] * (gg - a1.v[e] - xh * a2.v[e]);
-        }
-        o.store(dx + (base + p) * dx_ld + ch, dx_ld);
     }
 }
 
@@ -511,8 +655,10 @@ static inline int ew_blocks(long items) {
     return (int)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
 }
 
-// (pixel blocks, B) grid for the per-sample elementwise kernels: ~16 pixels per thread, >= 1 block per sample
-static inline dim3 pix_grid(int dtype, int B, int HW, int C) {
+// (pixel blocks, B) grid for the per-sample elementwise kernels: ~16 pixels per thread, >= 1 block per sample.
+// *per_out = the pixels per lane the rule settled on (16, 8, 4 or 2): the longest batch of trips worth launching, so the
+// small-batch grids are not half predicated off.
+static inline dim3 pix_grid(int dtype, int B, int HW, int C, int* per_out) {
     const int cpp = C / (dtype == DT_F32 ? 4 : 8);
     const int pl = 256 / cpp;
     // 16 pixels per lane; fewer while that leaves the chip under ~2048 workgroups (small batches: a lane's trips are dependent
@@ -523,10 +669,51 @@ static inline dim3 pix_grid(int dtype, int B, int HW, int C) {
     long bx = ((long)HW + pl * per - 1) / (pl * per);
     if (bx < 1) bx = 1;
     if (bx > 4096) bx = 4096;
+    *per_out = per;
     return dim3((unsigned)bx, (unsigned)B);
 }
 
 static inline bool pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
+
+// one instantiation per (activation, batch length): `per` is pix_grid's pixels per lane
+template <typename T, int ACT, bool RES, typename... A>
+static inline void launch_in_apply_unr(dim3 grid, int per, hipStream_t st, A... a) {
+    constexpr int U = InUnr<T>::FWD;
+    if (U > 2 && per < U) hipLaunchKernelGGL((in_apply_kernel<T, ACT, 2, RES>), grid, dim3(256), 0, st, a...);
+    else hipLaunchKernelGGL((in_apply_kernel<T, ACT, U, RES>), grid, dim3(256), 0, st, a...);
+}
+template <typename T, int ACT>
+static inline void launch_in_apply_act(dim3 grid, int per, hipStream_t st, const T* x, int x_ld, const float* mean,
+                                       const float* rstd, int act, const T* res, int r_ld, T* out, int o_ld, int HW, int C) {
+    if (res != nullptr) launch_in_apply_unr<T, ACT, true>(grid, per, st, x, x_ld, mean, rstd, act, res, r_ld, out, o_ld, HW, C);
+    else launch_in_apply_unr<T, ACT, false>(grid, per, st, x, x_ld, mean, rstd, act, res, r_ld, out, o_ld, HW, C);
+}
+template <typename T>
+static inline void launch_in_apply(dim3 grid, int per, hipStream_t st, const T* x, int x_ld, const float* mean,
+                                   const float* rstd, int act, const T* res, int r_ld, T* out, int o_ld, int HW, int C) {
+    switch (act) {
+        case ACT_NONE: launch_in_apply_act<T, ACT_NONE>(grid, per, st, x, x_ld, mean, rstd, act, res, r_ld, out, o_ld, HW, C); break;
+        case ACT_RELU: launch_in_apply_act<T, ACT_RELU>(grid, per, st, x, x_ld, mean, rstd, act, res, r_ld, out, o_ld, HW, C); break;
+        case ACT_LRELU: launch_in_apply_act<T, ACT_LRELU>(grid, per, st, x, x_ld, mean, rstd, act, res, r_ld, out, o_ld, HW, C); break;
+        default: launch_in_apply_act<T, ACT_RT>(grid, per, st, x, x_ld, mean, rstd, act, res, r_ld, out, o_ld, HW, C); break;
+    }
+}
+template <typename T, typename TX, int ACT, typename... A>
+static inline void launch_in_bwd_apply_act(dim3 grid, int per, hipStream_t st, A... a) {
+    constexpr int U = InUnr<TX>::BWD;
+    if (U > 2 && per < U) hipLaunchKernelGGL((in_bwd_apply_kernel<T, TX, ACT, 2>), grid, dim3(256), 0, st, a...);
+    else hipLaunchKernelGGL((in_bwd_apply_kernel<T, TX, ACT, U>), grid, dim3(256), 0, st, a...);
+}
+template <typename T, typename TX>
+static inline void launch_in_bwd_apply(dim3 grid, int per, hipStream_t st, const TX* x, int x_ld, const T* dout, int d_ld,
+                                       int pad, const float* mean, const float* rstd, const float* s1, const float* s2,
+                                       int act, T* dx, int dx_ld, int H, int W, int C) {
+    switch (act) {
+        case ACT_RELU: launch_in_bwd_apply_act<T, TX, ACT_RELU>(grid, per, st, x, x_ld, dout, d_ld, pad, mean, rstd, s1, s2, dx, dx_ld, H, W, C); break;
+        case ACT_LRELU: launch_in_bwd_apply_act<T, TX, ACT_LRELU>(grid, per, st, x, x_ld, dout, d_ld, pad, mean, rstd, s1, s2, dx, dx_ld, H, W, C); break;
+        default: launch_in_bwd_apply_act<T, TX, ACT_NONE>(grid, per, st, x, x_ld, dout, d_ld, pad, mean, rstd, s1, s2, dx, dx_ld, H, W, C); break;
+    }
+}
 
 #define DISPATCH_T(dtype, CALL)                   \
     if ((dtype) == DT_BF16) { typedef bf16_t T; CALL; } \
@@ -577,9 +764,10 @@ extern "C" int ctg_in_apply(int dtype, const void* x, int x_ld, const float* mea
                             const void* res, int r_ld, void* out, int o_ld, int B, int H, int W, int C, void* stream) {
     CTG_ENTER();
     if (check_c(dtype, C) || out == nullptr) return CTG_EINVAL;
-    DISPATCH_T(dtype, hipLaunchKernelGGL((in_apply_kernel<T>), pix_grid(dtype, B, H * W, C), dim3(256), 0,
-                                         (hipStream_t)stream, (const T*)x, x_ld, mean, rstd, act, (const T*)res, r_ld,
-                                         (T*)out, o_ld, H * W, C));
+    int per;
+    const dim3 grid = pix_grid(dtype, B, H * W, C, &per);
+    DISPATCH_T(dtype, (launch_in_apply<T>(grid, per, (hipStream_t)stream, (const T*)x, x_ld, mean, rstd, act, (const T*)res,
+                                          r_ld, (T*)out, o_ld, H * W, C)));
     return ctg_launch_status();
 }
 
@@ -644,9 +832,10 @@ extern "C" int ctg_in_bwd_apply(int dtype, const void* x, int x_ld, const void* 
                                 int H, int W, int C, void* stream) {
     CTG_ENTER();
     if (check_c(dtype, C) || pad < 0 || pad >= H || pad >= W || s1 == nullptr || s2 == nullptr) return CTG_EINVAL;
-    DISPATCH_TX(dtype, hipLaunchKernelGGL((in_bwd_apply_kernel<T, TX>), pix_grid(dtype, B, H * W, C), dim3(256), 0,
-                                          (hipStream_t)stream, (const TX*)x, x_ld, (const T*)dout, d_ld, pad, mean, rstd, s1, s2,
-                                          act, (T*)dx, dx_ld, H, W, C));
+    int per;
+    const dim3 grid = pix_grid(dtype, B, H * W, C, &per);
+    DISPATCH_TX(dtype, (launch_in_bwd_apply<T, TX>(grid, per, (hipStream_t)stream, (const TX*)x, x_ld, (const T*)dout, d_ld,
+                                                   pad, mean, rstd, s1, s2, act, (T*)dx, dx_ld, H, W, C)));
     return ctg_launch_status();
 }
 

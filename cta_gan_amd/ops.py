@@ -296,7 +296,9 @@ def _nhwc(t: torch.Tensor):
     elif b > 1:
         ld = t.stride(0)
     else:
-        ld = c
+        # a single pixel: a channel slice of a wider buffer -- every split-pair handle is one, its lo plane lies ld / 2 behind --
+        # still carries the buffer's pitch in the strides of its size-1 dims
+        ld = max(t.stride(2), c)
     if c > 1 and t.stride(3) != 1:
         raise RuntimeError("activation is not channels-innermost")
     exp = (h * w * ld, w * ld, ld)

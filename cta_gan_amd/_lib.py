@@ -78,6 +78,8 @@ SIGNATURES = {
     "ctg_resize_nearest": "piiipiip",
     "ctg_affine_nearest": "ppiiifpiip",
     "ctg_hu_affine_inputs": "ppiiifffppiip",
+    "ctg_export_slices": "pppiiippiiip",
+    "ctg_series_inputs": "piiipiip",
     "ctg_adam_step": "ipppppffffipp",
     "ctg_adam_tick": "pffp",
 }
@@ -86,7 +88,7 @@ DIAG_SIGNATURES = {
     "ctg_lds_canary": "iipip",
 }
 _CT = {"i": _I, "l": _L, "p": _P, "f": _F, "d": ctypes.c_double}
-ABI_VERSION = 12      # CTG_ABI_VERSION of include/ctagan_hip.h this table was written against
+ABI_VERSION = 13      # CTG_ABI_VERSION of include/ctagan_hip.h this table was written against
 
 _lib = None
 

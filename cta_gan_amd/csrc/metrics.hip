@@ -8,33 +8,9 @@
 // which hang on exact comparisons (== 0, >= 0.3) -- are identical; the reductions accumulate in fp64.
 #include "common.h"
 #include "input_arith.h"
+#include "window_arith.h"
 
 #define MET_NSUM 20   // per (x, y) pair: n_m, sum|d|_m, sum d^2_m, sum|d|, sum d^2, sx, sy, sxx, syy, sxy
-
-struct WinParams { float wmin, dfac; };
-
-__device__ __forceinline__ WinParams win_params(float wc, float ww) {
-    // python floats in the reference: win_min = (2*c - w)/2.0 + 0.5, dFactor = 255.0 / (win_max - win_min);
-    // a float32 array combined with them rounds each to float32 first
-    const double c = (double)wc, w = (double)ww;
-    const double wmin = (2.0 * c - w) / 2.0 + 0.5, wmax = (2.0 * c + w) / 2.0 + 0.5;
-    WinParams p;
-    p.wmin = (float)wmin;
-    p.dfac = (float)(255.0 / (wmax - wmin));
-    return p;
-}
-
-__device__ __forceinline__ float window_one(float v, const WinParams p) {
-    float t = __fmul_rn(__fmul_rn(__fadd_rn(v, 1.0f), 0.5f), 4095.0f);
-    if (t == 0.0f) t = -2000.0f;
-    t = __fsub_rn(t, 1024.0f);
-    t = __fsub_rn(t, p.wmin);
-    t = truncf(__fmul_rn(t, p.dfac));
-    if (t > 255.0f) t = 255.0f;
-    if (t < 0.0f) t = 0.0f;
-    t = __fdiv_rn(t, 255.0f);
-    return __fdiv_rn(__fsub_rn(t, 0.5f), 0.5f);
-}
 
 __global__ __launch_bounds__(256) void to_windowdata_kernel(const float* __restrict__ img, const float* __restrict__ wc,
                                                             const float* __restrict__ ww, float* __restrict__ out,

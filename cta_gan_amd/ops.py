@@ -1553,3 +1553,52 @@ def hu_affine_inputs(hu, coef, size, wc=50.0, ww=400.0, fill=-1.0):
     _lib.check(lib.ctg_hu_affine_inputs(_p(h), _p(c), b, hi, wi, float(wc), float(ww), float(fill), _p(win), _p(full), ho, wo,
                                         _stream()), "ctg_hu_affine_inputs")
     return win, full
+
+
+# ---------------------------------------------------------------------------- series inference (csrc/export.hip)
+def _out_size(size, h, w):
+    if size is None:
+        return h, w
+    if isinstance(size, int):
+        return size, size
+    return int(size[0]), int(size[1])
+
+
+def export_slices(fake, wc, ww, size=None, hu=False, want_level=True):
+    """The export half of the reference's test() loop (trainer/HdTrainer.py:539-543) on the device: the generator's output
+    (B, [1,] H, W) fp32 on the GPU -> (pix, level), one launch.  pix: int16 (B, Ho, Wo), `((fake + 1) * 0.5 * 4095).astype(int16)`
+    (`hu`: minus 1024, SimpleITK's convention); level: uint8 (B, Ho, Wo), the 8-bit window level of `to_windowdata` for the
+    per-slice (or scalar) window wc / ww, or None with want_level=False.  `size` (int or (Ho, Wo); None: the input's): a nearest
+    resize by `resize_nearest`'s rule on the way out."""
+    lib = _lib.load()
+    if not fake.is_cuda:
+        raise RuntimeError("export_slices: CPU tensors are not supported (no CPU fallback)")
+    x = fake.float().contiguous()
+    b, hi, wi = x.shape[0], x.shape[-2], x.shape[-1]
+    if x.dim() < 3 or x.numel() != b * hi * wi:
+        raise RuntimeError("export_slices: one plane per slice (B, [1,] H, W)")
+    ho, wo = _out_size(size, hi, wi)
+    pix = torch.empty((b, max(ho, 0), max(wo, 0)), dtype=torch.int16, device=x.device)
+    level = wcv = wwv = None
+    if want_level:
+        level = torch.empty(pix.shape, dtype=torch.uint8, device=x.device)
+        wcv, wwv = _win_vec(wc, b, x.device), _win_vec(ww, b, x.device)
+        assert wcv.numel() == b and wwv.numel() == b
+    _lib.check(lib.ctg_export_slices(_p(x), _p(wcv), _p(wwv), b, hi, wi, _p(pix), _p(level), ho, wo, int(bool(hu)), _stream()),
+               "ctg_export_slices")
+    return pix, level
+
+
+def series_inputs(hu, size=None):
+    """Raw HU (..., H, W) int16 on the GPU -> the full-range fp32 plane (..., Ho, Wo) the generator reads in test() (`A2`):
+    `resize_nearest(hu_to_inputs(hu)[1], size)` bit for bit, one launch and without the windowed plane."""
+    lib = _lib.load()
+    if not hu.is_cuda:
+        raise RuntimeError("series_inputs: CPU tensors are not supported (no CPU fallback)")
+    h = hu.to(torch.int16).contiguous()
+    hi, wi = h.shape[-2:]
+    ho, wo = _out_size(size, hi, wi)
+    b = h.numel() // max(hi * wi, 1)
+    out = torch.empty(h.shape[:-2] + (max(ho, 0), max(wo, 0)), dtype=torch.float32, device=h.device)
+    _lib.check(lib.ctg_series_inputs(_p(h), b, hi, wi, _p(out), ho, wo, _stream()), "ctg_series_inputs")
+    return out

@@ -184,12 +184,35 @@ def resume_epoch(trainer, epoch, files, optimizers):
     trainer.config["epoch"] = epoch
 
 
+def _export_batch(fake_B, wc, ww, paths, first, root, png):
+    """One batch of the test() loop's export: `<root>/<stem>.npy` (int16) per slice, and `<stem>.png` (uint8 level) with `png`."""
+    import os
+    import numpy as np
+    pix, level = ops.export_slices(fake_B, wc, ww, want_level=png)
+    pix = pix.cpu().numpy()
+    level = level.cpu().numpy() if png else None
+    if isinstance(paths, str):
+        paths = [paths]
+    os.makedirs(root, exist_ok=True)
+    for i in range(pix.shape[0]):
+        stem = "%06d" % (first + i)
+        if paths is not None and i < len(paths):
+            stem = os.path.splitext(os.path.basename(str(paths[i])))[0]
+        np.save(os.path.join(root, stem + ".npy"), pix[i])
+        if png:
+            from PIL import Image
+            Image.fromarray(level[i]).save(os.path.join(root, stem + ".png"))      # uint8 [H, W]: mode "L"
+
+
 def run_test_loop(trainer, dataloader, keys, ckpt_name, aliased, uqiw_label="UQIW:"):
     """The inference + metrics loop shared by the trainers' `test()` (HdTrainer.py:951-1087, CycTrainer.py:238-398,
     p2pTrainer.py:186-312, RegTrainer.py:242-380): load `save_root/ckpt_name` into the generator if it exists, run the
     generator over the batches (dicts holding `keys` = (input, target), optionally per-slice 'WC' / 'WW') and average the
     windowed and raw MAE / PSNR / SSIM / UQI on the device.  `aliased`: the reference's `bb = b` / `cc = c` aliasing (Cyc, P2p).
-    LPIPS (a pretrained AlexNet) and the DICOM export of the same loop are not part of this build."""
+    LPIPS (a pretrained AlexNet) and the DICOM container of the same loop's export are not part of this build; the export's
+    pixels are, behind `config['export_root']` (absent: nothing is written): every slice's `newimg.astype(np.int16)`
+    (HdTrainer.py:539-543) is saved as `<export_root>/<stem>.npy`, <stem> = the basename of `batch['A_path'][i]` without its
+    extension or a running %06d index, plus `<stem>.png` (the 8-bit window level) with `config['export_png']`; rank 0 writes."""
     import os
     cfg = trainer.config
     ckpt = os.path.join(cfg.get("save_root", ""), ckpt_name)
@@ -200,6 +223,9 @@ def run_test_loop(trainer, dataloader, keys, ckpt_name, aliased, uqiw_label="UQI
     total = torch.zeros(2, 3, dtype=torch.float64, device=trainer.device)
     total_ssim = torch.zeros(2, dtype=torch.float64, device=trainer.device)
     num = 0
+    export_root = cfg.get("export_root")
+    if export_root and dp.world_size() > 1 and torch.distributed.get_rank() != 0:
+        export_root = None
     with torch.no_grad():
         for batch in it:
             real_A = batch[keys[0]].to(trainer.device, non_blocking=True)
@@ -209,6 +235,8 @@ def run_test_loop(trainer, dataloader, keys, ckpt_name, aliased, uqiw_label="UQI
             fake_B = trainer.netG_A2B(real_A)
             total += ops.window_metrics(fake_B, real_B, wc, ww, aliased=aliased).sum(0)
             total_ssim += ops.window_ssim(fake_B, real_B, wc, ww, aliased=aliased).sum(0)      # HdTrainer.py:1028, 1053
+            if export_root:
+                _export_batch(fake_B, wc, ww, batch.get("A_path"), num, export_root, bool(cfg.get("export_png")))
             num += real_A.shape[0]
     res = (total / max(num, 1)).cpu().numpy()
     res_ssim = (total_ssim / max(num, 1)).cpu().numpy()

@@ -41,7 +41,7 @@ extern "C" {
 /* Bumped whenever the signature or the meaning of an existing entry point changes: a binding compares it with the value it
  * was written against before it makes any other call (cta_gan_amd/_lib.py does), so a stale library is an error, not a
  * mis-typed call. */
-#define CTG_ABI_VERSION 12
+#define CTG_ABI_VERSION 13
 int ctg_abi_version(void);
 
 /* ---- convolution: forward / backward-data / transposed, as one gather-GEMM ----
@@ -361,6 +361,28 @@ int ctg_affine_nearest(const float* src, const int* coef, int N, int Hi, int Wi,
                        void* stream);
 int ctg_hu_affine_inputs(const short* hu, const int* coef, int B, int Hi, int Wi, float wc, float ww, float fill, float* win,
                          float* full, int Ho, int Wo, void* stream);
+
+/* ---- series inference, the way back (ABI 13): the export half of every trainer's test() loop (trainer/HdTrainer.py:539-552,
+ * 1062-1075; CycTrainer.py:337-340, p2pTrainer.py:288-291, RegTrainer.py:360-363) without its DICOM container ----
+ * ctg_export_slices: img = the generator's fp32 output planes [B][Hi][Wi]; wc / ww = per-slice window centre / width on the
+ * device, as ctg_to_windowdata takes them (read only when level != NULL).  One pass writes
+ *   pix   int16 [B][Ho][Wo]: `newimg = (fake_BB + 1) * 0.5 * 4095; newimg.astype(np.int16)` (HdTrainer.py:539, 543) -- the three
+ *         float32 operations one after another, each rounded, then truncated toward zero; hu != 0 subtracts 1024 after the
+ *         truncation (SimpleITK's convention, the inverse of the + 1024 of ctg_hu_to_inputs' full-range image).  The reference's
+ *         domain is the generator's tanh range [-1, 1], where the value is 0 .. 4095; outside it the conversion saturates to
+ *         the int16 range (also after the hu subtraction) and NaN gives 0 -- numpy leaves both undefined.
+ *   level uint8 [B][Ho][Wo]: the 8-bit window level to_windowdata (HdTrainer.py:41-61) computes before it rescales to [-1, 1]
+ *         (:62-63), `== 0 -> -2000` included: level / 255 rescaled IS ctg_to_windowdata's value, bit for bit (NaN gives 0).
+ * Either of pix / level may be NULL to skip it (not both).  (Ho, Wo) != (Hi, Wi): every output pixel gathers its source by
+ * ctg_resize_nearest's index rule, so a series scanned at another size than the generator runs at comes back at its own.
+ * img 4-byte, pix 2-byte aligned; the 16-byte streaming path needs no more than that.  B <= 65535, planes below 2^31 pixels.
+ * The reference's 8-bit DICOM branch (`astype(np.int8)`, :544-545) is not built.
+ * ctg_series_inputs: raw HU int16 [B][Hi][Wi] (ctg_hu_to_inputs' input) -> only the full-range plane [B][Ho][Wo] that test()
+ * feeds the generator (`A2`; trainer/datasets.py:36-71 + Resize, trainer/utils.py:13-32), gathered by the same index rule:
+ * equals ctg_hu_to_inputs' `full` -> ctg_resize_nearest bit for bit. */
+int ctg_export_slices(const float* img, const float* wc, const float* ww, int B, int Hi, int Wi, short* pix,
+                      unsigned char* level, int Ho, int Wo, int hu, void* stream);
+int ctg_series_inputs(const short* hu, int B, int Hi, int Wi, float* full, int Ho, int Wo, void* stream);
 
 /* ---- torch.optim.Adam(lr, betas=(0.5, 0.999)) step over `count` fp32 tensors (HdTrainer.py:612-616,738-739,751;
  * CycTrainer.py:67-73,162,178,197).  Host arrays of device pointers; `step` is 1-based. ---- */

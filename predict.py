@@ -1,0 +1,70 @@
+#!/usr/bin/python3
+"""Series inference from the command line: a raw HU volume in, the synthesized CTA volume out.
+
+    python predict.py --config Yaml/HdGan.yaml --weights netG_A2B.pth --input series.npy --output out.npy
+                      [--level-dir DIR] [--hu] [--wc 50 --ww 400] [--batch 16] [--dtype bf16x3]
+
+--input: int16 [N, H, W] .npy in SimpleITK's convention (what the reference's loaders read from the DICOMs); --weights: the
+reference-format `state_dict` of Model.HdGan.Generator (what train() saves as netG_A2B*.pth).  --output receives the int16
+volume the reference's test() writes into the DICOMs (trainer/HdTrainer.py:539-543; --hu: minus 1024, SimpleITK's convention
+again); --level-dir one 8-bit PNG per slice of the window (--wc, --ww).  The generator runs at config['size']; a series of
+another size is resized on the way in and comes back at its own.  DICOM reading and writing are not part of this build.
+"""
+import argparse
+import os
+
+DTYPES = ["fp32", "bf16", "bf16x3", "bf16x3f"]
+DEFAULT_DTYPE = "bf16x3"      # train.py's default
+
+
+def build_parser():
+    parser = argparse.ArgumentParser(description="HU series (.npy) -> synthesized CTA series (.npy)")
+    parser.add_argument("--config", type=str, default="Yaml/HdGan.yaml", help="Path to the config file.")
+    parser.add_argument("--weights", type=str, required=True, help="state_dict of Model.HdGan.Generator (.pth)")
+    parser.add_argument("--input", type=str, required=True, help="int16 [N, H, W] .npy, raw HU")
+    parser.add_argument("--output", type=str, required=True, help="int16 [N, H, W] .npy to write")
+    parser.add_argument("--level-dir", type=str, default=None, help="also write one 8-bit PNG of the window per slice here")
+    parser.add_argument("--hu", action="store_true", help="write HU (stored value - 1024) instead of stored values")
+    parser.add_argument("--wc", type=float, default=50.0, help="window centre of the 8-bit level")
+    parser.add_argument("--ww", type=float, default=400.0, help="window width of the 8-bit level")
+    parser.add_argument("--batch", type=int, default=16, help="slices per generator forward")
+    parser.add_argument("--dtype", choices=DTYPES, default=None, help="compute mode (default %s, as train.py)" % DEFAULT_DTYPE)
+    return parser
+
+
+def main(argv=None):
+    opts = build_parser().parse_args(argv)
+    import numpy as np
+    import torch
+    import yaml
+    with open(opts.config, "r") as stream:
+        config = yaml.safe_load(stream)
+    from cta_gan_amd import _lib, nets
+    from cta_gan_amd.infer import SeriesTranslator
+    from Model.HdGan import Generator
+    _lib.load()
+    mode = opts.dtype or DEFAULT_DTYPE
+    nets.set_default_compute_dtype({"fp32": torch.float32, "bf16": torch.bfloat16}.get(mode, mode))
+    print("compute mode: %s%s" % (nets.compute_mode(), "" if opts.dtype else " (default; --dtype fp32 is the reference's own arithmetic)"),
+          flush=True)
+    volume = np.load(opts.input)
+    if volume.dtype != np.int16 or volume.ndim != 3:
+        raise SystemExit("--input: an int16 [N, H, W] array expected, got %s %s" % (volume.dtype, volume.shape))
+    device = torch.device("cuda", torch.cuda.current_device())
+    generator = Generator(config["input_nc"], config["output_nc"]).to(device)
+    generator.load_state_dict(torch.load(opts.weights, map_location=device))
+    translate = SeriesTranslator(generator, batch=opts.batch, size=config.get("size"), wc=opts.wc, ww=opts.ww, hu=opts.hu,
+                                 level=opts.level_dir is not None, device=device)
+    out = translate(volume)
+    np.save(opts.output, out["pix"])
+    if opts.level_dir is not None:
+        from PIL import Image
+        os.makedirs(opts.level_dir, exist_ok=True)
+        for i, plane in enumerate(out["level"]):
+            Image.fromarray(plane).save(os.path.join(opts.level_dir, "%06d.png" % i))      # uint8 [H, W]: mode "L"
+    print("wrote %s: %d slices of %d x %d%s" % (opts.output, volume.shape[0], volume.shape[1], volume.shape[2],
+                                               "" if opts.level_dir is None else " (+ PNGs in %s)" % opts.level_dir), flush=True)
+
+
+if __name__ == "__main__":
+    main()

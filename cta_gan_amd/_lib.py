@@ -80,6 +80,9 @@ SIGNATURES = {
     "ctg_hu_affine_inputs": "ppiiifffppiip",
     "ctg_export_slices": "pppiiippiiip",
     "ctg_series_inputs": "piiipiip",
+    "ctg_window_pairs": "ppppilipp",
+    "ctg_maxpool3s2_fwd": "pipiiiiip",
+    "ctg_lpips_layer": "pipiliippp",
     "ctg_adam_step": "ipppppffffipp",
     "ctg_adam_tick": "pffp",
 }
@@ -88,7 +91,7 @@ DIAG_SIGNATURES = {
     "ctg_lds_canary": "iipip",
 }
 _CT = {"i": _I, "l": _L, "p": _P, "f": _F, "d": ctypes.c_double}
-ABI_VERSION = 13      # CTG_ABI_VERSION of include/ctagan_hip.h this table was written against
+ABI_VERSION = 14      # CTG_ABI_VERSION of include/ctagan_hip.h this table was written against
 
 _lib = None
 

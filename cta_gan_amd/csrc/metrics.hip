@@ -57,29 +57,9 @@ __global__ __launch_bounds__(256) void window_metrics_partial_kernel(const float
     ar.clear();
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < HW; i += (long)gridDim.x * 256) {
         const float f = fake[n * HW + i], r = real[n * HW + i];
-        // b = W(real); bb = b >= 0.3; b = b*bb; b[b == 0] = -1
-        float b = window_one(r, p);
-        const float bb = b >= 0.3f ? 1.f : 0.f;
-        b = __fmul_rn(b, bb);
-        if (b == 0.f) b = -1.f;
-        // c = W(fake)*bb; cc = c >= 0.3; c = c*cc; c[c == 0] = -1
-        float c = __fmul_rn(window_one(f, p), bb);
-        const float cc = c >= 0.3f ? 1.f : 0.f;
-        c = __fmul_rn(c, cc);
-        if (c == 0.f) c = -1.f;
-        if (aliased) {
-            // trainer/CycTrainer.py:288-298 writes `bb = b` / `cc = c` WITHOUT a copy, so thresholding the masks also
-            // thresholds b and c: its windowed pair is the two binary masks mapped to +-1
-            b = bb != 0.f ? 1.f : -1.f;
-            c = cc != 0.f ? 1.f : -1.f;
-        }
-        aw.add(c, b);
-        // raw maps under the same masks
-        float rm = __fmul_rn(r, bb);
-        if (rm == 0.f) rm = -1.f;
-        float fm = __fmul_rn(f, cc);
-        if (fm == 0.f) fm = -1.f;
-        ar.add(fm, rm);
+        const MaskedPixel q = masked_pixel(f, r, p, aliased);      // csrc/window_arith.h
+        aw.add(q.c, q.b);
+        ar.add(q.fm, q.rm);
     }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
@@ -142,6 +122,36 @@ extern "C" int ctg_window_metrics(const float* fake, const float* real, const fl
     return ctg_launch_status();
 }
 
+// The four masked images window_metrics_partial_kernel only reduces, written out as planes: out[4][B][HW] in the order
+// [c, fake_m, b, real_m] -- planes 0 .. 2B-1 are the generated ("x") side, 2B .. 4B-1 the reference ("y") side of the 2B pairs
+// {windowed (c, b), raw (fake_m, real_m)} that LPIPS of the test() loop compares (HdTrainer.py:1029-1031, 1054-1056).
+__global__ __launch_bounds__(256) void window_pairs_kernel(const float* __restrict__ fake, const float* __restrict__ real,
+                                                           const float* __restrict__ wc, const float* __restrict__ ww, long HW,
+                                                           int B, float* __restrict__ out, int aliased) {
+    const int n = blockIdx.y;
+    const WinParams p = win_params(wc[n], ww[n]);
+    const size_t plane = (size_t)B * HW;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < HW; i += (long)gridDim.x * 256) {
+        const MaskedPixel q = masked_pixel(fake[n * HW + i], real[n * HW + i], p, aliased);
+        const size_t o = (size_t)n * HW + i;
+        out[o] = q.c;
+        out[plane + o] = q.fm;
+        out[2 * plane + o] = q.b;
+        out[3 * plane + o] = q.rm;
+    }
+}
+
+extern "C" int ctg_window_pairs(const float* fake, const float* real, const float* wc, const float* ww, int B, long HW,
+                                int aliased, float* out, void* stream) {
+    CTG_ENTER();
+    if (fake == nullptr || real == nullptr || wc == nullptr || ww == nullptr || out == nullptr) return CTG_EINVAL;
+    if (B < 1 || B > 65535 || HW < 1) return CTG_EINVAL;
+    const int blocks = (int)((HW + 255) / 256 < 1024 ? (HW + 255) / 256 : 1024);
+    hipLaunchKernelGGL(window_pairs_kernel, dim3(blocks, B), dim3(256), 0, (hipStream_t)stream, fake, real, wc, ww, HW, B, out,
+                       aliased);
+    return ctg_launch_status();
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // Mean structural similarity of slice pairs: what `skimage.measure.compare_ssim(x, y)` returns for two float images with its
 // defaults -- the call of the reference's validation pass (trainer/HdTrainer.py:256,779, CycTrainer.py:216, p2pTrainer.py:164,
@@ -179,26 +189,11 @@ __global__ __launch_bounds__(256) void ssim_partial_kernel(const float* __restri
             tile[0][i] = f;
             tile[1][i] = r;
         } else {
-            float b = window_one(r, p);
-            const float bb = b >= 0.3f ? 1.f : 0.f;
-            b = __fmul_rn(b, bb);
-            if (b == 0.f) b = -1.f;
-            float c = __fmul_rn(window_one(f, p), bb);
-            const float cc = c >= 0.3f ? 1.f : 0.f;
-            c = __fmul_rn(c, cc);
-            if (c == 0.f) c = -1.f;
-            if (aliased) {
-                b = bb != 0.f ? 1.f : -1.f;
-                c = cc != 0.f ? 1.f : -1.f;
-            }
-            float rm = __fmul_rn(r, bb);
-            if (rm == 0.f) rm = -1.f;
-            float fm = __fmul_rn(f, cc);
-            if (fm == 0.f) fm = -1.f;
-            tile[0][i] = c;
-            tile[1][i] = b;
-            tile[2][i] = fm;
-            tile[3][i] = rm;
+            const MaskedPixel q = masked_pixel(f, r, p, aliased);
+            tile[0][i] = q.c;
+            tile[1][i] = q.b;
+            tile[2][i] = q.fm;
+            tile[3][i] = q.rm;
         }
     }
     __syncthreads();

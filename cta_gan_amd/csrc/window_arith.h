@@ -50,3 +50,39 @@ __device__ __forceinline__ float level_rescale(float t) {
 }
 
 __device__ __forceinline__ float window_one(float v, const WinParams p) { return level_rescale(window_level(v, p)); }
+
+// The four masked images of one pixel of the test() loop (HdTrainer.py:1008-1023, 1041-1047): the windowed pair (c, b) and the raw
+// pair (fake * cc, real * bb), background := -1.  f = generated, r = reference sample.  Every product is rounded on its own and the
+// masks hang on exact comparisons, so every kernel that needs these images calls this one definition (ctg_window_metrics, ctg_ssim
+// mode 1, ctg_window_pairs): the same bits.
+struct MaskedPixel { float c, b, fm, rm; };
+
+__device__ __forceinline__ MaskedPixel masked_pixel(float f, float r, const WinParams p, int aliased) {
+    MaskedPixel o;
+    // b = W(real); bb = b >= 0.3; b = b*bb; b[b == 0] = -1
+    float b = window_one(r, p);
+    const float bb = b >= 0.3f ? 1.f : 0.f;
+    b = __fmul_rn(b, bb);
+    if (b == 0.f) b = -1.f;
+    // c = W(fake)*bb; cc = c >= 0.3; c = c*cc; c[c == 0] = -1
+    float c = __fmul_rn(window_one(f, p), bb);
+    const float cc = c >= 0.3f ? 1.f : 0.f;
+    c = __fmul_rn(c, cc);
+    if (c == 0.f) c = -1.f;
+    if (aliased) {
+        // trainer/CycTrainer.py:288-298 writes `bb = b` / `cc = c` WITHOUT a copy, so thresholding the masks also
+        // thresholds b and c: its windowed pair is the two binary masks mapped to +-1
+        b = bb != 0.f ? 1.f : -1.f;
+        c = cc != 0.f ? 1.f : -1.f;
+    }
+    o.c = c;
+    o.b = b;
+    // raw maps under the same masks
+    float rm = __fmul_rn(r, bb);
+    if (rm == 0.f) rm = -1.f;
+    float fm = __fmul_rn(f, cc);
+    if (fm == 0.f) fm = -1.f;
+    o.fm = fm;
+    o.rm = rm;
+    return o;
+}

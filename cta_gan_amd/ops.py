@@ -958,6 +958,24 @@ def maxpool2_fwd(x, out):
                "ctg_maxpool2_fwd")
 
 
+def maxpool3s2_fwd(x, out=None):
+    """nn.MaxPool2d(3, 2) (AlexNet's pools; no padding, floor) of an fp32 NHWC activation [B, H, W, C], C % 4 == 0 -> out
+    [B, (H-3)//2+1, (W-3)//2+1, C] (a new tensor, or `out`); bit-equal to F.max_pool2d(x, 3, 2)."""
+    lib = _lib.load()
+    if not x.is_cuda:
+        raise RuntimeError("maxpool3s2_fwd: CPU tensors are not supported (no CPU fallback)")
+    b, h, w, c, ld = _nhwc(x)
+    if x.dtype != torch.float32 or h < 3 or w < 3:
+        raise RuntimeError("maxpool3s2_fwd: fp32 maps of at least 3 x 3 pixels")
+    ho, wo = (h - 3) // 2 + 1, (w - 3) // 2 + 1
+    if out is None:
+        out = torch.empty((b, ho, wo, c), dtype=torch.float32, device=x.device)
+    ob, oh, ow, oc, o_ld = _nhwc(out)
+    assert (ob, oh, ow, oc) == (b, ho, wo, c) and out.dtype == torch.float32
+    _lib.check(lib.ctg_maxpool3s2_fwd(_p(x), ld, _p(out), o_ld, b, h, w, c, _stream()), "ctg_maxpool3s2_fwd")
+    return out
+
+
 def maxpool2_bwd(x, dout, dx, accumulate):
     lib = _lib.load()
     b, h, w, c, ld = _nhwc(x)
@@ -998,15 +1016,18 @@ def chan_pad(src_f32, cs, dtype, cpad):
     return out
 
 
-def im2col_pack(s0, s1, k, stride, pad, pad_mode, dtype, kpad):
-    """s0, s1: dense fp32 [B,H,W] single-channel images (s1 optional) -> [B,Ho,Wo,kpad]."""
+def im2col_pack(s0, s1, k, stride, pad, pad_mode, dtype, kpad, out=None):
+    """s0, s1: dense fp32 [B,H,W] single-channel images (s1 optional) -> [B,Ho,Wo,kpad] (a new tensor, or the dense `out`)."""
     lib = _lib.load()
     b, hi, wi = s0.shape
     cin = 1 if s1 is None else 2
     ho = (hi + 2 * pad - k) // stride + 1
     wo = (wi + 2 * pad - k) // stride + 1
     assert s0.is_contiguous() and (s1 is None or s1.is_contiguous())
-    out = empty_act((b, ho, wo, kpad), dtype, s0.device)
+    if out is None:
+        out = empty_act((b, ho, wo, kpad), dtype, s0.device)
+    else:
+        assert tuple(out.shape) == (b, ho, wo, kpad) and out.dtype == dtype and out.is_contiguous() and not is_pair(out)
     _lib.check(lib.ctg_im2col_pack(dtc(out), _p(s0), _p(s1), cin, b, hi, wi, k, k, stride, pad, pad_mode, _p(out),
                                    ho, wo, kpad, _stream()), "ctg_im2col_pack")
     return out
@@ -1430,6 +1451,48 @@ def window_metrics(fake, real, wc, ww, aliased=False):
     assert wcv.numel() == b and wwv.numel() == b
     _lib.check(lib.ctg_window_metrics(_p(f), _p(r), _p(wcv), _p(wwv), b, hw, nblk, int(aliased), _p(part), _p(out), _stream()),
                "ctg_window_metrics")
+    return out
+
+
+def window_pairs(fake, real, wc, ww, aliased=False):
+    """The four masked images `window_metrics` reduces, as tensors: fake, real (B, [1,] H, W) fp32 on the GPU -> fp32
+    [4, B, H, W] = [c, fake_m, b, real_m] (HdTrainer.py:1008-1023, 1041-1047).  `out[:2].reshape(2B, H, W)` is the generated side and
+    `out[2:].reshape(2B, H, W)` the reference side of the 2B pairs {windowed, raw} that the test() loop hands to LPIPS."""
+    lib = _lib.load()
+    if not (fake.is_cuda and real.is_cuda):
+        raise RuntimeError("window_pairs: CPU tensors are not supported (no CPU fallback)")
+    f, r = fake.float().contiguous(), real.float().contiguous()
+    assert f.shape == r.shape and f.dim() >= 3
+    b, h, w = f.shape[0], f.shape[-2], f.shape[-1]
+    if f.numel() != b * h * w:
+        raise RuntimeError("window_pairs: one plane per slice (B, [1,] H, W)")
+    out = torch.empty((4, b, h, w), dtype=torch.float32, device=f.device)
+    wcv, wwv = _win_vec(wc, b, f.device), _win_vec(ww, b, f.device)
+    assert wcv.numel() == b and wwv.numel() == b
+    _lib.check(lib.ctg_window_pairs(_p(f), _p(r), _p(wcv), _p(wwv), b, h * w, int(aliased), _p(out), _stream()),
+               "ctg_window_pairs")
+    return out
+
+
+LPIPS_PART = 64      # csrc/lpips.hip: most partial sums per pair of ctg_lpips_layer
+
+
+def lpips_layer(feat, lin, k, out, part=None):
+    """One layer's LPIPS distance (csrc/lpips.hip): feat fp32 NHWC [2P, H, W, C] -- images 0 .. P-1 the "x" side, P .. 2P-1 the
+    "y" side -- and lin fp32 [C] -> column k of out (float64 [P, 5]) = mean over pixels of sum_c lin[c] (n(x) - n(y))^2.
+    C % 64 == 0, C <= 384.  part: float64 workspace of P * LPIPS_PART elements (made here when absent)."""
+    lib = _lib.load()
+    if not (feat.is_cuda and lin.is_cuda and out.is_cuda):
+        raise RuntimeError("lpips_layer: CPU tensors are not supported (no CPU fallback)")
+    b2, h, w, c, ld = _nhwc(feat)
+    p = b2 // 2
+    assert b2 == 2 * p and p >= 1 and feat.dtype == torch.float32
+    assert lin.dtype == torch.float32 and lin.is_contiguous() and lin.numel() == c
+    assert out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == (p, 5)
+    if part is None:
+        part = torch.empty(p * LPIPS_PART, dtype=torch.float64, device=feat.device)
+    assert part.dtype == torch.float64 and part.is_contiguous() and part.numel() >= p * LPIPS_PART
+    _lib.check(lib.ctg_lpips_layer(_p(feat), ld, _p(lin), p, h * w, c, int(k), _p(part), _p(out), _stream()), "ctg_lpips_layer")
     return out
 
 

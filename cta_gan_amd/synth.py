@@ -84,3 +84,33 @@ def synth_smooth_images(name: str, batch: int, size: int, seed: int = 1234) -> t
         acc /= max(np.abs(acc).max(), 1e-6)
         out[b, 0] = acc
     return torch.from_numpy(out)
+
+
+def lpips_state_dict(seed: int = 0, fmt: str = "full"):
+    """Synthetic LPIPS (AlexNet) weights under the key names `cta_gan_amd.lpips.KEYS` reads: convs He-scaled, biases
+    0.1 * N(0, 1), `lin` ~ U[0, 1) (the trained ones are non-negative).  fmt "full": one dict shaped like
+    `lpips.LPIPS(net='alex').state_dict()` (with the `lins.*` duplicates and the scaling layer); fmt "two": (alexnet, lins) shaped
+    like torchvision's alexnet state dict and lpips' weights/v0.1/alex.pth.  The values do not depend on the format."""
+    from .lpips import CONVS, KEYS, SCALE, SHIFT
+    conv, lin = [], []
+    for k, (cout, cin, ks, _, _) in enumerate(CONVS):
+        w = fill_tensor("lpips.conv%d.weight" % k, (cout, cin, ks, ks), seed=seed)
+        b = torch.from_numpy((0.1 * _rng_for("lpips.conv%d.bias" % k, seed).standard_normal(cout)).astype(np.float32))
+        conv.append((w, b))
+        lin.append(torch.from_numpy(_rng_for("lpips.lin%d" % k, seed).uniform(0.0, 1.0, (1, cout, 1, 1)).astype(np.float32)))
+    if fmt == "full":
+        sd = {}
+        for k, (w, b) in enumerate(conv):
+            sd[KEYS["full_conv"][k] + ".weight"], sd[KEYS["full_conv"][k] + ".bias"] = w, b
+            sd[KEYS["lin"][k]] = lin[k]
+            sd[KEYS["lin_duplicate"][k]] = lin[k].clone()
+        sd[KEYS["shift"]] = torch.tensor(SHIFT, dtype=torch.float32).reshape(1, 3, 1, 1)
+        sd[KEYS["scale"]] = torch.tensor(SCALE, dtype=torch.float32).reshape(1, 3, 1, 1)
+        return sd
+    if fmt != "two":
+        raise ValueError("fmt: 'full' or 'two'")
+    alex = {}
+    for k, (w, b) in enumerate(conv):
+        alex[KEYS["alexnet_conv"][k] + ".weight"], alex[KEYS["alexnet_conv"][k] + ".bias"] = w, b
+    alex["classifier.1.weight"] = torch.zeros(4, 4)      # ignored by the loader
+    return alex, {KEYS["lin"][k]: lin[k] for k in range(5)}

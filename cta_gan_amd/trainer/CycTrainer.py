@@ -135,5 +135,5 @@ class Cyc_Trainer:
     def test(self, dataloader=None):
         """Inference + metrics loop of CycTrainer.py:238-398 (see Hd_Trainer_x2.test): batches are dicts with 'A', 'B'
         (B,1,S,S) and optionally 'WC' / 'WW'.  The windowed metrics reproduce the reference's aliasing (`bb = b`,
-        `cc = c` at :288-298), i.e. they compare the two +-1 foreground masks.  SSIM / SSIMw (`ops.window_ssim`) are reported as well; LPIPS, DICOM export: not built."""
+        `cc = c` at :288-298), i.e. they compare the two +-1 foreground masks.  SSIM / SSIMw (`ops.window_ssim`) are reported as well, LPIPS / LPIPSw of the same pairs with `config['lpips_weights']` (`cta_gan_amd.lpips`); DICOM export: not built."""
         return run_test_loop(self, dataloader, ("A", "B"), "aa.pth", aliased=True)

@@ -209,7 +209,12 @@ def run_test_loop(trainer, dataloader, keys, ckpt_name, aliased, uqiw_label="UQI
     p2pTrainer.py:186-312, RegTrainer.py:242-380): load `save_root/ckpt_name` into the generator if it exists, run the
     generator over the batches (dicts holding `keys` = (input, target), optionally per-slice 'WC' / 'WW') and average the
     windowed and raw MAE / PSNR / SSIM / UQI on the device.  `aliased`: the reference's `bb = b` / `cc = c` aliasing (Cyc, P2p).
-    LPIPS (a pretrained AlexNet) and the DICOM container of the same loop's export are not part of this build; the export's
+    With `config['lpips_weights']` (one path: the full `lpips.LPIPS(net='alex')` state dict; or {'alexnet': path, 'lins': path}: a
+    torchvision AlexNet state dict + lpips' weights/v0.1/alex.pth) the loop also reports `LPIPSw` / `LPIPS`, the reference's
+    `loss_fn_alex.forward` on the windowed and on the raw masked pair (HdTrainer.py:504-513, 531-536), from `cta_gan_amd.lpips` on
+    the planes `ops.window_pairs` writes; with `aliased` the windowed pair is the two +-1 masks, as in the reference.  Without the
+    key nothing of it is imported, computed or printed.
+    The DICOM container of the same loop's export is not part of this build; the export's
     pixels are, behind `config['export_root']` (absent: nothing is written): every slice's `newimg.astype(np.int16)`
     (HdTrainer.py:539-543) is saved as `<export_root>/<stem>.npy`, <stem> = the basename of `batch['A_path'][i]` without its
     extension or a running %06d index, plus `<stem>.png` (the 8-bit window level) with `config['export_png']`; rank 0 writes."""
@@ -222,6 +227,11 @@ def run_test_loop(trainer, dataloader, keys, ckpt_name, aliased, uqiw_label="UQI
         trainer.synthetic_batch(i) for i in range(cfg.get("synthetic_steps", 4)))
     total = torch.zeros(2, 3, dtype=torch.float64, device=trainer.device)
     total_ssim = torch.zeros(2, dtype=torch.float64, device=trainer.device)
+    lp = total_lpips = None
+    if cfg.get("lpips_weights"):
+        from ..lpips import LPIPS
+        lp = LPIPS.from_config(cfg["lpips_weights"])
+        total_lpips = torch.zeros(2, dtype=torch.float64, device=trainer.device)
     num = 0
     export_root = cfg.get("export_root")
     if export_root and dp.world_size() > 1 and torch.distributed.get_rank() != 0:
@@ -235,6 +245,10 @@ def run_test_loop(trainer, dataloader, keys, ckpt_name, aliased, uqiw_label="UQI
             fake_B = trainer.netG_A2B(real_A)
             total += ops.window_metrics(fake_B, real_B, wc, ww, aliased=aliased).sum(0)
             total_ssim += ops.window_ssim(fake_B, real_B, wc, ww, aliased=aliased).sum(0)      # HdTrainer.py:1028, 1053
+            if lp is not None:
+                pairs = ops.window_pairs(fake_B, real_B, wc, ww, aliased=aliased)      # [c, fake_m, b, real_m]
+                n, (h, w) = pairs.shape[1], pairs.shape[2:]
+                total_lpips += lp(pairs[:2].reshape(2 * n, h, w), pairs[2:].reshape(2 * n, h, w)).reshape(2, n).sum(1)
             if export_root:
                 _export_batch(fake_B, wc, ww, batch.get("A_path"), num, export_root, bool(cfg.get("export_png")))
             num += real_A.shape[0]
@@ -243,8 +257,17 @@ def run_test_loop(trainer, dataloader, keys, ckpt_name, aliased, uqiw_label="UQI
     ops.nie_check("test loop")      # the generator forwards above ran fused conv + InstanceNorm launches: none may have given up
     out = {"MAEw": res[0, 0], "PSNRw": res[0, 1], "UQIw": res[0, 2], "MAE": res[1, 0], "PSNR": res[1, 1],
            "UQI": res[1, 2], "SSIMw": res_ssim[0], "SSIM": res_ssim[1], "num": num}
-    print("MAEw", out["MAEw"]); print("PSNRw:", out["PSNRw"]); print("SSIMw:", out["SSIMw"]); print(uqiw_label, out["UQIw"]); print("\n")
-    print("MAE:", out["MAE"]); print("PSNR:", out["PSNR"]); print("SSIM:", out["SSIM"]); print("UQI:", out["UQI"])
+    if lp is not None:
+        res_lpips = (total_lpips / max(num, 1)).cpu().numpy()
+        out["LPIPSw"], out["LPIPS"] = res_lpips[0], res_lpips[1]
+    print("MAEw", out["MAEw"]); print("PSNRw:", out["PSNRw"]); print("SSIMw:", out["SSIMw"])
+    if lp is not None:
+        print("LPIPSw:", out["LPIPSw"])
+    print(uqiw_label, out["UQIw"]); print("\n")
+    print("MAE:", out["MAE"]); print("PSNR:", out["PSNR"]); print("SSIM:", out["SSIM"])
+    if lp is not None:
+        print("LPIPS:", out["LPIPS"])
+    print("UQI:", out["UQI"])
     return out
 
 
@@ -494,8 +517,8 @@ class _HdBase:
         are one reduction launch per batch instead of a D2H copy + numpy per slice.  Batches are dicts with 'A2', 'B2'
         (B,1,S,S) and optionally per-slice 'WC' / 'WW' (the reference reads them from the DICOM header; default:
         config['WC'], config['WW'] or 40 / 400).  Without a dataloader, `config.get('synthetic_steps', 4)` synthetic
-        batches; SSIM / SSIMw (`measure.compare_ssim`, :1028, 1053) come from `ops.window_ssim`.  LPIPS (lpips) and the DICOM
-        export are not part of this build.
+        batches; SSIM / SSIMw (`measure.compare_ssim`, :1028, 1053) come from `ops.window_ssim`, LPIPS / LPIPSw (:1029-1031, 1054-1056) from
+        `cta_gan_amd.lpips` when `config['lpips_weights']` names the weight file(s).  The DICOM export is not part of this build.
         If `config['save_root']` holds netG_A2B_x_3.pth it is loaded first, as in the reference."""
         return run_test_loop(self, dataloader, ("A2", "B2"), "netG_A2B_x_3.pth", aliased=False, uqiw_label="UQIw:")
 

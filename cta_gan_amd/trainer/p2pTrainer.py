@@ -105,5 +105,5 @@ class P2p_Trainer:
 
     def test(self, dataloader=None):
         """p2pTrainer.py:186-312 (generator inference + windowed / raw MAE, PSNR, UQI with its `bb = b`, `cc = c`
-        aliasing at :233-243) and SSIM / SSIMw; LPIPS and the DICOM export are not part of this build."""
+        aliasing at :233-243) and SSIM / SSIMw, plus LPIPS / LPIPSw with `config['lpips_weights']`; the DICOM export is not part of this build."""
         return run_test_loop(self, dataloader, ("A", "B"), "netG_A2B.pth", aliased=True)

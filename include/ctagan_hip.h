@@ -41,7 +41,7 @@ extern "C" {
 /* Bumped whenever the signature or the meaning of an existing entry point changes: a binding compares it with the value it
  * was written against before it makes any other call (cta_gan_amd/_lib.py does), so a stale library is an error, not a
  * mis-typed call. */
-#define CTG_ABI_VERSION 13
+#define CTG_ABI_VERSION 14
 int ctg_abi_version(void);
 
 /* ---- convolution: forward / backward-data / transposed, as one gather-GEMM ----
@@ -383,6 +383,26 @@ int ctg_hu_affine_inputs(const short* hu, const int* coef, int B, int Hi, int Wi
 int ctg_export_slices(const float* img, const float* wc, const float* ww, int B, int Hi, int Wi, short* pix,
                       unsigned char* level, int Ho, int Wo, int hu, void* stream);
 int ctg_series_inputs(const short* hu, int B, int Hi, int Wi, float* full, int Ho, int Wo, void* stream);
+
+/* ---- LPIPS (AlexNet, lpips 0.1) of the test() loops (ABI 14): `loss_fn_alex = lpips.LPIPS(net='alex')` (trainer/HdTrainer.py:26-28)
+ * and its calls `loss_fn_alex.forward(torch.tensor(c), torch.tensor(b))` on the windowed and on the raw masked pair of every slice
+ * (HdTrainer.py:504-513, 531-536, 1029-1031, 1054-1056; the twins in CycTrainer.py, p2pTrainer.py, RegTrainer.py).  The five
+ * convolutions run on ctg_im2col_pack / ctg_conv_igemm in fp32; the three entries below are the rest.  fp32 only.
+ * ctg_window_pairs: the four masked images ctg_window_metrics reduces, written out: out[4][B][HW] = [c, fake_m, b, real_m]
+ *   (HdTrainer.py:1008-1023, 1041-1047), i.e. planes 0 .. 2B-1 the generated side and 2B .. 4B-1 the reference side of 2B pairs;
+ *   `aliased` as in ctg_window_metrics, the same per-pixel arithmetic bit for bit.
+ * ctg_maxpool3s2_fwd: nn.MaxPool2d(kernel_size=3, stride=2) of torchvision's AlexNet features (no padding, floor): NHWC
+ *   [B][H][W][x_ld] -> [B][(H-3)/2+1][(W-3)/2+1][o_ld], C % 4 == 0, 16-byte aligned; equals F.max_pool2d bit for bit.
+ * ctg_lpips_layer: one layer's distance (lpips/__init__.py: normalize_tensor, `(feats0 - feats1) ** 2`, NetLinLayer, spatial_average).
+ *   f = features [2P][HW][f_ld], images 0 .. P-1 the "x" side and P .. 2P-1 the "y" side; lin[C] the 1x1 weights;
+ *   out[p][k] = mean over pixels of sum_c lin[c] (n(x)[c] - n(y)[c])^2, n(v) = v / (sqrt(sum_c v^2) + 1e-10), for out[P][5] doubles and
+ *   0 <= k < 5.  C % 64 == 0, 64 <= C <= 384 (CTG_EINVAL beyond).  part = P * 64 doubles of workspace; pixels are summed in fp64 in a
+ *   fixed order (no atomics): the same bits on every run. ---- */
+int ctg_window_pairs(const float* fake, const float* real, const float* wc, const float* ww, int B, long HW, int aliased,
+                     float* out, void* stream);
+int ctg_maxpool3s2_fwd(const float* x, int x_ld, float* out, int o_ld, int B, int H, int W, int C, void* stream);
+int ctg_lpips_layer(const float* f, int f_ld, const float* lin, int P, long HW, int C, int k, double* part, double* out,
+                    void* stream);
 
 /* ---- torch.optim.Adam(lr, betas=(0.5, 0.999)) step over `count` fp32 tensors (HdTrainer.py:612-616,738-739,751;
  * CycTrainer.py:67-73,162,178,197).  Host arrays of device pointers; `step` is 1-based. ---- */

@@ -6,8 +6,8 @@ on the MI355X path.  Extra flags (not in the reference): --stage {1,2} selects H
 asks the user to rename the class by hand, train.py:42); --steps N limits the synthetic run; --bf16 / --dtype select the
 compute mode (default bf16x3: the fastest one inside the reference's fp32 tolerance on outputs and gradients; bf16x3f: the same
 forward with a bf16 backward); --test runs `trainer.test()` (generator
-inference + device-side windowed / raw MAE, PSNR, SSIM, UQI; the reference's train.py:45 calls test()) instead of train() -- LPIPS
-and the DICOM container of its export are not part of this build; with `export_root` in the config test() saves every slice's int16
+inference + device-side windowed / raw MAE, PSNR, SSIM, UQI, and LPIPS when the config names `lpips_weights`; the reference's
+train.py:45 calls test()) instead of train() -- the DICOM container of its export is not part of this build; with `export_root` in the config test() saves every slice's int16
 pixels as .npy (`export_png`: + the 8-bit window as .png), and predict.py translates a whole HU series from the command line.  train() validates every fifth epoch (PSNR / SSIM, on synthetic pairs here) and puts
 both numbers into that epoch's checkpoint names, as the reference does.
 """

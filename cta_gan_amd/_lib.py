@@ -80,6 +80,8 @@ SIGNATURES = {
     "ctg_hu_affine_inputs": "ppiiifffppiip",
     "ctg_export_slices": "pppiiippiiip",
     "ctg_series_inputs": "piiipiip",
+    "ctg_project_accumulate": "piiiiiipppp",
+    "ctg_project_finish": "piliiiffippp",
     "ctg_window_pairs": "ppppilipp",
     "ctg_maxpool3s2_fwd": "pipiiiiip",
     "ctg_lpips_layer": "pipiliippp",
@@ -91,7 +93,7 @@ DIAG_SIGNATURES = {
     "ctg_lds_canary": "iipip",
 }
 _CT = {"i": _I, "l": _L, "p": _P, "f": _F, "d": ctypes.c_double}
-ABI_VERSION = 14      # CTG_ABI_VERSION of include/ctagan_hip.h this table was written against
+ABI_VERSION = 15      # CTG_ABI_VERSION of include/ctagan_hip.h this table was written against
 
 _lib = None
 

@@ -29,10 +29,10 @@ __device__ __forceinline__ float stored_value(float v) {
     return ((v + 1.0f) * 0.5f) * 4095.0f;
 }
 
-// the 8-bit window level, a whole number in [0, 255] (HdTrainer.py:42-61; NaN stays NaN)
-__device__ __forceinline__ float window_level(float v, const WinParams p) {
+// the 8-bit window level of a stored value t, a whole number in [0, 255] (HdTrainer.py:43-61; NaN stays NaN): what
+// ctg_project_finish (csrc/project.hip) applies to a projected pixel
+__device__ __forceinline__ float stored_level(float t, const WinParams p) {
 #pragma clang fp contract(off)
-    float t = stored_value(v);
     if (t == 0.0f) t = -2000.0f;
     t = t - 1024.0f;
     t = t - p.wmin;
@@ -41,6 +41,9 @@ __device__ __forceinline__ float window_level(float v, const WinParams p) {
     if (t < 0.0f) t = 0.0f;
     return t;
 }
+
+// the 8-bit window level of a generator-range sample (HdTrainer.py:42-61)
+__device__ __forceinline__ float window_level(float v, const WinParams p) { return stored_level(stored_value(v), p); }
 
 // level -> [-1, 1] (HdTrainer.py:62-63)
 __device__ __forceinline__ float level_rescale(float t) {

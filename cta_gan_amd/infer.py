@@ -5,6 +5,11 @@ PCIe at 2 B/pixel, `ops.series_inputs` makes the generator's plane on the device
 `ops.export_slices` turns its output into int16 pixels (+ the 8-bit window level) that cross back at 3 B/pixel.  Chunks of
 `batch` slices go through two page-locked slots per direction; the H2D and the D2H copies run on streams of their own behind
 events, so both hide behind the forward of the neighbouring chunks and the host only ever waits to get a slot back.
+
+Projections (`SeriesProjector`, `project_volume`, `SeriesTranslator(project=...)`): the maximum- / minimum-intensity or mean
+projection of the volume along the three body axes, and thin-slab axial ones, accumulated on the device chunk by chunk
+(`ops.project_accumulate`) as the chunks leave `ops.export_slices`; only the finished projections and their 8-bit window
+levels (`ops.project_finish`) cross PCIe, once, after the last chunk.
 """
 from __future__ import annotations
 
@@ -30,18 +35,123 @@ def _pair(size):
     return (int(size), int(size)) if isinstance(size, int) else (int(size[0]), int(size[1]))
 
 
+AXES = ("axial", "coronal", "sagittal")
+PROJECTIONS = ("max", "min", "mean")
+
+
+def slab_plan(n, thick):
+    """(S, div_last): `n` slices in S = ceil(n / thick) slabs that do not overlap, the last of div_last <= thick slices."""
+    n, thick = int(n), int(thick)
+    if n < 1 or thick < 1:
+        raise ValueError("slab_plan: n >= 1 and thick >= 1 expected, got n=%d thick=%d" % (n, thick))
+    s = (n + thick - 1) // thick
+    return s, n - (s - 1) * thick
+
+
+def aspect_rows(n, aspect):
+    """Source row of every output row when the n rows of a coronal / sagittal projection are drawn at `aspect` = slice spacing /
+    pixel spacing: round(n * aspect) rows by the index rule of the nearest Resize (trainer/utils.py:13-32; float32, as
+    `ops.resize_nearest` computes it)."""
+    rows = max(1, int(round(int(n) * float(aspect))))
+    scale = np.float32(n) / np.float32(rows)
+    return np.minimum(np.floor(np.arange(rows, dtype=np.float32) * scale).astype(np.int64), int(n) - 1)
+
+
+class SeriesProjector:
+    """Running projections of an int16 volume [n, h, w] that arrives in chunks on the device.
+
+    mode "max" (MIP), "min" (MinIP) or "mean" (ray sum / count, truncated toward zero); slab: slices per axial slab (None: the
+    whole volume, one plane; slabs do not overlap, the last may be shorter); axes: which of "axial" [S, h, w], "coronal" [n, w]
+    (the reduction over h) and "sagittal" [n, h] (over w) to keep.  `update(pix_chunk, n0)` in any order, every slice once;
+    `result(wc, ww)` -> {axis: {"values": int16, "level": uint8 or None}} on the device; `reset()` for the next volume of the
+    same shape.  Exact integer arithmetic on the current stream: equal to numpy bit for bit."""
+
+    def __init__(self, n, h, w, mode="max", slab=None, axes=AXES, device=None):
+        if mode not in PROJECTIONS:
+            raise ValueError("SeriesProjector: mode %r is not one of %s" % (mode, PROJECTIONS))
+        axes = tuple(axes)
+        if not axes or any(a not in AXES for a in axes):
+            raise ValueError("SeriesProjector: axes %r, a non-empty choice of %s expected" % (axes, AXES))
+        self.n, self.h, self.w = int(n), int(h), int(w)
+        if min(self.n, self.h, self.w) < 1:
+            raise ValueError("SeriesProjector: a volume of at least one voxel expected")
+        self.mode, self.axes = mode, tuple(a for a in AXES if a in axes)
+        self.code = ops.PROJECT_MODES[mode]
+        self.thick = self.n if slab is None else int(slab)
+        self.slabs, self.div_last = slab_plan(self.n, self.thick)
+        self.thick = min(self.thick, self.n)
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("SeriesProjector: a GPU device is required (no CPU fallback)")
+        shapes = {"axial": (self.slabs, self.h, self.w), "coronal": (self.n, self.w), "sagittal": (self.n, self.h)}
+        self.acc = {a: torch.empty(shapes[a], dtype=torch.int32, device=self.device) for a in self.axes}
+        self.reset()
+
+    def reset(self):
+        for t in self.acc.values():
+            t.fill_(ops.PROJECT_IDENTITY[self.code])
+
+    def update(self, pix_chunk, n0):
+        k = pix_chunk.shape[0]
+        if tuple(pix_chunk.shape[1:]) != (self.h, self.w) or int(n0) < 0 or int(n0) + k > self.n:
+            raise RuntimeError("SeriesProjector: chunk %s at slice %d does not lie in the volume (%d, %d, %d)"
+                               % (tuple(pix_chunk.shape), int(n0), self.n, self.h, self.w))
+        ops.project_accumulate(pix_chunk, int(n0), self.thick, self.code, **self.acc)
+
+    def result(self, wc=50.0, ww=400.0, hu=False, level=True):
+        div = {"axial": (self.thick, self.div_last), "coronal": (self.h, self.h), "sagittal": (self.w, self.w)}
+        out = {}
+        for a, acc in self.acc.items():
+            values, lvl = ops.project_finish(acc, self.code, div[a][0], div[a][1], wc=wc, ww=ww, hu=hu, want_level=level)
+            out[a] = {"values": values, "level": lvl}
+        return out
+
+
+def project_volume(volume, mode="max", slab=None, wc=50.0, ww=400.0, hu=False, batch=64, axes=AXES, level=True, device=None):
+    """The projections of a volume that already exists (the input CT, the real CTA for a side-by-side view): int16 [N, H, W],
+    a host array / CPU tensor (chunks of `batch` slices cross PCIe one after another) or a device tensor.  Returns what
+    `SeriesProjector.result` returns, of the input's kind (numpy arrays, CPU tensors or device tensors)."""
+    is_np = isinstance(volume, np.ndarray)
+    vol = torch.from_numpy(np.ascontiguousarray(volume)) if is_np else volume
+    if not torch.is_tensor(vol) or vol.dtype != torch.int16 or vol.dim() != 3:
+        raise RuntimeError("project_volume: an int16 volume [N, H, W] expected")
+    if int(batch) < 1:
+        raise ValueError("project_volume: batch >= 1 expected")
+    on_host = not vol.is_cuda
+    n, h, w = vol.shape
+    proj = SeriesProjector(n, h, w, mode=mode, slab=slab, axes=axes, device=device if on_host else vol.device)
+    with torch.cuda.device(proj.device):
+        for s, e, _ in plan_chunks(n, batch):
+            proj.update(vol[s:e].to(proj.device) if on_host else vol[s:e], s)
+        out = proj.result(wc, ww, hu=hu, level=level)
+    return _projections_to_host(out, is_np) if on_host else out
+
+
+def _projections_to_host(out, is_np):
+    conv = (lambda t: t.cpu().numpy()) if is_np else (lambda t: t.cpu())
+    return {a: {k: None if t is None else conv(t) for k, t in d.items()} for a, d in out.items()}
+
+
 class SeriesTranslator:
     """`SeriesTranslator(generator)(volume)`: int16 HU volume [N, H, W] (numpy array or CPU tensor, SimpleITK convention) ->
-    {"pix": int16 [N, H, W], "level": uint8 [N, H, W] or None}, of the input's kind.
+    {"pix": int16 [N, H, W], "level": uint8 [N, H, W] or None}, of the input's kind.  project = "max" / "min" / "mean" (slab:
+    slices per axial slab, None: the whole volume) adds "projections": {axis: {"values": int16, "level": uint8 or None}} of
+    the synthesized volume (`SeriesProjector`), in the translator's own window and `hu` (their level whatever `level` says).
 
     size: the side(s) the generator runs at (None: the volume's own); a volume of another size is resized (nearest) on the way
     in and comes back at its own size.  wc / ww: the window of the 8-bit level; hu: pixels minus 1024 (SimpleITK) instead of
     the reference's stored values; level=False skips the 8-bit plane.  Runs in whatever compute mode is set, on the current
     stream, outside any captured graph."""
 
-    def __init__(self, generator, batch=16, size=None, wc=50.0, ww=400.0, hu=False, level=True, device=None):
+    def __init__(self, generator, batch=16, size=None, wc=50.0, ww=400.0, hu=False, level=True, device=None, project=None,
+                 slab=None):
         if int(batch) < 1:
             raise ValueError("SeriesTranslator: batch >= 1 expected")
+        if project is not None and project not in PROJECTIONS:
+            raise ValueError("SeriesTranslator: project %r is not one of %s" % (project, PROJECTIONS))
+        self.project, self.slab = project, slab
+        self.window = (float(wc), float(ww))
+        self._projector = self._proj_host = None
         self.generator = generator
         self.batch = int(batch)
         self.size = None if size is None else _pair(size)
@@ -91,6 +201,7 @@ class SeriesTranslator:
         self._stage(h, w)
         with torch.cuda.device(self.device):
             cur = torch.cuda.current_stream()
+            proj = self._projector_for(n, h, w)
             in_free = [None] * SLOTS       # event: the slot's H2D copy has drained, the host may rewrite it
             pending = [None] * SLOTS       # (event, start, stop): the slot's D2H copy, not yet moved into the result
 
@@ -128,6 +239,8 @@ class SeriesTranslator:
                     x = ops.series_inputs(dev_hu, gsize).unsqueeze(1)
                     fake = self.generator(x)
                     pix, lvl = ops.export_slices(fake, self.wc[:k], self.ww[:k], size=(h, w), hu=self.hu, want_level=self.level)
+                    if proj is not None:
+                        proj.update(pix, s)
                 computed = torch.cuda.Event()
                 computed.record(cur)
                 drain(slot)                          # the chunk that used this slot last: its D2H started two chunks ago
@@ -141,12 +254,48 @@ class SeriesTranslator:
                         lvl.record_stream(self.d2h)
                     done.record()
                 pending[slot] = (done, s, e)
+            proj_done = None
+            if proj is not None:      # one copy back, after the last chunk: it runs while the host drains the last slots
+                staged = self._stage_projections(proj.result(*self.window, hu=self.hu))
+                proj_done = torch.cuda.Event()
+                proj_done.record(cur)
             for slot in sorted(range(SLOTS), key=lambda q: pending[q][1] if pending[q] else -1):
                 drain(slot)
+            projections = None
+            if proj_done is not None:
+                t0 = clock()
+                proj_done.synchronize()
+                stats["wait"] += clock() - t0
+                projections = {a: {k: t.clone().numpy() if is_np else t.clone() for k, t in d.items()} for a, d in staged.items()}
         # the forwards above ran fused conv + InstanceNorm launches: none may have given up (raises)
         ops.nie_check("series inference")
         stats["total"] = clock() - t_call
-        return self._result(out_pix, out_lvl, is_np)
+        out = self._result(out_pix, out_lvl, is_np)
+        if projections is not None:
+            out["projections"] = projections
+        return out
+
+    def _stage_projections(self, dev):
+        """Start the copies of the finished projections into page-locked buffers (kept between calls on volumes of one shape)."""
+        shapes = {a: tuple(d["values"].shape) for a, d in dev.items()}
+        if self._proj_host is None or {a: tuple(d["values"].shape) for a, d in self._proj_host.items()} != shapes:
+            self._proj_host = {a: {k: torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for k, t in d.items()}
+                               for a, d in dev.items()}
+        for a, d in dev.items():
+            for k, t in d.items():
+                self._proj_host[a][k].copy_(t, non_blocking=True)
+        return self._proj_host
+
+    def _projector_for(self, n, h, w):
+        """The projector of an (n, h, w) volume, kept between calls on volumes of one shape; None without `project`."""
+        if self.project is None:
+            return None
+        p = self._projector
+        if p is None or (p.n, p.h, p.w) != (n, h, w):
+            p = self._projector = SeriesProjector(n, h, w, mode=self.project, slab=self.slab, device=self.device)
+        else:
+            p.reset()
+        return p
 
     @staticmethod
     def _result(pix, lvl, is_np):

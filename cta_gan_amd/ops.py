@@ -1665,3 +1665,81 @@ def series_inputs(hu, size=None):
     out = torch.empty(h.shape[:-2] + (max(ho, 0), max(wo, 0)), dtype=torch.float32, device=h.device)
     _lib.check(lib.ctg_series_inputs(_p(h), b, hi, wi, _p(out), ho, wo, _stream()), "ctg_series_inputs")
     return out
+
+
+# ---------------------------------------------------------------------------- series projections (csrc/project.hip)
+PROJECT_MODES = {"max": 0, "min": 1, "sum": 2, "mean": 2}
+PROJECT_IDENTITY = (-32768, 32767, 0)      # what an accumulator holds before the first chunk, by mode code
+
+
+def _project_mode(mode, what):
+    code = PROJECT_MODES.get(mode, mode) if isinstance(mode, str) else mode
+    if isinstance(code, bool) or not isinstance(code, int) or code not in (0, 1, 2):
+        raise RuntimeError("%s: mode 0 / 'max', 1 / 'min' or 2 / 'sum' expected, got %r" % (what, mode))
+    return code
+
+
+def _project_acc(t, shape, name):
+    if t is None:
+        return
+    if not t.is_cuda or t.dtype != torch.int32 or not t.is_contiguous():
+        raise RuntimeError("project_accumulate: %s must be a contiguous int32 tensor on the GPU" % name)
+    if t.dim() != len(shape) or t.shape[0] < shape[0] or tuple(t.shape[1:]) != tuple(shape[1:]):
+        raise RuntimeError("project_accumulate: %s of shape %s cannot take this chunk (needs [>= %d%s])"
+                           % (name, tuple(t.shape), shape[0], "".join(", %d" % v for v in shape[1:])))
+
+
+def project_accumulate(pix, n0, thick, mode, axial=None, coronal=None, sagittal=None):
+    """One chunk of an int16 volume into its running projections, in place: pix (K, H, W) int16 on the GPU (a contiguous view is
+    taken as it is: 2-byte alignment is enough) = slices n0 .. n0+K-1; mode 0 / "max", 1 / "min", 2 / "sum".  int32 accumulators
+    on the GPU, any of them None: axial (S, H, W) in slabs of `thick` slices (slice n -> slab n // thick), coronal (N, W) =
+    the reduction over H, sagittal (N, H) = the reduction over W.  The caller fills them with PROJECT_IDENTITY[mode] before the
+    first chunk; every call combines.  Exact integer arithmetic, the same bits on every run."""
+    lib = _lib.load()
+    if not pix.is_cuda:
+        raise RuntimeError("project_accumulate: CPU tensors are not supported (no CPU fallback)")
+    if pix.dtype != torch.int16 or pix.dim() != 3:
+        raise RuntimeError("project_accumulate: pix must be int16 (K, H, W), got %s %s" % (pix.dtype, tuple(pix.shape)))
+    code = _project_mode(mode, "project_accumulate")
+    n0, thick = int(n0), int(thick)
+    if n0 < 0 or thick < 1:
+        raise RuntimeError("project_accumulate: n0 >= 0 and thick >= 1 expected, got n0=%d thick=%d" % (n0, thick))
+    if axial is None and coronal is None and sagittal is None:
+        raise RuntimeError("project_accumulate: at least one accumulator expected")
+    x = pix.contiguous()
+    k, h, w = x.shape
+    if k < 1:
+        return
+    _project_acc(axial, ((n0 + k - 1) // thick + 1, h, w), "axial")
+    _project_acc(coronal, (n0 + k, w), "coronal")
+    _project_acc(sagittal, (n0 + k, h), "sagittal")
+    _lib.check(lib.ctg_project_accumulate(_p(x), k, h, w, n0, thick, code, _p(axial), _p(coronal), _p(sagittal), _stream()),
+               "ctg_project_accumulate")
+
+
+def project_finish(acc, mode, div=1, div_last=None, wc=50.0, ww=400.0, hu=False, want_values=True, want_level=True):
+    """An accumulator of `project_accumulate` -> (values, level) of its shape, one launch: values int16 = the accumulator
+    (max, min) or acc / div truncated toward zero (mode 2; div_last, default div, in the last plane acc[-1] of a 3-d accumulator:
+    the last axial slab may be shorter); level uint8 = the 8-bit window level `export_slices` gives a pixel of that stored value
+    (hu: the values are stored values minus 1024).  Either is None when not wanted."""
+    lib = _lib.load()
+    if not acc.is_cuda:
+        raise RuntimeError("project_finish: CPU tensors are not supported (no CPU fallback)")
+    if acc.dtype != torch.int32 or acc.dim() not in (2, 3) or not acc.is_contiguous():
+        raise RuntimeError("project_finish: a contiguous int32 accumulator of 2 or 3 dimensions expected, got %s %s"
+                           % (acc.dtype, tuple(acc.shape)))
+    if not (want_values or want_level):
+        raise RuntimeError("project_finish: values, level or both expected")
+    code = _project_mode(mode, "project_finish")
+    div = int(div)
+    div_last = div if div_last is None else int(div_last)
+    if code == 2 and (div < 1 or div_last < 1):
+        raise RuntimeError("project_finish: div >= 1 expected, got %d / %d" % (div, div_last))
+    planes = acc.shape[0] if acc.dim() == 3 else 1
+    values = torch.empty(acc.shape, dtype=torch.int16, device=acc.device) if want_values else None
+    level = torch.empty(acc.shape, dtype=torch.uint8, device=acc.device) if want_level else None
+    if acc.numel() == 0:
+        return values, level
+    _lib.check(lib.ctg_project_finish(_p(acc), planes, acc.numel() // planes, code, div, div_last, float(wc), float(ww),
+                                      int(bool(hu)), _p(values), _p(level), _stream()), "ctg_project_finish")
+    return values, level

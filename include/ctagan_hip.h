@@ -41,7 +41,7 @@ extern "C" {
 /* Bumped whenever the signature or the meaning of an existing entry point changes: a binding compares it with the value it
  * was written against before it makes any other call (cta_gan_amd/_lib.py does), so a stale library is an error, not a
  * mis-typed call. */
-#define CTG_ABI_VERSION 14
+#define CTG_ABI_VERSION 15
 int ctg_abi_version(void);
 
 /* ---- convolution: forward / backward-data / transposed, as one gather-GEMM ----
@@ -383,6 +383,30 @@ int ctg_hu_affine_inputs(const short* hu, const int* coef, int B, int Hi, int Wi
 int ctg_export_slices(const float* img, const float* wc, const float* ww, int B, int Hi, int Wi, short* pix,
                       unsigned char* level, int Ho, int Wo, int hu, void* stream);
 int ctg_series_inputs(const short* hu, int B, int Hi, int Wi, float* full, int Ho, int Wo, void* stream);
+
+/* ---- series inference, projections (ABI 15): the maximum- / minimum-intensity and mean projections of the exported volume along
+ * the three body axes, accumulated chunk by chunk behind ctg_export_slices (cta_gan_amd/infer.py: SeriesProjector.update /
+ * .result, SeriesTranslator(project=...), project_volume).  The reference has no counterpart: its test() writes slices only.
+ * ctg_project_accumulate: pix = int16 [K][H][W], contiguous, 2-byte aligned: slices n0 .. n0+K-1 of a volume of N slices.
+ *   mode 0 max, 1 min, 2 sum.  int32 accumulators, each may be NULL (not all three):
+ *     axial    [S][H][W], S = ceil(N / thick): slice n belongs to slab n / thick (slabs do not overlap; thick >= N is the whole
+ *              volume); chunks and slabs straddle each other freely, the slab index comes from n0;
+ *     coronal  [N][W], the reduction over H;  sagittal [N][H], the reduction over W: rows n0 .. n0+K-1 are completed by this call.
+ *   The caller fills every accumulator with the mode's identity (-32768, 32767, 0) before the first chunk; the call always combines
+ *   (coronal and sagittal with int32 atomics) and never first-writes, and the calls of one volume are ordered on one stream.  Exact
+ *   integer arithmetic: the same bits on every run.  The caller sizes the accumulators for n0 + K <= N.  K, H, W, thick 1 .. 65535
+ *   (a sum of fewer than 65536 int16 values stays inside int32), n0 >= 0; anything else is CTG_EINVAL.
+ * ctg_project_finish: acc = one accumulator array of `planes` planes of `plane_items` items -> values int16 and level uint8 of
+ *   the same shape in one pass; either may be NULL (not both).  mode 2: value = acc / div, C integer division (truncating toward
+ *   zero), div_last instead of div in the last plane (the last axial slab may be shorter); coronal / sagittal: planes = 1 and
+ *   div = div_last = H / W.  mode 0, 1: the accumulator itself.  level = the tail of to_windowdata (trainer/HdTrainer.py:43-61) on
+ *   the stored value t = (float)(value + (hu ? 1024 : 0)): t == 0 -> -2000; t - 1024; t - wmin; trunc(t * dfac); clamp to
+ *   [0, 255] -- float32, every operation rounded on its own, wmin / dfac as ctg_export_slices forms them from (wc, ww): the level
+ *   ctg_export_slices gives a pixel of that stored value. ---- */
+int ctg_project_accumulate(const short* pix, int K, int H, int W, int n0, int thick, int mode, int* axial, int* coronal,
+                           int* sagittal, void* stream);
+int ctg_project_finish(const int* acc, int planes, long plane_items, int mode, int div, int div_last, float wc, float ww, int hu,
+                       short* values, unsigned char* level, void* stream);
 
 /* ---- LPIPS (AlexNet, lpips 0.1) of the test() loops (ABI 14): `loss_fn_alex = lpips.LPIPS(net='alex')` (trainer/HdTrainer.py:26-28)
  * and its calls `loss_fn_alex.forward(torch.tensor(c), torch.tensor(b))` on the windowed and on the raw masked pair of every slice

@@ -3,12 +3,18 @@
 
     python predict.py --config Yaml/HdGan.yaml --weights netG_A2B.pth --input series.npy --output out.npy
                       [--level-dir DIR] [--hu] [--wc 50 --ww 400] [--batch 16] [--dtype bf16x3]
+                      [--mip-dir DIR [--mip-mode max|min|mean] [--slab K] [--aspect R]]
 
 --input: int16 [N, H, W] .npy in SimpleITK's convention (what the reference's loaders read from the DICOMs); --weights: the
 reference-format `state_dict` of Model.HdGan.Generator (what train() saves as netG_A2B*.pth).  --output receives the int16
 volume the reference's test() writes into the DICOMs (trainer/HdTrainer.py:539-543; --hu: minus 1024, SimpleITK's convention
 again); --level-dir one 8-bit PNG per slice of the window (--wc, --ww).  The generator runs at config['size']; a series of
-another size is resized on the way in and comes back at its own.  DICOM reading and writing are not part of this build.
+another size is resized on the way in and comes back at its own.  --mip-dir: the projections of the synthesized volume along
+the three body axes (--mip-mode: maximum, minimum or mean intensity), accumulated on the device while the volume is made:
+axial_%03d.png (one per slab of --slab slices; without --slab the whole volume, axial_000.png), coronal.png and sagittal.png in
+the window, and projections.npz with the int16 values (axial [S, H, W], coronal [N, W], sagittal [N, H]).  --aspect R = slice
+spacing / pixel spacing draws the coronal and sagittal PNGs with round(N R) rows (nearest; the .npz keeps N rows).
+DICOM reading and writing are not part of this build.
 """
 import argparse
 import os
@@ -28,12 +34,20 @@ def build_parser():
     parser.add_argument("--wc", type=float, default=50.0, help="window centre of the 8-bit level")
     parser.add_argument("--ww", type=float, default=400.0, help="window width of the 8-bit level")
     parser.add_argument("--batch", type=int, default=16, help="slices per generator forward")
+    parser.add_argument("--mip-dir", type=str, default=None, help="also write the projections of the synthesized volume here")
+    parser.add_argument("--mip-mode", choices=["max", "min", "mean"], default="max", help="projection (with --mip-dir)")
+    parser.add_argument("--slab", type=int, default=None, help="slices per axial slab (default: the whole volume)")
+    parser.add_argument("--aspect", type=float, default=1.0, help="slice spacing / pixel spacing of the coronal / sagittal PNGs")
     parser.add_argument("--dtype", choices=DTYPES, default=None, help="compute mode (default %s, as train.py)" % DEFAULT_DTYPE)
     return parser
 
 
 def main(argv=None):
     opts = build_parser().parse_args(argv)
+    if opts.slab is not None and opts.slab < 1:
+        raise SystemExit("--slab: at least one slice per slab expected")
+    if opts.aspect <= 0:
+        raise SystemExit("--aspect: a positive ratio expected")
     import numpy as np
     import torch
     import yaml
@@ -54,7 +68,8 @@ def main(argv=None):
     generator = Generator(config["input_nc"], config["output_nc"]).to(device)
     generator.load_state_dict(torch.load(opts.weights, map_location=device))
     translate = SeriesTranslator(generator, batch=opts.batch, size=config.get("size"), wc=opts.wc, ww=opts.ww, hu=opts.hu,
-                                 level=opts.level_dir is not None, device=device)
+                                 level=opts.level_dir is not None, device=device,
+                                 project=opts.mip_mode if opts.mip_dir is not None else None, slab=opts.slab)
     out = translate(volume)
     np.save(opts.output, out["pix"])
     if opts.level_dir is not None:
@@ -62,6 +77,18 @@ def main(argv=None):
         os.makedirs(opts.level_dir, exist_ok=True)
         for i, plane in enumerate(out["level"]):
             Image.fromarray(plane).save(os.path.join(opts.level_dir, "%06d.png" % i))      # uint8 [H, W]: mode "L"
+    if opts.mip_dir is not None:
+        from PIL import Image
+        from cta_gan_amd.infer import aspect_rows
+        os.makedirs(opts.mip_dir, exist_ok=True)
+        proj = out["projections"]
+        for i, plane in enumerate(proj["axial"]["level"]):
+            Image.fromarray(plane).save(os.path.join(opts.mip_dir, "axial_%03d.png" % i))
+        rows = aspect_rows(volume.shape[0], opts.aspect)
+        for axis in ("coronal", "sagittal"):
+            Image.fromarray(np.ascontiguousarray(proj[axis]["level"][rows])).save(os.path.join(opts.mip_dir, axis + ".png"))
+        np.savez(os.path.join(opts.mip_dir, "projections.npz"), **{axis: proj[axis]["values"] for axis in proj})
+        print("wrote the %s projections to %s" % (opts.mip_mode, opts.mip_dir), flush=True)
     print("wrote %s: %d slices of %d x %d%s" % (opts.output, volume.shape[0], volume.shape[1], volume.shape[2],
                                                "" if opts.level_dir is None else " (+ PNGs in %s)" % opts.level_dir), flush=True)
 

@@ -1,0 +1,223 @@
+"""CPU: tests/conv_ref.py (the reference of tests/test_conv_exact_gpu.py) against torch in float64 -- exact equality on
+integer inputs: forward / transposed / backward-data / weight-gradient sums through the tap lists the engine builds, zero
+and reflection padding, the parity classes, the reflection fold as the adjoint of F.pad, and the bf16 / split-pair stores."""
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+from conv_ref import (ACT_LRELU, ACT_NONE, ACT_RELU, PAD_REFLECT, PAD_ZERO, PAIR_GRANULE, act_f32, assert_exact_domain,
+                      conv_classes_ref, conv_pair_ref, conv_taps_ref, convT_classes, epilogue, fold_frame, frame_mask,
+                      fused_store_bf16, int_grid, linear_slabs, pack_tap, pad_index, pair_grid, pair_split, place, store_bf16,
+                      store_pair, tile_slabs, unpack_tap, wgrad_pair_ref, wgrad_taps_ref)
+
+
+def _nchw(t):
+    return t.permute(0, 3, 1, 2).contiguous()
+
+
+def _nhwc(t):
+    return t.permute(0, 2, 3, 1).contiguous()
+
+
+def _w_taps(w):
+    """torch weight [Cout, Cin, kh, kw] -> [kh kw, Cout, Cin]"""
+    co, ci, kh, kw = w.shape
+    return w.permute(2, 3, 0, 1).reshape(kh * kw, co, ci).contiguous()
+
+
+def _fwd_taps(k, pad):
+    return [pack_tap(ky - pad, kx - pad, ky * k + kx) for ky in range(k) for kx in range(k)]
+
+
+def test_tap_words_and_class_lists_match_the_engine():
+    from cta_gan_amd import ops
+    from cta_gan_amd.engine import _convT_classes
+    for dy, dx, wi in ((-3, 2, 0), (0, 0, 48), (63, -64, 255)):
+        assert pack_tap(dy, dx, wi) == ops.pack_tap(dy, dx, wi) and unpack_tap(pack_tap(dy, dx, wi)) == (dy, dx, wi)
+    for k, pad in ((3, 1), (4, 1)):
+        assert convT_classes(k, pad) == _convT_classes(k, pad)
+    assert (PAD_ZERO, PAD_REFLECT, ACT_NONE, ACT_RELU, ACT_LRELU) == (ops.PAD_ZERO, ops.PAD_REFLECT, ops.ACT_NONE, ops.ACT_RELU,
+                                                                      ops.ACT_LRELU)
+
+
+@pytest.mark.parametrize("k,stride,pad", [(3, 1, 1), (3, 2, 1), (4, 1, 1), (4, 2, 1), (7, 1, 3), (1, 1, 0)],
+                         ids=["3x3s1", "3x3s2", "4x4s1", "4x4s2", "7x7", "1x1"])
+@pytest.mark.parametrize("size", [(9, 12), (10, 7)], ids=["9x12", "10x7"])
+def test_forward_equals_conv2d(k, stride, pad, size):
+    rng = np.random.default_rng(k * 10 + stride)
+    h, w = size
+    x = int_grid(rng, (2, h, w, 5), -3, 3)
+    wt = int_grid(rng, (6, 5, k, k), -3, 3)
+    ho, wo = (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
+    got = conv_taps_ref(x, _w_taps(wt), _fwd_taps(k, pad), ho, wo, stride, PAD_ZERO)
+    assert torch.equal(_nchw(got), F.conv2d(_nchw(x), wt, stride=stride, padding=pad))
+    s = conv_taps_ref(x.abs(), _w_taps(wt).abs(), _fwd_taps(k, pad), ho, wo, stride, PAD_ZERO)
+    assert bool((s >= got.abs()).all())
+    assert_exact_domain(s)
+    if pad:
+        gotr = conv_taps_ref(x, _w_taps(wt), _fwd_taps(k, pad), ho, wo, stride, PAD_REFLECT)
+        assert torch.equal(_nchw(gotr), F.conv2d(F.pad(_nchw(x), (pad,) * 4, mode="reflect"), wt, stride=stride))
+
+
+@pytest.mark.parametrize("size", [(7, 9), (6, 4)], ids=["7x9", "6x4"])
+def test_transposed_equals_conv_transpose2d_through_the_four_classes(size):
+    rng = np.random.default_rng(3)
+    h, w = size
+    x = int_grid(rng, (2, h, w, 4), -3, 3)
+    wt = int_grid(rng, (4, 6, 3, 3), -3, 3)                       # (Cin, Cout, kh, kw)
+    want = F.conv_transpose2d(_nchw(x), wt, stride=2, padding=1, output_padding=1)
+    wtaps = wt.permute(2, 3, 1, 0).reshape(9, 6, 4)
+    got = conv_classes_ref(x, wtaps, convT_classes(3, 1), h, w, PAD_ZERO)
+    assert torch.equal(_nchw(got), want)
+
+
+@pytest.mark.parametrize("k,stride", [(3, 1), (4, 1), (3, 2), (4, 2)], ids=["3x3s1", "4x4s1", "3x3s2", "4x4s2"])
+@pytest.mark.parametrize("size", [(8, 10), (9, 7)], ids=["8x10", "9x7"])
+def test_backward_data_equals_autograd(k, stride, size):
+    rng = np.random.default_rng(k + stride)
+    h, w = size
+    x = _nchw(int_grid(rng, (2, h, w, 3), -3, 3)).requires_grad_(True)
+    wt = int_grid(rng, (5, 3, k, k), -3, 3)
+    y = F.conv2d(x, wt, stride=stride, padding=1)
+    g = int_grid(rng, tuple(y.shape), -3, 3)
+    y.backward(g)
+    gn = _nhwc(g)
+    wb = wt.permute(2, 3, 1, 0).reshape(k * k, 3, 5)              # [tap][Cin][Cout]: N = Cin, K = Cout
+    if stride == 1:
+        taps = [pack_tap(1 - ky, 1 - kx, ky * k + kx) for ky in range(k) for kx in range(k)]
+        got = conv_taps_ref(gn, wb, taps, h, w, 1, PAD_ZERO)
+    else:
+        got = torch.zeros(2, h, w, 3, dtype=torch.float64)
+        for py, px, taps in convT_classes(k, 1):
+            hs, ws = (h - py + 1) // 2, (w - px + 1) // 2
+            place(got, conv_taps_ref(gn, wb, taps, hs, ws, 1, PAD_ZERO), 2, py, px)
+    assert torch.equal(_nchw(got), x.grad)
+
+
+def test_reflect_backward_data_is_frame_plus_interior_plus_fold():
+    """Backward-data of ReflectionPad2d(1) + Conv2d(3): the gradient on the padded grid (flipped taps, zero padding; ring =
+    the frame launch, interior = the tile-aligned launch), folded: equals autograd's gradient of the unpadded input."""
+    rng = np.random.default_rng(8)
+    h, w = 6, 9
+    x = _nchw(int_grid(rng, (2, h, w, 3), -3, 3)).requires_grad_(True)
+    wt = int_grid(rng, (4, 3, 3, 3), -3, 3)
+    y = F.conv2d(F.pad(x, (1, 1, 1, 1), mode="reflect"), wt)
+    g = int_grid(rng, tuple(y.shape), -3, 3)
+    y.backward(g)
+    wb = wt.permute(2, 3, 1, 0).reshape(9, 3, 4)
+    taps = [pack_tap(-ky, -kx, ky * 3 + kx) for ky in range(3) for kx in range(3)]
+    dxp = conv_taps_ref(_nhwc(g), wb, taps, h + 2, w + 2, 1, PAD_ZERO)
+    ring = frame_mask(h + 2, w + 2)
+    poisoned = torch.where(ring[None, :, :, None], dxp, torch.full_like(dxp, 777.0))      # the interior is not read
+    taps_in = [pack_tap(1 - ky, 1 - kx, ky * 3 + kx) for ky in range(3) for kx in range(3)]
+    inner = conv_taps_ref(_nhwc(g), wb, taps_in, h, w, 1, PAD_ZERO)
+    assert torch.equal(inner, dxp[:, 1:-1, 1:-1])
+    assert torch.equal(_nchw(inner + fold_frame(poisoned)), x.grad)
+    assert int(ring.sum()) == 2 * (w + 2) + 2 * h
+
+
+def test_fold_is_the_adjoint_of_reflection_pad():
+    rng = np.random.default_rng(4)
+    a = int_grid(rng, (2, 5, 7, 3), -3, 3)
+    gp = int_grid(rng, (2, 7, 9, 3), -3, 3)
+    ap = _nhwc(F.pad(_nchw(a), (1, 1, 1, 1), mode="reflect"))
+    lhs = (ap * gp).sum()
+    rhs = (a * (gp[:, 1:-1, 1:-1] + fold_frame(gp))).sum()
+    assert float(lhs) == float(rhs)
+
+
+@pytest.mark.parametrize("k,stride", [(3, 1), (3, 2), (4, 2), (1, 1)], ids=["3x3s1", "3x3s2", "4x4s2", "1x1"])
+def test_weight_gradient_equals_conv2d_weight(k, stride):
+    rng = np.random.default_rng(20 + k)
+    pad = 1 if k > 1 else 0
+    h, w = (9, 11) if stride == 1 else (11, 12)
+    x = int_grid(rng, (2, h, w, 3), -3, 3)
+    ho, wo = (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
+    g = int_grid(rng, (2, ho, wo, 5), -3, 3)
+    want = torch.nn.grad.conv2d_weight(_nchw(x), (5, 3, k, k), _nchw(g), stride=stride, padding=pad)
+    taps = _fwd_taps(k, pad)
+    dw, part = wgrad_taps_ref(g, x, taps, stride, PAD_ZERO, slabs=linear_slabs(ho, wo, 16))
+    assert torch.equal(dw.view(k, k, 5, 3).permute(2, 3, 0, 1), want)
+    assert part.shape[0] == 2 * ((ho * wo + 15) // 16) and torch.equal(part.sum(0), dw)
+    dw2, part2 = wgrad_taps_ref(g, x, taps, stride, PAD_ZERO, slabs=tile_slabs(ho, wo, 16))
+    assert torch.equal(part2.sum(0), dw) and not torch.equal(part2[0], part[0])
+    # a slab's partial is the sum over ITS pixels: only sample 0, rows-major pixels 0 .. 15
+    ids, _ = linear_slabs(ho, wo, 16)
+    g0 = g.clone()
+    g0[1:] = 0
+    g0[0][ids != 0] = 0
+    assert torch.equal(wgrad_taps_ref(g0, x, taps, stride, PAD_ZERO), part[0])
+    if k == 3 and stride == 1:      # reflection padding
+        wantr = torch.nn.grad.conv2d_weight(F.pad(_nchw(x), (1, 1, 1, 1), mode="reflect"), (5, 3, 3, 3), _nchw(g))
+        assert torch.equal(wgrad_taps_ref(g, x, taps, 1, PAD_REFLECT).view(3, 3, 5, 3).permute(2, 3, 0, 1), wantr)
+
+
+def test_transposed_weight_gradient_with_the_roles_swapped():
+    """ConvTranspose2d(k=3, s=2, p=1, op=1): dW[ci][co][ky][kx] = sum x[ci, q] g[co, 2 q + k - 1] -- the stride-2 weight
+    gradient with the layer's INPUT on the small grid in the role of G."""
+    rng = np.random.default_rng(9)
+    x = _nchw(int_grid(rng, (2, 5, 6, 4), -3, 3))
+    wt = int_grid(rng, (4, 3, 3, 3), -3, 3).requires_grad_(True)
+    y = F.conv_transpose2d(x, wt, stride=2, padding=1, output_padding=1)
+    g = int_grid(rng, tuple(y.shape), -3, 3)
+    y.backward(g)
+    dw = wgrad_taps_ref(_nhwc(x), _nhwc(g), _fwd_taps(3, 1), 2, PAD_ZERO)      # [t][ci][co]
+    assert torch.equal(dw.view(3, 3, 4, 3).permute(2, 3, 0, 1), wt.grad)
+
+
+def test_pad_index():
+    idx = torch.arange(-2, 7)
+    r, ok = pad_index(idx, 5, PAD_REFLECT)
+    assert r.tolist() == [2, 1, 0, 1, 2, 3, 4, 3, 2] and bool(ok.all())
+    r, ok = pad_index(idx, 5, PAD_ZERO)
+    assert ok.tolist() == [False, False, True, True, True, True, True, False, False]
+
+
+def test_store_helpers_equal_torch_bfloat16():
+    rng = np.random.default_rng(12)
+    v = np.concatenate([rng.standard_normal(4096).astype(np.float32) * 300,
+                        np.arange(-5000, 5001).astype(np.float32),
+                        np.array([257.0, 258.0, 259.0, 385.0, 387.0, -0.0, 0.0, 1e-30, 3.0e38], dtype=np.float32)])
+    t = torch.from_numpy(v)
+    assert torch.equal(store_bf16(v).view(torch.int16), t.bfloat16().view(torch.int16))
+    hi, lo = store_pair(v)
+    assert torch.equal(hi.view(torch.int16), t.bfloat16().view(torch.int16))
+    assert torch.equal(lo.view(torch.int16), (t - t.bfloat16().float()).bfloat16().view(torch.int16))
+    ints = np.arange(-5000, 5001).astype(np.float32)
+    frac = float((store_bf16(ints).float().numpy() != ints).mean())
+    assert frac > 0.8      # most integers of the output range are not bf16 values: the output rounding is exercised
+
+
+def test_pair_grid_splits_exactly():
+    rng = np.random.default_rng(13)
+    v = pair_grid(rng, (4, 1000))
+    hi, lo = pair_split(v)
+    assert torch.equal(hi, torch.round(v)) and bool((hi.abs() >= 1).all()) and bool((hi.abs() <= 2).all())
+    assert torch.equal(lo, v - hi) and set((lo / PAIR_GRANULE).unique().tolist()) == {-1.0, 0.0, 1.0}
+    x = pair_grid(rng, (1, 5, 6, 32))
+    w = pair_grid(rng, (9, 8, 32))
+    taps = _fwd_taps(3, 1)
+    xh, xl = pair_split(x)
+    wh, wl = pair_split(w)
+    full = conv_taps_ref(x, w, taps, 5, 6, 1, PAD_ZERO)
+    assert torch.equal(conv_pair_ref(x, w, taps, 5, 6, 1, PAD_ZERO), full - conv_taps_ref(xl, wl, taps, 5, 6, 1, PAD_ZERO))
+    g = pair_grid(rng, (1, 5, 6, 8))
+    gh, gl = pair_split(g)
+    dw, s = wgrad_pair_ref(g, x, taps, 1, PAD_ZERO)
+    assert torch.equal(dw, wgrad_taps_ref(g, x, taps, 1, PAD_ZERO) - wgrad_taps_ref(gl, xl, taps, 1, PAD_ZERO))
+    assert bool((s >= dw.abs()).all())
+
+
+def test_epilogue_in_float32():
+    acc = torch.tensor([-7.0, -1.0, 0.0, 3.0, 1001.0], dtype=torch.float64)
+    b = torch.tensor([0.125] * 5, dtype=torch.float64)
+    v = epilogue(acc, b, ACT_LRELU)
+    assert v.dtype == np.float32
+    want = F.leaky_relu((acc.float() + b.float()), 0.2)
+    assert np.array_equal(v, want.numpy())
+    assert np.array_equal(act_f32(np.float32([-2, 0, 2]), ACT_RELU), np.float32([0, 0, 2]))
+    # res is added to the ROUNDED result: 257 -> bf16 256, + 1 = 257 -> 256; adding first would give 258
+    out = fused_store_bf16(np.full((1, 4, 4, 1), 257.0, dtype=np.float32), res=torch.ones(1, 4, 4, 1, dtype=torch.float64))
+    assert float(out[0, 0, 0, 0]) == 256.0
+    assert float(store_bf16(np.float32([258.0]))[0]) == 258.0

@@ -82,6 +82,7 @@ SIGNATURES = {
     "ctg_series_inputs": "piiipiip",
     "ctg_project_accumulate": "piiiiiipppp",
     "ctg_project_finish": "piliiiffippp",
+    "ctg_project_rotate": "piiiiipiiiiiffippp",
     "ctg_window_pairs": "ppppilipp",
     "ctg_maxpool3s2_fwd": "pipiiiiip",
     "ctg_lpips_layer": "pipiliippp",

@@ -1,0 +1,136 @@
+// Series inference, the rotating view: the maximum- / minimum-intensity or mean projection of the exported int16 volume at any
+// angle about the cranio-caudal axis (cta_gan_amd/infer.py: SeriesRotator).  project.hip has the three body axes; like them the
+// reference has no counterpart (its test() writes slices only).
+//
+// A row of a rotated projection depends on one slice only: out[a][n][u] reduces slice n along the ray of detector column u at
+// angle a.  A chunk of K slices therefore finishes rows n0 .. n0+K-1 of every angle in one launch: no accumulator, no atomics, no
+// identity fill, no finish pass.  Rays take T unit steps and sample the nearest pixel on a 16.16 fixed-point grid (the technique
+// of ctg_affine_nearest, csrc/augment.hip): the sample of (u, t) is pixel
+//     xi = (c0 + c1 u + c2 t) >> 16,   yi = (c3 + c4 u + c5 t) >> 16       (arithmetic shift; counted when inside the slice)
+// with six int32 coefficients per angle formed on the host (infer.py: rotation_coefficients).  Everything up to the 8-bit level
+// is integer arithmetic, equal to numpy bit for bit; max, min and sum are exact and commutative.
+//
+// One 256-thread workgroup per (slice, segment of ROT_WG_U detector columns, angle), the angle fastest over the grid so that a
+// slice stays cache-resident across its angles.  A wave owns ROT_UL = 8 neighbouring rays and walks them with 8 lanes each: lane
+// (ul, tl) takes the steps t = tl (mod 8) of ray ul, so one gather instruction of the wave covers an 8 x 8 patch of (u, t) -- at
+// most 12 rows of the slice at any angle, where 64 lanes along u touch 64 rows at 90 degrees, one cache line each (the first
+// version of this kernel: 233 us per 16 x 512 x 512 chunk and 36 angles against 148 for this one, LAB_NOTES section 15) -- and
+// the 8 partial results of a ray meet at the end in three xor-shuffles; max, min, sum and count are exact and commutative, so the order does not show.  The steps of a ray that can lie
+// inside the slice form one interval [lo, hi] (two linear inequalities per axis, exact integer division, once per ray); the lanes
+// walk only that interval, ROT_INFLIGHT gathers issued before the first is used.  The six coefficients are workgroup-uniform
+// (scalar loads).  Whatever the interval says, a sample is read only after its own index passed the bounds check, and a sample
+// that fails it reads pixel 0 of the slice and is not counted: every address is inside the slice whatever the table holds.  The
+// fixed-point sums are formed in unsigned arithmetic (wraps, never undefined) and read as int32.
+#include "common.h"
+#include "window_arith.h"
+
+#define ROT_THREADS 256
+#define ROT_UL 8            // rays of a wave
+#define ROT_TL 8            // lanes of a ray: lane tl takes the steps t = tl (mod ROT_TL)
+#define ROT_WG_U (ROT_THREADS / 64 * ROT_UL)
+#define ROT_INFLIGHT 4      // gathers a lane issues before it uses the first
+#define ROT_MAX_DIM 4096    // H, W, U, T, A: each term of the fixed-point sum stays below 2^28
+
+enum { ROT_MAX = 0, ROT_MIN = 1, ROT_SUM = 2 };
+
+// [lo, hi] := its part with 0 <= b + c t <= lim (exact for tables in range, where nothing wraps; empty: hi < lo)
+__device__ __forceinline__ void rot_clip(int b, int c, int lim, int& lo, int& hi) {
+    if (c < 0) {      // 0 <= b + c t <= lim  <=>  0 <= (lim - b) + (-c) t <= lim
+        b = (int)((unsigned)lim - (unsigned)b);
+        c = (int)(0u - (unsigned)c);
+    }
+    const int room = (int)((unsigned)lim - (unsigned)b);
+    if (room < 0 || (c == 0 && b < 0) || c < 0) {      // (c < 0 here: INT_MIN, no table in range has it)
+        hi = lo - 1;
+        return;
+    }
+    if (c == 0) return;
+    const int first = b >= 0 ? 0 : (int)((0u - (unsigned)b + (unsigned)c - 1u) / (unsigned)c);      // ceil(-b / c)
+    const int last = (int)((unsigned)room / (unsigned)c);                                            // floor((lim - b) / c)
+    lo = lo > first ? lo : first;
+    hi = hi < last ? hi : last;
+}
+
+template <int MODE> __device__ __forceinline__ int rot_op(int a, int b) {
+    if constexpr (MODE == ROT_MAX) return a > b ? a : b;
+    else if constexpr (MODE == ROT_MIN) return a < b ? a : b;
+    else return a + b;
+}
+
+template <int MODE>
+__global__ __launch_bounds__(ROT_THREADS) void project_rotate_kernel(const short* __restrict__ pix, int H, int W, int n0, int N,
+                                                                     const int* __restrict__ coef, int A, int U, int T, int nseg,
+                                                                     int fill, float wc, float ww, int add,
+                                                                     short* __restrict__ values, unsigned char* __restrict__ level) {
+    const unsigned a = blockIdx.x % (unsigned)A, rest = blockIdx.x / (unsigned)A;
+    const unsigned seg = rest % (unsigned)nseg, k = rest / (unsigned)nseg;
+    const int lane = threadIdx.x & 63, tl = lane / ROT_UL;
+    const int u = (int)(seg * ROT_WG_U + (threadIdx.x >> 6) * ROT_UL + lane % ROT_UL);
+    const bool live = u < U;      // (every lane stays for the shuffles; the 8 lanes of a ray are live together)
+    const int* __restrict__ c = coef + (size_t)a * 6;
+    const unsigned c2 = (unsigned)c[2], c5 = (unsigned)c[5];
+    const unsigned X0 = (unsigned)c[0] + (unsigned)c[1] * (unsigned)u, Y0 = (unsigned)c[3] + (unsigned)c[4] * (unsigned)u;
+    int lo = 0, hi = live ? T - 1 : -1;
+    rot_clip((int)X0, (int)c2, (W << 16) - 1, lo, hi);
+    rot_clip((int)Y0, (int)c5, (H << 16) - 1, lo, hi);
+    const short* __restrict__ slice = pix + (size_t)k * H * W;
+    int acc = MODE == ROT_MAX ? -32768 : (MODE == ROT_MIN ? 32767 : 0), cnt = 0;
+    int t = (lo & ~(ROT_TL - 1)) + tl;      // lo >= 0
+    unsigned X = X0 + c2 * (unsigned)t, Y = Y0 + c5 * (unsigned)t;
+    const unsigned dX = c2 * ROT_TL, dY = c5 * ROT_TL;
+    for (; t <= hi; t += ROT_TL * ROT_INFLIGHT) {
+        int raw[ROT_INFLIGHT];
+        bool ok[ROT_INFLIGHT];
+#pragma unroll
+        for (int j = 0; j < ROT_INFLIGHT; ++j) {
+            const int xi = (int)X >> 16, yi = (int)Y >> 16;
+            ok[j] = t + j * ROT_TL <= hi && xi >= 0 && xi < W && yi >= 0 && yi < H;
+            raw[j] = slice[ok[j] ? yi * W + xi : 0];
+            X += dX;
+            Y += dY;
+        }
+#pragma unroll
+        for (int j = 0; j < ROT_INFLIGHT; ++j) {
+            if (!ok[j]) continue;
+            acc = rot_op<MODE>(acc, raw[j]);
+            ++cnt;
+        }
+    }
+#pragma unroll
+    for (int o = ROT_UL; o < 64; o <<= 1) {      // the 8 lanes of a ray: lane, lane ^ 8, ^ 16, ^ 32
+        acc = rot_op<MODE>(acc, __shfl_xor(acc, o, 64));
+        cnt += __shfl_xor(cnt, o, 64);
+    }
+    if (!live || tl != 0) return;
+    int v = fill;
+    if (cnt > 0) v = MODE == ROT_SUM ? acc / cnt : acc;      // C division: truncates toward zero
+    const size_t o = ((size_t)a * N + (size_t)n0 + k) * U + u;
+    if (values != nullptr) values[o] = (short)v;
+    if (level != nullptr) level[o] = (unsigned char)(int)stored_level((float)(v + add), win_params(wc, ww));
+}
+
+template <int MODE>
+static void rotate_launch(const short* pix, int K, int H, int W, int n0, int N, const int* coef, int A, int U, int T, int fill,
+                          float wc, float ww, int hu, short* values, unsigned char* level, hipStream_t st) {
+    const int nseg = (U + ROT_WG_U - 1) / ROT_WG_U;
+    hipLaunchKernelGGL(project_rotate_kernel<MODE>, dim3((unsigned)((long)K * nseg * A)), dim3(ROT_THREADS), 0, st, pix, H, W, n0, N,
+                       coef, A, U, T, nseg, fill, wc, ww, hu ? 1024 : 0, values, level);
+}
+
+extern "C" int ctg_project_rotate(const short* pix, int K, int H, int W, int n0, int N, const int* coef, int A, int U, int T,
+                                  int mode, int fill, float wc, float ww, int hu, short* values, unsigned char* level,
+                                  void* stream) {
+    CTG_ENTER();
+    if (pix == nullptr || coef == nullptr || (values == nullptr && level == nullptr)) return CTG_EINVAL;
+    if (K < 1 || n0 < 0 || N < 1 || n0 > N - K) return CTG_EINVAL;
+    if (H < 1 || H > ROT_MAX_DIM || W < 1 || W > ROT_MAX_DIM || U < 1 || U > ROT_MAX_DIM || T < 1 || T > ROT_MAX_DIM) return CTG_EINVAL;
+    if (A < 1 || A > ROT_MAX_DIM || mode < ROT_MAX || mode > ROT_SUM || fill < -32768 || fill > 32767) return CTG_EINVAL;
+    if (((uintptr_t)pix & 1) != 0 || ((uintptr_t)coef & 3) != 0 || ((uintptr_t)values & 1) != 0) return CTG_EINVAL;
+    // one workgroup per (slice, segment, angle): the grid's x dimension
+    if ((long)K * ((U + ROT_WG_U - 1) / ROT_WG_U) * A > 0x7fffffffL) return CTG_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    if (mode == ROT_MAX) rotate_launch<ROT_MAX>(pix, K, H, W, n0, N, coef, A, U, T, fill, wc, ww, hu, values, level, st);
+    else if (mode == ROT_MIN) rotate_launch<ROT_MIN>(pix, K, H, W, n0, N, coef, A, U, T, fill, wc, ww, hu, values, level, st);
+    else rotate_launch<ROT_SUM>(pix, K, H, W, n0, N, coef, A, U, T, fill, wc, ww, hu, values, level, st);
+    return ctg_launch_status();
+}

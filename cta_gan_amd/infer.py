@@ -10,9 +10,16 @@ Projections (`SeriesProjector`, `project_volume`, `SeriesTranslator(project=...)
 projection of the volume along the three body axes, and thin-slab axial ones, accumulated on the device chunk by chunk
 (`ops.project_accumulate`) as the chunks leave `ops.export_slices`; only the finished projections and their 8-bit window
 levels (`ops.project_finish`) cross PCIe, once, after the last chunk.
+
+Rotating projections (`SeriesRotator`, `rotate_volume`, `SeriesTranslator(rotate=...)`): the same projection at any number of
+view angles about the cranio-caudal axis, what an angiography volume is read as first.  A row of a rotated view depends on one
+slice only, so every chunk finishes its own rows of every angle in one launch (`ops.project_rotate`): nearest sampling on a 16.16
+fixed-point grid, unit steps along the ray, integer arithmetic throughout.  Unit steps with nearest sampling visit about 82 % of
+the voxels at 45 degrees (a ray of slope 1 skips pixels between its samples); oversampled or bilinear steps are not built.
 """
 from __future__ import annotations
 
+import math
 import time
 
 import numpy as np
@@ -132,11 +139,127 @@ def _projections_to_host(out, is_np):
     return {a: {k: None if t is None else conv(t) for k, t in d.items()} for a, d in out.items()}
 
 
+def default_detector(h, w):
+    """D = ceil(hypot(h, w)): a detector of D columns and rays of D unit steps see the whole h x w slice at every angle."""
+    return int(math.ceil(math.hypot(int(h), int(w))))
+
+
+def view_angles(count, span=360.0, start=0.0):
+    """`count` view angles in degrees, start + i * span / count."""
+    count = int(count)
+    if count < 1:
+        raise ValueError("view_angles: at least one angle expected, got %d" % count)
+    return [float(start) + i * float(span) / count for i in range(count)]
+
+
+def rotation_coefficients(angle, h, w, u=None, t=None):
+    """The six 16.16 fixed-point coefficients (c0 .. c5) of the view at `angle` degrees about the axis through the centre
+    ((w-1)/2, (h-1)/2) of an h x w slice, for a detector of u columns and rays of t unit steps (default: `default_detector`):
+    sample (i, j) of the view is pixel x = (c0 + c1 i + c2 j) >> 16, y = (c3 + c4 i + c5 j) >> 16, the nearest pixel to
+        x = cx + (i - cu) cos - (j - ct) sin,   y = cy + (i - cu) sin + (j - ct) cos,   cu = (u-1)/2, ct = (t-1)/2.
+    0 degrees is the coronal view (rays along y, the detector along x), 90 the sagittal one.  float64, rounded by
+    floor(v * 65536 + 0.5)."""
+    h, w = int(h), int(w)
+    d = default_detector(h, w)
+    u, t = d if u is None else int(u), d if t is None else int(t)
+    if min(h, w, u, t) < 1 or max(h, w, u, t) > ops.ROTATE_MAX_DIM:
+        raise ValueError("rotation_coefficients: h, w, u, t in 1 .. %d expected, got %d %d %d %d" % (ops.ROTATE_MAX_DIM, h, w, u, t))
+    rad = math.radians(float(angle))
+    cos, sin = math.cos(rad), math.sin(rad)
+    cx, cy, cu, ct = (w - 1) / 2.0, (h - 1) / 2.0, (u - 1) / 2.0, (t - 1) / 2.0
+
+    def r(v):
+        return int(math.floor(v * 65536.0 + 0.5))
+
+    return (r(cx - cu * cos + ct * sin + 0.5), r(cos), r(-sin), r(cy - cu * sin - ct * cos + 0.5), r(sin), r(cos))
+
+
+class SeriesRotator:
+    """Rotating projections of an int16 volume [n, h, w] that arrives in chunks on the device: one plane [n, U] per view angle
+    (degrees about the cranio-caudal axis; 0 = coronal, 90 = sagittal), mode "max", "min" or "mean" along rays of T unit steps.
+    detector: None (U = T = `default_detector`), an int or (U, T).  A ray that misses the slice gets `fill` (default: air, 0 or
+    -1024 with `hu`); level=False skips the 8-bit planes of the window (wc, ww).  `update(pix_chunk, n0)` in any order, every
+    slice once: a chunk finishes its own rows of every angle; `result()` -> {"values": int16 [A, n, U], "level": uint8 or None,
+    "angles": float64 [A]} on the device.  Exact integer arithmetic on the current stream: equal to numpy bit for bit."""
+
+    def __init__(self, n, h, w, angles, mode="max", detector=None, fill=None, wc=50.0, ww=400.0, hu=False, level=True, device=None):
+        if mode not in PROJECTIONS:
+            raise ValueError("SeriesRotator: mode %r is not one of %s" % (mode, PROJECTIONS))
+        self.n, self.h, self.w = int(n), int(h), int(w)
+        if min(self.n, self.h, self.w) < 1:
+            raise ValueError("SeriesRotator: a volume of at least one voxel expected")
+        self.angles = [float(a) for a in angles]
+        if not 1 <= len(self.angles) <= ops.ROTATE_MAX_DIM:
+            raise ValueError("SeriesRotator: 1 .. %d view angles expected, got %d" % (ops.ROTATE_MAX_DIM, len(self.angles)))
+        d = default_detector(self.h, self.w)
+        self.u, self.t = (d, d) if detector is None else _pair(detector)
+        self.mode, self.code = mode, ops.PROJECT_MODES[mode]
+        self.hu, self.window = bool(hu), (float(wc), float(ww))
+        self.fill = (-1024 if self.hu else 0) if fill is None else int(fill)
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("SeriesRotator: a GPU device is required (no CPU fallback)")
+        self.table = ops.RotateTable([rotation_coefficients(a, self.h, self.w, self.u, self.t) for a in self.angles], self.device)
+        shape = (len(self.angles), self.n, self.u)
+        self.values = torch.empty(shape, dtype=torch.int16, device=self.device)
+        self.level = torch.empty(shape, dtype=torch.uint8, device=self.device) if level else None
+        self._angles = torch.tensor(self.angles, dtype=torch.float64, device=self.device)
+
+    def reset(self):
+        """Nothing to refill (every update writes whole rows); kept for symmetry with `SeriesProjector`."""
+
+    def update(self, pix_chunk, n0):
+        k = pix_chunk.shape[0]
+        if tuple(pix_chunk.shape[1:]) != (self.h, self.w) or int(n0) < 0 or int(n0) + k > self.n:
+            raise RuntimeError("SeriesRotator: chunk %s at slice %d does not lie in the volume (%d, %d, %d)"
+                               % (tuple(pix_chunk.shape), int(n0), self.n, self.h, self.w))
+        if k < 1:
+            return
+        ops.project_rotate(pix_chunk, int(n0), self.table, self.t, self.code, values=self.values, level=self.level,
+                           fill=self.fill, wc=self.window[0], ww=self.window[1], hu=self.hu)
+
+    def result(self):
+        return {"values": self.values, "level": self.level, "angles": self._angles}
+
+
+def rotate_volume(volume, angles, mode="max", detector=None, fill=None, wc=50.0, ww=400.0, hu=False, level=True, batch=64,
+                  device=None):
+    """The rotating projections of a volume that already exists, the counterpart of `project_volume`: int16 [N, H, W], a host
+    array / CPU tensor (chunks of `batch` slices cross PCIe one after another) or a device tensor; angles: degrees, or an int
+    count of views around the full circle (`view_angles`).  Returns what `SeriesRotator.result` returns, of the input's kind."""
+    is_np = isinstance(volume, np.ndarray)
+    vol = torch.from_numpy(np.ascontiguousarray(volume)) if is_np else volume
+    if not torch.is_tensor(vol) or vol.dtype != torch.int16 or vol.dim() != 3:
+        raise RuntimeError("rotate_volume: an int16 volume [N, H, W] expected")
+    if int(batch) < 1:
+        raise ValueError("rotate_volume: batch >= 1 expected")
+    on_host = not vol.is_cuda
+    n, h, w = vol.shape
+    rot = SeriesRotator(n, h, w, _angle_list(angles), mode=mode, detector=detector, fill=fill, wc=wc, ww=ww, hu=hu, level=level,
+                        device=device if on_host else vol.device)
+    with torch.cuda.device(rot.device):
+        for s, e, _ in plan_chunks(n, batch):
+            rot.update(vol[s:e].to(rot.device) if on_host else vol[s:e], s)
+        out = rot.result()
+    if not on_host:
+        return out
+    return {k: None if t is None else (t.cpu().numpy() if is_np else t.cpu()) for k, t in out.items()}
+
+
+def _angle_list(rotate):
+    """`rotate` of SeriesTranslator / `angles` of rotate_volume: an int count of views around the full circle, or degrees."""
+    if isinstance(rotate, (int, np.integer)) and not isinstance(rotate, bool):
+        return view_angles(int(rotate))
+    return [float(a) for a in rotate]
+
+
 class SeriesTranslator:
     """`SeriesTranslator(generator)(volume)`: int16 HU volume [N, H, W] (numpy array or CPU tensor, SimpleITK convention) ->
     {"pix": int16 [N, H, W], "level": uint8 [N, H, W] or None}, of the input's kind.  project = "max" / "min" / "mean" (slab:
     slices per axial slab, None: the whole volume) adds "projections": {axis: {"values": int16, "level": uint8 or None}} of
     the synthesized volume (`SeriesProjector`), in the translator's own window and `hu` (their level whatever `level` says).
+    rotate = an int count of views around the full circle, or a sequence of degrees (rotate_mode: "max" / "min" / "mean", default
+    `project` or "max") adds "rotation": {"values": int16 [A, N, D], "level": uint8, "angles": float64 [A]} (`SeriesRotator`).
 
     size: the side(s) the generator runs at (None: the volume's own); a volume of another size is resized (nearest) on the way
     in and comes back at its own size.  wc / ww: the window of the 8-bit level; hu: pixels minus 1024 (SimpleITK) instead of
@@ -144,12 +267,18 @@ class SeriesTranslator:
     stream, outside any captured graph."""
 
     def __init__(self, generator, batch=16, size=None, wc=50.0, ww=400.0, hu=False, level=True, device=None, project=None,
-                 slab=None):
+                 slab=None, rotate=None, rotate_mode=None):
         if int(batch) < 1:
             raise ValueError("SeriesTranslator: batch >= 1 expected")
         if project is not None and project not in PROJECTIONS:
             raise ValueError("SeriesTranslator: project %r is not one of %s" % (project, PROJECTIONS))
         self.project, self.slab = project, slab
+        self.rotate = None if rotate is None else _angle_list(rotate)
+        self.rotate_mode = rotate_mode or project or "max"
+        if self.rotate is not None and (self.rotate_mode not in PROJECTIONS or not self.rotate):
+            raise ValueError("SeriesTranslator: rotate needs at least one angle and a rotate_mode of %s, got %r"
+                             % (PROJECTIONS, self.rotate_mode))
+        self._rotator = self._rot_host = None
         self.window = (float(wc), float(ww))
         self._projector = self._proj_host = None
         self.generator = generator
@@ -202,6 +331,7 @@ class SeriesTranslator:
         with torch.cuda.device(self.device):
             cur = torch.cuda.current_stream()
             proj = self._projector_for(n, h, w)
+            rot = self._rotator_for(n, h, w)
             in_free = [None] * SLOTS       # event: the slot's H2D copy has drained, the host may rewrite it
             pending = [None] * SLOTS       # (event, start, stop): the slot's D2H copy, not yet moved into the result
 
@@ -241,6 +371,8 @@ class SeriesTranslator:
                     pix, lvl = ops.export_slices(fake, self.wc[:k], self.ww[:k], size=(h, w), hu=self.hu, want_level=self.level)
                     if proj is not None:
                         proj.update(pix, s)
+                    if rot is not None:
+                        rot.update(pix, s)
                 computed = torch.cuda.Event()
                 computed.record(cur)
                 drain(slot)                          # the chunk that used this slot last: its D2H started two chunks ago
@@ -259,6 +391,11 @@ class SeriesTranslator:
                 staged = self._stage_projections(proj.result(*self.window, hu=self.hu))
                 proj_done = torch.cuda.Event()
                 proj_done.record(cur)
+            rot_done = None
+            if rot is not None:       # the finished planes of every angle, staged the same way
+                rot_staged = self._stage_rotation(rot.result())
+                rot_done = torch.cuda.Event()
+                rot_done.record(cur)
             for slot in sorted(range(SLOTS), key=lambda q: pending[q][1] if pending[q] else -1):
                 drain(slot)
             projections = None
@@ -267,12 +404,21 @@ class SeriesTranslator:
                 proj_done.synchronize()
                 stats["wait"] += clock() - t0
                 projections = {a: {k: t.clone().numpy() if is_np else t.clone() for k, t in d.items()} for a, d in staged.items()}
+            rotation = None
+            if rot_done is not None:
+                t0 = clock()
+                rot_done.synchronize()
+                stats["wait"] += clock() - t0
+                rotation = {k: t.clone().numpy() if is_np else t.clone() for k, t in rot_staged.items()}
+                rotation["angles"] = np.array(rot.angles, dtype=np.float64) if is_np else torch.tensor(rot.angles, dtype=torch.float64)
         # the forwards above ran fused conv + InstanceNorm launches: none may have given up (raises)
         ops.nie_check("series inference")
         stats["total"] = clock() - t_call
         out = self._result(out_pix, out_lvl, is_np)
         if projections is not None:
             out["projections"] = projections
+        if rotation is not None:
+            out["rotation"] = rotation
         return out
 
     def _stage_projections(self, dev):
@@ -285,6 +431,25 @@ class SeriesTranslator:
             for k, t in d.items():
                 self._proj_host[a][k].copy_(t, non_blocking=True)
         return self._proj_host
+
+    def _stage_rotation(self, dev):
+        """Start the copies of the rotating projections into page-locked buffers (kept between calls on volumes of one shape)."""
+        dev = {k: dev[k] for k in ("values", "level")}
+        if self._rot_host is None or self._rot_host["values"].shape != dev["values"].shape:
+            self._rot_host = {k: torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for k, t in dev.items()}
+        for k, t in dev.items():
+            self._rot_host[k].copy_(t, non_blocking=True)
+        return self._rot_host
+
+    def _rotator_for(self, n, h, w):
+        """The rotator of an (n, h, w) volume, kept between calls on volumes of one shape; None without `rotate`."""
+        if self.rotate is None:
+            return None
+        r = self._rotator
+        if r is None or (r.n, r.h, r.w) != (n, h, w):
+            r = self._rotator = SeriesRotator(n, h, w, self.rotate, mode=self.rotate_mode, wc=self.window[0], ww=self.window[1],
+                                              hu=self.hu, device=self.device)
+        return r
 
     def _projector_for(self, n, h, w):
         """The projector of an (n, h, w) volume, kept between calls on volumes of one shape; None without `project`."""

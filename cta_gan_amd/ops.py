@@ -1743,3 +1743,82 @@ def project_finish(acc, mode, div=1, div_last=None, wc=50.0, ww=400.0, hu=False,
     _lib.check(lib.ctg_project_finish(_p(acc), planes, acc.numel() // planes, code, div, div_last, float(wc), float(ww),
                                       int(bool(hu)), _p(values), _p(level), _stream()), "ctg_project_finish")
     return values, level
+
+
+# ---------------------------------------------------------------------------- rotating projections (csrc/project_rotate.hip)
+ROTATE_MAX_DIM = 4096      # H, W, U, T and the number of angles: each term of the 16.16 fixed-point sum stays below 2^28
+
+
+class RotateTable:
+    """The coefficient table of `project_rotate`: (A, 6) int32, one row (c0 .. c5) per view angle
+    (`infer.rotation_coefficients`), range-checked on the host -- |c1|, |c2|, |c4|, |c5| <= 65536 and |c0|, |c3| < 2^29, so that
+    the fixed-point sums of the kernel stay inside int32 -- and uploaded once.  `.host`: the numpy table, `.dev`: its device copy."""
+
+    def __init__(self, coef, device=None):
+        import numpy as np
+        host = np.asarray(coef.cpu() if torch.is_tensor(coef) else coef)
+        if host.ndim != 2 or host.shape[1] != 6 or host.dtype.kind not in "iu" or not 1 <= host.shape[0] <= ROTATE_MAX_DIM:
+            raise RuntimeError("project_rotate: a coefficient table of A x 6 integers, 1 <= A <= %d, expected, got %s %s"
+                               % (ROTATE_MAX_DIM, host.dtype, tuple(host.shape)))
+        host = host.astype(np.int64)
+        if (np.abs(host[:, [1, 2, 4, 5]]) > 65536).any() or (np.abs(host[:, [0, 3]]) >= 1 << 29).any():
+            raise RuntimeError("project_rotate: coefficient out of range (|c1|, |c2|, |c4|, |c5| <= 65536 and |c0|, |c3| < 2^29)")
+        self.host = np.ascontiguousarray(host.astype(np.int32))
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("project_rotate: a GPU device is required (no CPU fallback)")
+        self.dev = torch.from_numpy(self.host).to(self.device)
+        self.count = int(host.shape[0])
+
+    def __len__(self):
+        return self.count
+
+
+def _rotate_out(t, dtype, name):
+    if t is None:
+        return
+    if not torch.is_tensor(t) or not t.is_cuda or t.dtype != dtype or not t.is_contiguous() or t.dim() != 3:
+        raise RuntimeError("project_rotate: %s must be a contiguous %s tensor (A, N, U) on the GPU" % (name, dtype))
+
+
+def project_rotate(pix, n0, coef, t, mode, values=None, level=None, fill=None, wc=50.0, ww=400.0, hu=False):
+    """One chunk of an int16 volume into its rotating projections, in place: pix (K, H, W) int16 on the GPU (a contiguous view is
+    taken as it is: 2-byte alignment is enough) = slices n0 .. n0+K-1; coef: a `RotateTable`, or a host table (A, 6) that is
+    checked and uploaded by this call; t: unit steps per ray; mode 0 / "max", 1 / "min", 2 / "mean".  values int16 and level uint8
+    on the GPU, both (A, N, U), either None: the call writes rows n0 .. n0+K-1 of every plane and nothing else -- the reduction of
+    each slice along the ray of every detector column (csrc/project_rotate.hip has the sampling rule), `fill` (default: air, 0 or
+    -1024 with hu) where a ray misses the slice, and the 8-bit window level of that value.  Exact integer arithmetic: equal to
+    numpy bit for bit."""
+    lib = _lib.load()
+    if not torch.is_tensor(pix) or not pix.is_cuda:
+        raise RuntimeError("project_rotate: CPU tensors are not supported (no CPU fallback)")
+    if pix.dtype != torch.int16 or pix.dim() != 3:
+        raise RuntimeError("project_rotate: pix must be int16 (K, H, W), got %s %s" % (pix.dtype, tuple(pix.shape)))
+    code = _project_mode(mode, "project_rotate")
+    if values is None and level is None:
+        raise RuntimeError("project_rotate: values, level or both expected")
+    _rotate_out(values, torch.int16, "values")
+    _rotate_out(level, torch.uint8, "level")
+    out = values if values is not None else level
+    if values is not None and level is not None and values.shape != level.shape:
+        raise RuntimeError("project_rotate: values %s and level %s differ in shape" % (tuple(values.shape), tuple(level.shape)))
+    if torch.is_tensor(coef) and coef.is_cuda:
+        raise RuntimeError("project_rotate: the coefficients are checked on the host: pass a host table or an ops.RotateTable")
+    table = coef if isinstance(coef, RotateTable) else RotateTable(coef, pix.device)
+    if any(x is not None and x.device != pix.device for x in (values, level, table.dev)):
+        raise RuntimeError("project_rotate: pix, the coefficient table, values and level must live on one device")
+    a, n, u = out.shape
+    x = pix.contiguous()
+    k, h, w = x.shape
+    n0, t, hu = int(n0), int(t), bool(hu)
+    fill = (-1024 if hu else 0) if fill is None else int(fill)
+    if a != table.count:
+        raise RuntimeError("project_rotate: %d planes for a table of %d angles" % (a, table.count))
+    if k < 1 or n0 < 0 or n0 + k > n:
+        raise RuntimeError("project_rotate: chunk of %d slices at slice %d does not lie in the volume of %d" % (k, n0, n))
+    if not (1 <= min(h, w, u, t) and max(h, w, u, t) <= ROTATE_MAX_DIM):
+        raise RuntimeError("project_rotate: H, W, U, T in 1 .. %d expected, got %d %d %d %d" % (ROTATE_MAX_DIM, h, w, u, t))
+    if not -32768 <= fill <= 32767:
+        raise RuntimeError("project_rotate: fill %d is not an int16 value" % fill)
+    _lib.check(lib.ctg_project_rotate(_p(x), k, h, w, n0, n, _p(table.dev), a, u, t, code, fill, float(wc), float(ww), int(hu),
+                                      _p(values), _p(level), _stream()), "ctg_project_rotate")

@@ -408,6 +408,29 @@ int ctg_project_accumulate(const short* pix, int K, int H, int W, int n0, int th
 int ctg_project_finish(const int* acc, int planes, long plane_items, int mode, int div, int div_last, float wc, float ww, int hu,
                        short* values, unsigned char* level, void* stream);
 
+/* ---- series inference, rotating projections (added under ABI 15: purely additive, no existing signature or meaning moves, so
+ * the version stays 15): the maximum- / minimum-intensity or mean projection of the exported volume at any view angle about the
+ * cranio-caudal axis, chunk by chunk behind ctg_export_slices (cta_gan_amd/infer.py: SeriesRotator.update,
+ * SeriesTranslator(rotate=...), rotate_volume).  The reference has no counterpart.
+ * ctg_project_rotate: pix = int16 [K][H][W], contiguous, 2-byte aligned (a view into a larger buffer is fine): slices
+ *   n0 .. n0+K-1 of a volume of N slices.  coef = int32 [A][6] on the device, one row (c0 .. c5) per angle.  A view has a detector
+ *   of U columns and rays of T unit steps; the sample of (u, t) is pixel
+ *       xi = (c0 + c1 u + c2 t) >> 16,   yi = (c3 + c4 u + c5 t) >> 16      (arithmetic shift)
+ *   of the slice and counts only when 0 <= xi < W and 0 <= yi < H.  For the angle theta about ((W-1)/2, (H-1)/2) the host forms, in
+ *   float64 with r(v) = floor(v 65536 + 0.5), cu = (U-1)/2, ct = (T-1)/2 (infer.py: rotation_coefficients):
+ *       c0 = r(cx - cu cos + ct sin + 0.5)  c1 = r(cos)  c2 = r(-sin)      c3 = r(cy - cu sin - ct cos + 0.5)  c4 = r(sin)  c5 = r(cos)
+ *   (theta = 0: the coronal view, rays along y; 90: the sagittal view; the + 0.5 makes the sampling nearest).  The caller keeps
+ *   |c1|, |c2|, |c4|, |c5| <= 65536 and |c0|, |c3| < 2^29, so that with H, W, U, T <= 4096 the sums stay inside int32; the kernel
+ *   bounds-checks every sample index and is memory-safe whatever the table holds (the sums wrap).
+ *   mode 0 max, 1 min, 2 mean = sum / count of the ray's own counted samples, C integer division (truncating toward zero); a ray
+ *   without a counted sample gets `fill` (an int16 value).  values int16 [A][N][U] and level uint8 [A][N][U], either may be NULL
+ *   (not both): one launch writes rows n0 .. n0+K-1 of all A planes and nothing else.  level = what ctg_project_finish gives that
+ *   value for (wc, ww, hu), written in the same pass.  Exact integer arithmetic up to the level: the same bits as numpy.
+ *   CTG_EINVAL: pix or coef NULL, both outputs NULL, K < 1, n0 < 0, n0 + K > N, H / W / U / T / A outside 1 .. 4096, mode outside
+ *   0 .. 2, fill outside int16, a misaligned pointer. ---- */
+int ctg_project_rotate(const short* pix, int K, int H, int W, int n0, int N, const int* coef, int A, int U, int T, int mode,
+                       int fill, float wc, float ww, int hu, short* values, unsigned char* level, void* stream);
+
 /* ---- LPIPS (AlexNet, lpips 0.1) of the test() loops (ABI 14): `loss_fn_alex = lpips.LPIPS(net='alex')` (trainer/HdTrainer.py:26-28)
  * and its calls `loss_fn_alex.forward(torch.tensor(c), torch.tensor(b))` on the windowed and on the raw masked pair of every slice
  * (HdTrainer.py:504-513, 531-536, 1029-1031, 1054-1056; the twins in CycTrainer.py, p2pTrainer.py, RegTrainer.py).  The five

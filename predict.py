@@ -4,6 +4,7 @@
     python predict.py --config Yaml/HdGan.yaml --weights netG_A2B.pth --input series.npy --output out.npy
                       [--level-dir DIR] [--hu] [--wc 50 --ww 400] [--batch 16] [--dtype bf16x3]
                       [--mip-dir DIR [--mip-mode max|min|mean] [--slab K] [--aspect R]]
+                      [--rot-dir DIR [--rot-angles 36] [--rot-span 360] [--mip-mode max|min|mean] [--aspect R]]
 
 --input: int16 [N, H, W] .npy in SimpleITK's convention (what the reference's loaders read from the DICOMs); --weights: the
 reference-format `state_dict` of Model.HdGan.Generator (what train() saves as netG_A2B*.pth).  --output receives the int16
@@ -14,6 +15,10 @@ the three body axes (--mip-mode: maximum, minimum or mean intensity), accumulate
 axial_%03d.png (one per slab of --slab slices; without --slab the whole volume, axial_000.png), coronal.png and sagittal.png in
 the window, and projections.npz with the int16 values (axial [S, H, W], coronal [N, W], sagittal [N, H]).  --aspect R = slice
 spacing / pixel spacing draws the coronal and sagittal PNGs with round(N R) rows (nearest; the .npz keeps N rows).
+--rot-dir: the rotating projection of the synthesized volume, --rot-angles views over --rot-span degrees about the cranio-caudal
+axis (0 = coronal, 90 = sagittal; --mip-mode, --wc / --ww, --hu and --aspect as above), made on the device while the volume is
+made: rot_%03d.png, one 8-bit frame [round(N R), D] per angle with D = ceil(hypot(H, W)), and rotation.npz with values (int16
+[A, N, D]), level (uint8) and angles (degrees).
 DICOM reading and writing are not part of this build.
 """
 import argparse
@@ -38,6 +43,9 @@ def build_parser():
     parser.add_argument("--mip-mode", choices=["max", "min", "mean"], default="max", help="projection (with --mip-dir)")
     parser.add_argument("--slab", type=int, default=None, help="slices per axial slab (default: the whole volume)")
     parser.add_argument("--aspect", type=float, default=1.0, help="slice spacing / pixel spacing of the coronal / sagittal PNGs")
+    parser.add_argument("--rot-dir", type=str, default=None, help="also write the rotating projection of the synthesized volume here")
+    parser.add_argument("--rot-angles", type=int, default=36, help="view angles of the rotating projection (with --rot-dir)")
+    parser.add_argument("--rot-span", type=float, default=360.0, help="degrees the view angles are spread over (with --rot-dir)")
     parser.add_argument("--dtype", choices=DTYPES, default=None, help="compute mode (default %s, as train.py)" % DEFAULT_DTYPE)
     return parser
 
@@ -48,13 +56,15 @@ def main(argv=None):
         raise SystemExit("--slab: at least one slice per slab expected")
     if opts.aspect <= 0:
         raise SystemExit("--aspect: a positive ratio expected")
+    if opts.rot_dir is not None and opts.rot_angles < 1:
+        raise SystemExit("--rot-angles: at least one view angle expected")
     import numpy as np
     import torch
     import yaml
     with open(opts.config, "r") as stream:
         config = yaml.safe_load(stream)
     from cta_gan_amd import _lib, nets
-    from cta_gan_amd.infer import SeriesTranslator
+    from cta_gan_amd.infer import SeriesTranslator, view_angles
     from Model.HdGan import Generator
     _lib.load()
     mode = opts.dtype or DEFAULT_DTYPE
@@ -69,7 +79,9 @@ def main(argv=None):
     generator.load_state_dict(torch.load(opts.weights, map_location=device))
     translate = SeriesTranslator(generator, batch=opts.batch, size=config.get("size"), wc=opts.wc, ww=opts.ww, hu=opts.hu,
                                  level=opts.level_dir is not None, device=device,
-                                 project=opts.mip_mode if opts.mip_dir is not None else None, slab=opts.slab)
+                                 project=opts.mip_mode if opts.mip_dir is not None else None, slab=opts.slab,
+                                 rotate=view_angles(opts.rot_angles, opts.rot_span) if opts.rot_dir is not None else None,
+                                 rotate_mode=opts.mip_mode)
     out = translate(volume)
     np.save(opts.output, out["pix"])
     if opts.level_dir is not None:
@@ -89,6 +101,16 @@ def main(argv=None):
             Image.fromarray(np.ascontiguousarray(proj[axis]["level"][rows])).save(os.path.join(opts.mip_dir, axis + ".png"))
         np.savez(os.path.join(opts.mip_dir, "projections.npz"), **{axis: proj[axis]["values"] for axis in proj})
         print("wrote the %s projections to %s" % (opts.mip_mode, opts.mip_dir), flush=True)
+    if opts.rot_dir is not None:
+        from PIL import Image
+        from cta_gan_amd.infer import aspect_rows
+        os.makedirs(opts.rot_dir, exist_ok=True)
+        rot = out["rotation"]
+        rows = aspect_rows(volume.shape[0], opts.aspect)
+        for i, plane in enumerate(rot["level"]):
+            Image.fromarray(np.ascontiguousarray(plane[rows])).save(os.path.join(opts.rot_dir, "rot_%03d.png" % i))
+        np.savez(os.path.join(opts.rot_dir, "rotation.npz"), values=rot["values"], level=rot["level"], angles=rot["angles"])
+        print("wrote %d views of the %s projection to %s" % (len(rot["angles"]), opts.mip_mode, opts.rot_dir), flush=True)
     print("wrote %s: %d slices of %d x %d%s" % (opts.output, volume.shape[0], volume.shape[1], volume.shape[2],
                                                "" if opts.level_dir is None else " (+ PNGs in %s)" % opts.level_dir), flush=True)
 

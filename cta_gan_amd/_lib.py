@@ -83,6 +83,7 @@ SIGNATURES = {
     "ctg_project_accumulate": "piiiiiipppp",
     "ctg_project_finish": "piliiiffippp",
     "ctg_project_rotate": "piiiiipiiiiiffippp",
+    "ctg_subtract_slices": "ppiiiiiiiiffppp",
     "ctg_window_pairs": "ppppilipp",
     "ctg_maxpool3s2_fwd": "pipiiiiip",
     "ctg_lpips_layer": "pipiliippp",

@@ -16,6 +16,12 @@ view angles about the cranio-caudal axis, what an angiography volume is read as 
 slice only, so every chunk finishes its own rows of every angle in one launch (`ops.project_rotate`): nearest sampling on a 16.16
 fixed-point grid, unit steps along the ray, integer arithmetic throughout.  Unit steps with nearest sampling visit about 82 % of
 the voxels at 45 degrees (a ray of slope 1 skips pixels between its samples); oversampled or bilinear steps are not built.
+
+Subtraction (`subtract_volume`, `SeriesTranslator(subtract=True)`): the synthesized CTA minus the CT it was made from.  The
+generator writes on its input's pixel grid, so the pair is registered by construction: the difference of the stored values is the
+contrast-enhancement map and bone cancels without a segmentation.  One launch per chunk (`ops.subtract_slices`: 3 x 3 in-plane
+median, a floor and a band on the input HU), from the two chunks that are on the device anyway; `project_source="sub"` hands
+that chunk to the projector and the rotator instead of the synthesized one: the bone-free MIP and rotating MIP.
 """
 from __future__ import annotations
 
@@ -246,6 +252,49 @@ def rotate_volume(volume, angles, mode="max", detector=None, fill=None, wc=50.0,
     return {k: None if t is None else (t.cpu().numpy() if is_np else t.cpu()) for k, t in out.items()}
 
 
+def subtract_volume(cta, ct_hu, cta_is_hu=False, median=True, floor=0, ct_range=(None, None), wc=150.0, ww=300.0, level=True,
+                    batch=64, device=None):
+    """The subtraction of two volumes that already exist (a real CTA and its registered CT for a side-by-side view, or a
+    synthesized volume written earlier): int16 [N, H, W] each, of one kind -- host arrays / CPU tensors (chunks of `batch`
+    slices cross PCIe one after another) or device tensors.  Arguments as `ops.subtract_slices`.  Returns {"sub": int16
+    [N, H, W], "level": uint8 or None} of the input's kind.  The median is in-plane, so chunking does not change a bit."""
+    is_np = isinstance(cta, np.ndarray)
+    if is_np != isinstance(ct_hu, np.ndarray):
+        raise RuntimeError("subtract_volume: cta and ct_hu of one kind expected (both arrays or both tensors)")
+    a = torch.from_numpy(np.ascontiguousarray(cta)) if is_np else cta
+    c = torch.from_numpy(np.ascontiguousarray(ct_hu)) if is_np else ct_hu
+    for t in (a, c):
+        if not torch.is_tensor(t) or t.dtype != torch.int16 or t.dim() != 3:
+            raise RuntimeError("subtract_volume: int16 volumes [N, H, W] expected")
+    if a.shape != c.shape or a.is_cuda != c.is_cuda:
+        raise RuntimeError("subtract_volume: cta %s and ct_hu %s differ in shape or place" % (tuple(a.shape), tuple(c.shape)))
+    if int(batch) < 1:
+        raise ValueError("subtract_volume: batch >= 1 expected")
+    on_host = not a.is_cuda
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    dev = dev if on_host else a.device
+    if dev.type != "cuda":
+        raise RuntimeError("subtract_volume: a GPU device is required (no CPU fallback)")
+    n = a.shape[0]
+    sub = torch.empty(a.shape, dtype=torch.int16, device=dev)
+    lvl = torch.empty(a.shape, dtype=torch.uint8, device=dev) if level else None
+    with torch.cuda.device(dev):
+        for s, e, _ in plan_chunks(n, batch):
+            xa, xc = (a[s:e].to(dev), c[s:e].to(dev)) if on_host else (a[s:e].contiguous(), c[s:e].contiguous())
+            ds, dl = ops.subtract_slices(xa, xc, cta_is_hu=cta_is_hu, median=median, floor=floor, ct_range=ct_range, wc=wc, ww=ww,
+                                         want_level=level)
+            sub[s:e].copy_(ds)
+            if lvl is not None:
+                lvl[s:e].copy_(dl)
+    if not on_host:
+        return {"sub": sub, "level": lvl}
+    conv = (lambda t: t.cpu().numpy()) if is_np else (lambda t: t.cpu())
+    return {"sub": conv(sub), "level": None if lvl is None else conv(lvl)}
+
+
+PROJECT_SOURCES = ("cta", "sub")
+
+
 def _angle_list(rotate):
     """`rotate` of SeriesTranslator / `angles` of rotate_volume: an int count of views around the full circle, or degrees."""
     if isinstance(rotate, (int, np.integer)) and not isinstance(rotate, bool):
@@ -260,6 +309,10 @@ class SeriesTranslator:
     the synthesized volume (`SeriesProjector`), in the translator's own window and `hu` (their level whatever `level` says).
     rotate = an int count of views around the full circle, or a sequence of degrees (rotate_mode: "max" / "min" / "mean", default
     `project` or "max") adds "rotation": {"values": int16 [A, N, D], "level": uint8, "angles": float64 [A]} (`SeriesRotator`).
+    subtract=True adds "sub" (int16 [N, H, W]: synthesized minus input, `ops.subtract_slices` with sub_median, sub_floor,
+    sub_ct_range) and "sub_level" (uint8 in sub_window = (wc, ww) of a HU difference, None with level=False).
+    project_source="sub" (needs subtract=True) projects and rotates the subtraction volume instead of the synthesized one, its
+    levels in sub_window with hu=True: the bone-free MIP.  Without `subtract` nothing of this is allocated or launched.
 
     size: the side(s) the generator runs at (None: the volume's own); a volume of another size is resized (nearest) on the way
     in and comes back at its own size.  wc / ww: the window of the 8-bit level; hu: pixels minus 1024 (SimpleITK) instead of
@@ -267,9 +320,17 @@ class SeriesTranslator:
     stream, outside any captured graph."""
 
     def __init__(self, generator, batch=16, size=None, wc=50.0, ww=400.0, hu=False, level=True, device=None, project=None,
-                 slab=None, rotate=None, rotate_mode=None):
+                 slab=None, rotate=None, rotate_mode=None, subtract=False, sub_median=True, sub_floor=0, sub_ct_range=(None, None),
+                 sub_window=(150.0, 300.0), project_source="cta"):
         if int(batch) < 1:
             raise ValueError("SeriesTranslator: batch >= 1 expected")
+        if project_source not in PROJECT_SOURCES or (project_source == "sub" and not subtract):
+            raise ValueError("SeriesTranslator: project_source %r: one of %s expected, and 'sub' needs subtract=True"
+                             % (project_source, PROJECT_SOURCES))
+        self.subtract, self.project_source = bool(subtract), project_source
+        self.sub_median, self.sub_floor, self.sub_ct_range = bool(sub_median), sub_floor, tuple(sub_ct_range)
+        self.sub_window = (float(sub_window[0]), float(sub_window[1]))
+        self._sub = self._sub_lvl = None
         if project is not None and project not in PROJECTIONS:
             raise ValueError("SeriesTranslator: project %r is not one of %s" % (project, PROJECTIONS))
         self.project, self.slab = project, slab
@@ -308,6 +369,9 @@ class SeriesTranslator:
             self._in = [torch.empty(shape, dtype=torch.int16, pin_memory=True) for _ in range(SLOTS)]
             self._pix = [torch.empty(shape, dtype=torch.int16, pin_memory=True) for _ in range(SLOTS)]
             self._lvl = [torch.empty(shape, dtype=torch.uint8, pin_memory=True) for _ in range(SLOTS)] if self.level else None
+            if self.subtract:
+                self._sub = [torch.empty(shape, dtype=torch.int16, pin_memory=True) for _ in range(SLOTS)]
+                self._sub_lvl = [torch.empty(shape, dtype=torch.uint8, pin_memory=True) for _ in range(SLOTS)] if self.level else None
             self._hw = (h, w)
 
     def __call__(self, volume):
@@ -325,8 +389,10 @@ class SeriesTranslator:
         gsize = self.size or (h, w)
         out_pix = torch.empty((n, h, w), dtype=torch.int16)
         out_lvl = torch.empty((n, h, w), dtype=torch.uint8) if self.level else None
+        out_sub = torch.empty((n, h, w), dtype=torch.int16) if self.subtract else None
+        out_sub_lvl = torch.empty((n, h, w), dtype=torch.uint8) if self.subtract and self.level else None
         if n == 0:
-            return self._result(out_pix, out_lvl, is_np)
+            return self._with_sub(self._result(out_pix, out_lvl, is_np), out_sub, out_sub_lvl, is_np)
         self._stage(h, w)
         with torch.cuda.device(self.device):
             cur = torch.cuda.current_stream()
@@ -345,6 +411,10 @@ class SeriesTranslator:
                 out_pix[s:e].copy_(self._pix[slot][:e - s])
                 if out_lvl is not None:
                     out_lvl[s:e].copy_(self._lvl[slot][:e - s])
+                if out_sub is not None:
+                    out_sub[s:e].copy_(self._sub[slot][:e - s])
+                if out_sub_lvl is not None:
+                    out_sub_lvl[s:e].copy_(self._sub_lvl[slot][:e - s])
                 pending[slot] = None
                 stats["wait"] += t1 - t0
                 stats["stage_out"] += clock() - t1
@@ -369,10 +439,16 @@ class SeriesTranslator:
                     x = ops.series_inputs(dev_hu, gsize).unsqueeze(1)
                     fake = self.generator(x)
                     pix, lvl = ops.export_slices(fake, self.wc[:k], self.ww[:k], size=(h, w), hu=self.hu, want_level=self.level)
+                    sub = sub_lvl = None
+                    if self.subtract:
+                        sub, sub_lvl = ops.subtract_slices(pix, dev_hu, cta_is_hu=self.hu, median=self.sub_median,
+                                                           floor=self.sub_floor, ct_range=self.sub_ct_range, wc=self.sub_window[0],
+                                                           ww=self.sub_window[1], want_level=self.level)
+                    src = sub if self.project_source == "sub" else pix
                     if proj is not None:
-                        proj.update(pix, s)
+                        proj.update(src, s)
                     if rot is not None:
-                        rot.update(pix, s)
+                        rot.update(src, s)
                 computed = torch.cuda.Event()
                 computed.record(cur)
                 drain(slot)                          # the chunk that used this slot last: its D2H started two chunks ago
@@ -384,11 +460,17 @@ class SeriesTranslator:
                     if lvl is not None:
                         self._lvl[slot][:k].copy_(lvl, non_blocking=True)
                         lvl.record_stream(self.d2h)
+                    if sub is not None:
+                        self._sub[slot][:k].copy_(sub, non_blocking=True)
+                        sub.record_stream(self.d2h)
+                    if sub_lvl is not None:
+                        self._sub_lvl[slot][:k].copy_(sub_lvl, non_blocking=True)
+                        sub_lvl.record_stream(self.d2h)
                     done.record()
                 pending[slot] = (done, s, e)
             proj_done = None
             if proj is not None:      # one copy back, after the last chunk: it runs while the host drains the last slots
-                staged = self._stage_projections(proj.result(*self.window, hu=self.hu))
+                staged = self._stage_projections(proj.result(*self._view_window(), hu=self._view_hu()))
                 proj_done = torch.cuda.Event()
                 proj_done.record(cur)
             rot_done = None
@@ -414,7 +496,7 @@ class SeriesTranslator:
         # the forwards above ran fused conv + InstanceNorm launches: none may have given up (raises)
         ops.nie_check("series inference")
         stats["total"] = clock() - t_call
-        out = self._result(out_pix, out_lvl, is_np)
+        out = self._with_sub(self._result(out_pix, out_lvl, is_np), out_sub, out_sub_lvl, is_np)
         if projections is not None:
             out["projections"] = projections
         if rotation is not None:
@@ -447,8 +529,9 @@ class SeriesTranslator:
             return None
         r = self._rotator
         if r is None or (r.n, r.h, r.w) != (n, h, w):
-            r = self._rotator = SeriesRotator(n, h, w, self.rotate, mode=self.rotate_mode, wc=self.window[0], ww=self.window[1],
-                                              hu=self.hu, device=self.device)
+            wc, ww = self._view_window()
+            r = self._rotator = SeriesRotator(n, h, w, self.rotate, mode=self.rotate_mode, wc=wc, ww=ww, hu=self._view_hu(),
+                                              device=self.device)
         return r
 
     def _projector_for(self, n, h, w):
@@ -461,6 +544,20 @@ class SeriesTranslator:
         else:
             p.reset()
         return p
+
+    def _view_window(self):
+        """The window of the projections' and the rotation's levels: the subtraction's when that is what they show."""
+        return self.sub_window if self.project_source == "sub" else self.window
+
+    def _view_hu(self):
+        """A subtraction value is a HU difference: 0 is the window's zero, whatever convention the synthesized pixels use."""
+        return True if self.project_source == "sub" else self.hu
+
+    def _with_sub(self, out, sub, sub_lvl, is_np):
+        if self.subtract:
+            out["sub"] = sub.numpy() if is_np else sub
+            out["sub_level"] = None if sub_lvl is None else (sub_lvl.numpy() if is_np else sub_lvl)
+        return out
 
     @staticmethod
     def _result(pix, lvl, is_np):

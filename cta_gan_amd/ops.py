@@ -1822,3 +1822,52 @@ def project_rotate(pix, n0, coef, t, mode, values=None, level=None, fill=None, w
         raise RuntimeError("project_rotate: fill %d is not an int16 value" % fill)
     _lib.check(lib.ctg_project_rotate(_p(x), k, h, w, n0, n, _p(table.dev), a, u, t, code, fill, float(wc), float(ww), int(hu),
                                       _p(values), _p(level), _stream()), "ctg_project_rotate")
+
+
+# ---------------------------------------------------------------------------- subtraction volume (csrc/subtract.hip)
+INT_MIN = -2 ** 31      # `floor` of subtract_slices that keeps every difference
+
+
+def _subtract_band(ct_range):
+    lo, hi = ct_range
+    lo, hi = -32768 if lo is None else int(lo), 32767 if hi is None else int(hi)
+    if lo > hi:
+        raise RuntimeError("subtract_slices: ct_range (%d, %d) is empty" % (lo, hi))
+    return max(lo, -32768), min(hi, 32767)
+
+
+def subtract_slices(cta, ct_hu, *, cta_is_hu=False, median=True, floor=0, ct_range=(None, None), wc=150.0, ww=300.0,
+                    want_sub=True, want_level=True):
+    """Synthesized CTA minus the CT it was made from, one launch: cta (B, H, W) int16 on the GPU as `export_slices` wrote it
+    (`cta_is_hu`: with its hu=True), ct_hu (B, H, W) int16 raw HU, both contiguous (a view into a larger buffer is taken as it
+    is: 2-byte alignment is enough) -> (sub, level).  sub int16 = the difference of the stored values, `median`: after a 3 x 3
+    in-plane median (edges replicated), set to 0 where it is below `floor` (None: keep all) or where ct_hu lies outside
+    ct_range = (min, max) (None: open; the cheap air / dense-bone mask), clamped to int16; level uint8 = the 8-bit level of
+    that HU difference in the window (wc, ww), as `project_finish(..., hu=True)` forms it.  Either is None when not wanted.
+    Exact integer arithmetic: equal to numpy bit for bit."""
+    lib = _lib.load()
+    if not cta.is_cuda or not ct_hu.is_cuda:
+        raise RuntimeError("subtract_slices: CPU tensors are not supported (no CPU fallback)")
+    if cta.dtype != torch.int16 or ct_hu.dtype != torch.int16 or cta.dim() != 3:
+        raise RuntimeError("subtract_slices: cta and ct_hu must be int16 (B, H, W), got %s %s and %s %s"
+                           % (cta.dtype, tuple(cta.shape), ct_hu.dtype, tuple(ct_hu.shape)))
+    if cta.shape != ct_hu.shape or cta.device != ct_hu.device:
+        raise RuntimeError("subtract_slices: cta %s and ct_hu %s differ in shape or device" % (tuple(cta.shape), tuple(ct_hu.shape)))
+    if not cta.is_contiguous() or not ct_hu.is_contiguous():
+        raise RuntimeError("subtract_slices: contiguous inputs expected")
+    if not (want_sub or want_level):
+        raise RuntimeError("subtract_slices: sub, level or both expected")
+    ct_min, ct_max = _subtract_band(ct_range)
+    floor = INT_MIN if floor is None else max(int(floor), INT_MIN)
+    if floor > 2 ** 31 - 1:
+        raise RuntimeError("subtract_slices: floor %d is not an int32 value" % floor)
+    b, h, w = cta.shape
+    if b and (max(b, h, w) > 65535 or min(h, w) < 1):
+        raise RuntimeError("subtract_slices: B, H, W in 1 .. 65535 expected, got %d %d %d" % (b, h, w))
+    sub = torch.empty(cta.shape, dtype=torch.int16, device=cta.device) if want_sub else None
+    level = torch.empty(cta.shape, dtype=torch.uint8, device=cta.device) if want_level else None
+    if b == 0:
+        return sub, level
+    _lib.check(lib.ctg_subtract_slices(_p(cta), _p(ct_hu), b, h, w, int(bool(cta_is_hu)), int(bool(median)), floor, ct_min, ct_max,
+                                       float(wc), float(ww), _p(sub), _p(level), _stream()), "ctg_subtract_slices")
+    return sub, level

@@ -431,6 +431,27 @@ int ctg_project_finish(const int* acc, int planes, long plane_items, int mode, i
 int ctg_project_rotate(const short* pix, int K, int H, int W, int n0, int N, const int* coef, int A, int U, int T, int mode,
                        int fill, float wc, float ww, int hu, short* values, unsigned char* level, void* stream);
 
+/* ---- series inference, the subtraction volume (added under ABI 15: purely additive, no existing signature or meaning moves, so
+ * the version stays 15): synthesized CTA minus the CT it was made from, chunk by chunk behind ctg_export_slices
+ * (cta_gan_amd/infer.py: SeriesTranslator(subtract=True), subtract_volume).  The generator writes on its input's pixel grid, so the
+ * pair is registered by construction and bone cancels in the difference.
+ * ctg_subtract_slices: cta = int16 [B][H][W], the synthesized pixels as ctg_export_slices wrote them (cta_is_hu != 0: its hu
+ *   convention, stored value - 1024); ct_hu = int16 [B][H][W], the raw HU the generator was fed (ctg_series_inputs' input).  Both
+ *   contiguous and 2-byte aligned: a view one plane into a larger buffer and planes of odd H W are fine.  Per pixel, in int32:
+ *     a = max(ct_hu + 1024, 0);   b = cta + (cta_is_hu ? 1024 : 0);   d = b - a
+ *     median != 0: d = the median of the 3 x 3 in-plane neighbourhood of d, the edge pixel replicated outside the plane
+ *                  (scipy.ndimage.median_filter(size=3, mode='nearest') of every plane; H = 1 or W = 1 is legal)
+ *     d = 0 where ct_hu < ct_min, ct_hu > ct_max or d < floor: the centre pixel, after the median; equality keeps the pixel
+ *           (ct_min = -32768 and ct_max = 32767 switch the band off, floor = INT_MIN the floor)
+ *     sub = clamp(d, -32768, 32767)
+ *     level = what ctg_project_finish gives the value `sub` for (wc, ww, hu = 1): the window a HU difference is viewed in.
+ *   sub int16 [B][H][W] (2-byte aligned) and level uint8 [B][H][W]; either may be NULL (not both).  The outputs must not overlap
+ *   the inputs: with the median a pixel is read by the workgroups of its neighbours, so an in-place call is wrong.  One launch,
+ *   nothing allocates or synchronises.  Exact integer arithmetic up to the level: the same bits as numpy.
+ *   CTG_EINVAL: cta or ct_hu NULL, both outputs NULL, B / H / W outside 1 .. 65535, ct_min > ct_max, a misaligned pointer. ---- */
+int ctg_subtract_slices(const short* cta, const short* ct_hu, int B, int H, int W, int cta_is_hu, int median, int floor, int ct_min,
+                        int ct_max, float wc, float ww, short* sub, unsigned char* level, void* stream);
+
 /* ---- LPIPS (AlexNet, lpips 0.1) of the test() loops (ABI 14): `loss_fn_alex = lpips.LPIPS(net='alex')` (trainer/HdTrainer.py:26-28)
  * and its calls `loss_fn_alex.forward(torch.tensor(c), torch.tensor(b))` on the windowed and on the raw masked pair of every slice
  * (HdTrainer.py:504-513, 531-536, 1029-1031, 1054-1056; the twins in CycTrainer.py, p2pTrainer.py, RegTrainer.py).  The five

@@ -5,6 +5,8 @@
                       [--level-dir DIR] [--hu] [--wc 50 --ww 400] [--batch 16] [--dtype bf16x3]
                       [--mip-dir DIR [--mip-mode max|min|mean] [--slab K] [--aspect R]]
                       [--rot-dir DIR [--rot-angles 36] [--rot-span 360] [--mip-mode max|min|mean] [--aspect R]]
+                      [--sub-output sub.npy [--sub-level-dir DIR] [--sub-floor 0] [--sub-no-median] [--sub-ct-min HU]
+                       [--sub-ct-max HU] [--sub-wc 150 --sub-ww 300] [--mip-source cta|sub]]
 
 --input: int16 [N, H, W] .npy in SimpleITK's convention (what the reference's loaders read from the DICOMs); --weights: the
 reference-format `state_dict` of Model.HdGan.Generator (what train() saves as netG_A2B*.pth).  --output receives the int16
@@ -19,6 +21,12 @@ spacing / pixel spacing draws the coronal and sagittal PNGs with round(N R) rows
 axis (0 = coronal, 90 = sagittal; --mip-mode, --wc / --ww, --hu and --aspect as above), made on the device while the volume is
 made: rot_%03d.png, one 8-bit frame [round(N R), D] per angle with D = ceil(hypot(H, W)), and rotation.npz with values (int16
 [A, N, D]), level (uint8) and angles (degrees).
+--sub-output: the subtraction volume, synthesized CTA minus the input CT (int16 [N, H, W] .npy of HU differences), made on the
+device while the volume is made: the pair is registered by construction, so bone cancels.  A 3 x 3 in-plane median unless
+--sub-no-median; differences below --sub-floor, and pixels whose input HU lies outside --sub-ct-min .. --sub-ct-max (default:
+open), become 0.  --sub-level-dir: one 8-bit PNG per slice in the window --sub-wc / --sub-ww of a HU difference.  --mip-source
+sub makes --mip-dir and --rot-dir show the subtraction volume (levels in the --sub window) instead of the synthesized one: the
+bone-free MIP.
 DICOM reading and writing are not part of this build.
 """
 import argparse
@@ -46,12 +54,31 @@ def build_parser():
     parser.add_argument("--rot-dir", type=str, default=None, help="also write the rotating projection of the synthesized volume here")
     parser.add_argument("--rot-angles", type=int, default=36, help="view angles of the rotating projection (with --rot-dir)")
     parser.add_argument("--rot-span", type=float, default=360.0, help="degrees the view angles are spread over (with --rot-dir)")
+    parser.add_argument("--sub-output", type=str, default=None, help="also write the subtraction volume (synthesized - input) here")
+    parser.add_argument("--sub-level-dir", type=str, default=None, help="one 8-bit PNG per subtraction slice (with --sub-output)")
+    parser.add_argument("--sub-floor", type=int, default=0, help="differences below this many HU become 0")
+    parser.add_argument("--sub-no-median", action="store_true", help="skip the 3 x 3 in-plane median of the difference")
+    parser.add_argument("--sub-ct-min", type=int, default=None, help="pixels whose input HU is below this become 0")
+    parser.add_argument("--sub-ct-max", type=int, default=None, help="pixels whose input HU is above this become 0")
+    parser.add_argument("--sub-wc", type=float, default=150.0, help="window centre of the subtraction's 8-bit level")
+    parser.add_argument("--sub-ww", type=float, default=300.0, help="window width of the subtraction's 8-bit level")
+    parser.add_argument("--mip-source", choices=["cta", "sub"], default="cta", help="what --mip-dir / --rot-dir project")
     parser.add_argument("--dtype", choices=DTYPES, default=None, help="compute mode (default %s, as train.py)" % DEFAULT_DTYPE)
     return parser
 
 
+def parse_args(argv=None):
+    parser = build_parser()
+    opts = parser.parse_args(argv)
+    if opts.sub_output is None and (opts.mip_source == "sub" or opts.sub_level_dir is not None):
+        parser.error("--mip-source sub and --sub-level-dir need --sub-output")
+    if opts.sub_ct_min is not None and opts.sub_ct_max is not None and opts.sub_ct_min > opts.sub_ct_max:
+        parser.error("--sub-ct-min above --sub-ct-max")
+    return opts
+
+
 def main(argv=None):
-    opts = build_parser().parse_args(argv)
+    opts = parse_args(argv)
     if opts.slab is not None and opts.slab < 1:
         raise SystemExit("--slab: at least one slice per slab expected")
     if opts.aspect <= 0:
@@ -78,7 +105,10 @@ def main(argv=None):
     generator = Generator(config["input_nc"], config["output_nc"]).to(device)
     generator.load_state_dict(torch.load(opts.weights, map_location=device))
     translate = SeriesTranslator(generator, batch=opts.batch, size=config.get("size"), wc=opts.wc, ww=opts.ww, hu=opts.hu,
-                                 level=opts.level_dir is not None, device=device,
+                                 level=opts.level_dir is not None or opts.sub_level_dir is not None, device=device,
+                                 subtract=opts.sub_output is not None, sub_median=not opts.sub_no_median, sub_floor=opts.sub_floor,
+                                 sub_ct_range=(opts.sub_ct_min, opts.sub_ct_max), sub_window=(opts.sub_wc, opts.sub_ww),
+                                 project_source=opts.mip_source,
                                  project=opts.mip_mode if opts.mip_dir is not None else None, slab=opts.slab,
                                  rotate=view_angles(opts.rot_angles, opts.rot_span) if opts.rot_dir is not None else None,
                                  rotate_mode=opts.mip_mode)
@@ -89,6 +119,14 @@ def main(argv=None):
         os.makedirs(opts.level_dir, exist_ok=True)
         for i, plane in enumerate(out["level"]):
             Image.fromarray(plane).save(os.path.join(opts.level_dir, "%06d.png" % i))      # uint8 [H, W]: mode "L"
+    if opts.sub_output is not None:
+        np.save(opts.sub_output, out["sub"])
+        if opts.sub_level_dir is not None:
+            from PIL import Image
+            os.makedirs(opts.sub_level_dir, exist_ok=True)
+            for i, plane in enumerate(out["sub_level"]):
+                Image.fromarray(plane).save(os.path.join(opts.sub_level_dir, "%06d.png" % i))
+        print("wrote the subtraction volume to %s" % opts.sub_output, flush=True)
     if opts.mip_dir is not None:
         from PIL import Image
         from cta_gan_amd.infer import aspect_rows

@@ -45,6 +45,13 @@ struct StripArgs {
 // pixels p, p + 1 and p + 2 are all conflict-free; conv_halo's swz<4> (tiles read at one pixel offset only) leaves two of the
 // three 2-way conflicted.
 __device__ __forceinline__ int strip_swz(int px, int c) { return c ^ ((px >> 1) & 3); }
+// none / ReLU / LeakyReLU by the negative slope (1 / 0 / 0.2): v > 0 ? v : v * slope, the product as fma(v, slope, +0).  The "+ 0"
+// changes one thing: a negative v under ReLU gives +0 as act_apply does (v * 0.f alone is -0: other bits than conv_halo_kernel
+// stores for the same pixel); a non-zero product is unchanged (same single rounding).  NaN and infinities behave as v * slope
+// always did here: a NaN pre-activation stays NaN under every activation (none and LeakyReLU as in act_apply and torch; under
+// ReLU act_apply would store 0), and -inf under ReLU gives NaN (act_apply: 0) -- a diverged step stays visible to isfinite checks.
+// (v = -0 under none / LeakyReLU would give +0 where act_apply gives -0; acc + bias in round-to-nearest is -0 only for -0 + -0.)
+__device__ __forceinline__ float strip_act(float v, float neg_slope) { return v > 0.f ? v : __builtin_fmaf(v, neg_slope, 0.f); }
 
 template <bool FLIP, bool EPI>
 __global__ __launch_bounds__(256, 2) void conv_strip32_kernel(const StripArgs a) {
@@ -142,7 +149,11 @@ __global__ __launch_bounds__(256, 2) void conv_strip32_kernel(const StripArgs a)
 #pragma unroll
     for (int j = 0; j < STRIP_R; ++j)
         if (j < nin) issue_row(j);
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * (STRIP_R - 3)) : "memory");     // rows 0, 1, 2 (and the weight / bias loads)
+    // rows 0, 1, 2 (and the weight / bias loads).  With the whole ring in flight the 2 (R - 3) newest instructions are the rows
+    // behind them; a band shorter than the ring (a last band of < R - 2 rows) has fewer rows in flight, and the same count would
+    // let its rows 0 .. 2 be read before they have landed
+    if (nin >= STRIP_R) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * (STRIP_R - 3)) : "memory");
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     read_row(0, 0);
     read_row(1, 1);
     read_row(2, 2);
@@ -182,7 +193,7 @@ __global__ __launch_bounds__(256, 2) void conv_strip32_kernel(const StripArgs a)
                         float v = acc[nt][r];
                         if constexpr (EPI) {
                             v += bv[nt][r];
-                            v = v > 0.f ? v : v * neg_slope;
+                            v = strip_act(v, neg_slope);
                         }
                         o[r] = (bf16_t)v;
                     }
@@ -389,7 +400,7 @@ __global__ __launch_bounds__(256, 2) void conv_strip32p_kernel(const StripArgs a
                             float v = acc[q][nt][r];
                             if constexpr (EPI) {
                                 v += bv[nt][r];
-                                v = v > 0.f ? v : v * neg_slope;
+                                v = strip_act(v, neg_slope);
                             }
                             hi[r] = (bf16_t)v;
                             lo[r] = (bf16_t)(v - (float)hi[r]);

@@ -4,7 +4,9 @@
     part[z][t][m][c]             = sum over slab z of G[n, j, i, m] * X[n, pad(j*is+dy_t), pad(i*is+dx_t), c]
 
 for the tests of csrc/conv_igemm.hip, conv_halo.h, conv_wgrad.hip, conv_small.hip, corr_small.hip, conv_tail.hip and
-conv_cout1.hip (tests/test_conv_exact_gpu.py) and its own check against torch (tests/test_conv_ref.py).
+conv_cout1.hip (tests/test_conv_exact_gpu.py), of the sliding-window kernels csrc/conv_strip*.h (tests/test_strip_exact_gpu.py:
+the band plan, the per-slab moments and the float64 torch wrappers for their large shapes are at the end of this file) and its
+own check against torch (tests/test_conv_ref.py).
 
 The accumulators are float64.  On INTEGER-GRID operands (small integers, or integers plus multiples of 2^-10 for the
 split-pair mode) every product and every partial sum is a multiple of the grid's granule; while the sum of the terms'
@@ -298,3 +300,96 @@ def first_diff(got, want):
         return None
     idx = tuple(int(i) for i in ne.nonzero()[0])
     return idx, float(got[idx]), float(want[idx]), int(ne.sum())
+
+
+# ---------------------------------------------------------------------------- sliding-window ("strip") kernels
+def band_plan(rows, min_band, slots, strips):
+    """Mirror of band_plan in csrc/conv_dispatch.h with band_env = 0: as many bands per strip as fill `slots` once over `strips`
+    strips, but no band shorter than min_band.  -> (band_rows, nbands)"""
+    nb = max(1, slots // strips)
+    band = max((rows + nb - 1) // nb, min_band)
+    return band, (rows + band - 1) // band
+
+
+def plan_edges(rows, cols, band_rows):
+    """(band_rows, nbands, rows of the last band, nstrips, columns of the last strip) of a rows x cols grid cut into bands of
+    band_rows rows and strips of 16 columns."""
+    nbands, nstrips = (rows + band_rows - 1) // band_rows, (cols + 15) // 16
+    return band_rows, nbands, rows - (nbands - 1) * band_rows, nstrips, cols - (nstrips - 1) * 16
+
+
+def band_slabs(rows, cols, band_rows, os_=1):
+    """Slab of every OUTPUT pixel of a strip kernel: slab = band * nstrips + strip, one band x one 16-column strip of the
+    rows x cols grid the kernel walks.  os_ = 2 (the transposed kernels: the grid is the INPUT's): the four parity classes of a
+    grid pixel -- output pixels (2 j + py, 2 i + px) -- lie in the slab of (j, i).  -> ([os rows, os cols] ids, count)"""
+    nbands, nstrips = (rows + band_rows - 1) // band_rows, (cols + 15) // 16
+    j, i = torch.arange(rows * os_) // os_, torch.arange(cols * os_) // os_
+    return (j[:, None] // band_rows) * nstrips + i[None, :] // 16, nbands * nstrips
+
+
+def slab_moments_ref(acc, slabs):
+    """Exact per-slab (sum, sum of squares) of the accumulators [B, H, W, C] -> [B, count, C, 2] float64; slabs = band_slabs()."""
+    ids, cnt = slabs
+    a = acc.double()
+    b, h, w, c = a.shape
+    assert tuple(ids.shape) == (h, w)
+    out = torch.zeros(b, cnt, c, 2, dtype=torch.float64)
+    flat = a.reshape(b, h * w, c)
+    idx = ids.reshape(-1)
+    out[..., 0].index_add_(1, idx, flat)
+    out[..., 1].index_add_(1, idx, flat * flat)
+    return out
+
+
+def _chunks(n, chunk):
+    return [(s, min(n, s + chunk)) for s in range(0, n, chunk)]
+
+
+def conv3x3_f64(x, w, flipped=False, pad_mode=PAD_ZERO, stride=1, chunk=16):
+    """float64 torch conv2d over explicitly padded input, for the large shapes of the strip kernels: the ABI's sum for the nine
+    taps of a 3x3 window in forward order (tap ky*3+kx reads x[s j + ky - 1, s i + kx - 1]) or flipped (backward-data: tap
+    ky*3+kx reads x[j + 1 - ky, i + 1 - kx]), slice t of w [9, Cout, Cin] for tap t.  x NHWC [B, H, W, Cin] -> [B, Ho, Wo, Cout],
+    `chunk` samples at a time.  Equals conv_taps_ref (tests/test_conv_ref.py)."""
+    x, w = x.double(), w.double()
+    co, ci = w.shape[1], w.shape[2]
+    wt = w.view(3, 3, co, ci)
+    if flipped:
+        wt = wt.flip(0, 1)
+    wt = wt.permute(2, 3, 0, 1).contiguous()
+    out = []
+    for s, e in _chunks(x.shape[0], chunk):
+        xp = torch.nn.functional.pad(x[s:e].permute(0, 3, 1, 2), (1, 1, 1, 1), mode="reflect" if pad_mode == PAD_REFLECT else "constant")
+        out.append(torch.nn.functional.conv2d(xp, wt, stride=stride).permute(0, 2, 3, 1))
+    return torch.cat(out).contiguous()
+
+
+def convT3x3_f64(x, w, chunk=16):
+    """float64 ConvTranspose2d(k 3, stride 2, padding 1, output_padding 1): slice ky*3+kx of w [9, Cout, Cin] is the layer's
+    weight[ci][co][ky][kx].  x NHWC [B, H, W, Cin] -> [B, 2 H, 2 W, Cout].  Equals conv_classes_ref with convT_classes(3, 1)."""
+    x, w = x.double(), w.double()
+    wt = w.view(3, 3, w.shape[1], w.shape[2]).permute(3, 2, 0, 1).contiguous()
+    out = [torch.nn.functional.conv_transpose2d(x[s:e].permute(0, 3, 1, 2), wt, stride=2, padding=1, output_padding=1).permute(0, 2, 3, 1)
+           for s, e in _chunks(x.shape[0], chunk)]
+    return torch.cat(out).contiguous()
+
+
+def pair_f64(conv, x, w, parts=None, **kw):
+    """The split-pair contraction x_hi.w_hi + x_hi.w_lo + x_lo.w_hi through one of the float64 wrappers above (two passes:
+    x_hi with w_hi + w_lo, x_lo with w_hi -- every term exact in float64).  Equals conv_pair_ref.  parts: (x_hi, x_lo) where the
+    caller has them already."""
+    xh, xl = parts if parts is not None else pair_split(x)
+    wh, wl = pair_split(w)
+    return conv(xh, wh + wl, **kw) + conv(xl, wh, **kw)
+
+
+# kernel -> (min band, slots per CU, strips per (sample, 16-column strip)): read from the launchers (csrc/conv_strip*.h)
+STRIP_PLAN = {"strip32": (32, 12, 1), "strip32p": (32, 8, 1), "stript": (16, 2, 1), "striptp": (16, 1, 1),
+              "strips2": (8, 2, 1), "strips2p": (8, 1, 1), "strips2w": (8, 1, 2)}
+
+
+def strip_plan(kernel, cu, b, rows, cols):
+    """plan_edges of the band plan `kernel`'s launcher makes on a chip of `cu` compute units for b samples of rows x cols (the
+    grid the kernel walks: the output's, for the transposed kernels the input's)."""
+    min_band, per_cu, mult = STRIP_PLAN[kernel]
+    band, _ = band_plan(rows, min_band, per_cu * cu, mult * b * ((cols + 15) // 16))
+    return plan_edges(rows, cols, band)

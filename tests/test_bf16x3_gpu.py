@@ -202,7 +202,8 @@ def test_sliding_window_conv32_split_pair(shape):
     and out, both weight halves in registers, input-stationary row loop, counted vmcnt ring).  The same launch restricted to one
     sample runs the halo-resident kernel: the batched launch must agree with the per-sample launches to fp32 rounding (other
     summation order) -- reflect and zero padding, forward and flipped tap order, bias + LeakyReLU / ReLU epilogues, ragged
-    strips and bands, InstanceNorm moments -- and with stock fp32 torch to the mode's 1e-5."""
+    strips and bands, InstanceNorm moments -- and with stock fp32 torch to the mode's 1e-5.
+    Bit-exact per-sample, per-band and per-slab checks of this kernel against a float64 reference: tests/test_strip_exact_gpu.py."""
     import torch.nn.functional as F
     from cta_gan_amd import ops
     dev = torch.device("cuda:0")
@@ -250,7 +251,8 @@ def test_sliding_window_transposed_conv_split_pair_equals_the_class_kernels(shap
     merged parity classes on `conv_halo_kernel<PK, MC>`.  Per class both accumulate (32-channel slice, tap, [hi.w_hi, hi.w_lo,
     lo.w_hi]) in the same order with the same MFMA operand roles and split the fp32 result the same way: the batched launch must
     equal the per-sample launches BIT FOR BIT in both planes, ragged strips and bands included; the InstanceNorm moments (another
-    partial layout) agree after finalisation; and the result matches F.conv_transpose2d in fp32 to the mode's 1e-5."""
+    partial layout) agree after finalisation; and the result matches F.conv_transpose2d in fp32 to the mode's 1e-5.
+    Bit-exact per-sample, per-band and per-slab checks of this kernel against a float64 reference: tests/test_strip_exact_gpu.py."""
     import torch.nn.functional as F
     from cta_gan_amd import ops
     from cta_gan_amd.engine import _convT_classes
@@ -295,7 +297,8 @@ def test_sliding_window_stride2_conv_split_pair_equals_the_polyphase_kernel(shap
     `conv_halo_kernel<PK, S2D>`.  Both accumulate (phase, 32-channel slice, tap, [hi.w_hi, hi.w_lo, lo.w_hi]) in the same order with
     the same MFMA operand roles and split the fp32 result the same way: the batched launch must equal the per-sample launches BIT
     FOR BIT in both planes; the InstanceNorm moments (another partial layout) agree after finalisation; and the result matches
-    F.conv2d in fp32 to the mode's 1e-5."""
+    F.conv2d in fp32 to the mode's 1e-5.
+    Bit-exact per-sample, per-band and per-slab checks of this kernel against a float64 reference: tests/test_strip_exact_gpu.py."""
     import torch.nn.functional as F
     from cta_gan_amd import ops
     from cta_gan_amd.ops import pack_tap

@@ -39,6 +39,8 @@ twin launch without bias / activation returns, and the partial count Z (and the 
                                                                                                                     runs of 8 x 16 tiles
   wgrad stride 2            is 2, zero padding                                    s2m (64-multiples) / 4 launches   not observable (see below)
   wgrad split pair          dtype 2                                               three sweeps / phase_split        status 0 / 3, Z = B sps / 3 B sps
+  strip kernels             B Hs Ws >= 2^20 / 2^18 / 2^17 (csrc/conv_strip*.h)    not reached (every grid here is     covered by tests/test_strip_exact_gpu.py
+                                                                                  smaller): "no strip kernel" above
 
 What Z does NOT show: Z = B sps with status 0 is what the per-tap kernel, the halo-resident kernel, the merged stride-2 kernel
 (s2m) and its four-launch form all answer, so for the weight-gradient cases without a per-slab comparison it only shows that

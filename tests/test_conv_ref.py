@@ -6,10 +6,11 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from conv_ref import (ACT_LRELU, ACT_NONE, ACT_RELU, PAD_REFLECT, PAD_ZERO, PAIR_GRANULE, act_f32, assert_exact_domain,
-                      conv_classes_ref, conv_pair_ref, conv_taps_ref, convT_classes, epilogue, fold_frame, frame_mask,
-                      fused_store_bf16, int_grid, linear_slabs, pack_tap, pad_index, pair_grid, pair_split, place, store_bf16,
-                      store_pair, tile_slabs, unpack_tap, wgrad_pair_ref, wgrad_taps_ref)
+from conv_ref import (ACT_LRELU, ACT_NONE, ACT_RELU, PAD_REFLECT, PAD_ZERO, PAIR_GRANULE, STRIP_PLAN, act_f32,
+                      assert_exact_domain, band_plan, band_slabs, conv3x3_f64, conv_classes_ref, conv_pair_ref, conv_taps_ref,
+                      convT3x3_f64, convT_classes, epilogue, fold_frame, frame_mask, fused_store_bf16, int_grid, linear_slabs,
+                      moments_ref, pack_tap, pad_index, pair_f64, pair_grid, pair_split, place, plan_edges, slab_moments_ref,
+                      store_bf16, store_pair, strip_plan, tile_slabs, unpack_tap, wgrad_pair_ref, wgrad_taps_ref)
 
 
 def _nchw(t):
@@ -221,3 +222,120 @@ def test_epilogue_in_float32():
     out = fused_store_bf16(np.full((1, 4, 4, 1), 257.0, dtype=np.float32), res=torch.ones(1, 4, 4, 1, dtype=torch.float64))
     assert float(out[0, 0, 0, 0]) == 256.0
     assert float(store_bf16(np.float32([258.0]))[0]) == 258.0
+
+
+# ---------------------------------------------------------------------------- helpers of tests/test_strip_exact_gpu.py
+# The shapes of tests/test_strip_exact_gpu.py with their plans on 256 compute units, worked out by hand:
+# (kernel, B, rows, cols) -> (band_rows, nbands, rows of the last band, nstrips, columns of the last strip)
+STRIP_CASES_CU256 = {
+    ("strip32", 1024, 32, 32): (32, 1, 32, 2, 16),       # 3072 slots / 2048 strips = 1 band
+    ("strip32", 64, 65, 255): (32, 3, 1, 16, 15),        # 3072 / 1024 = 3 bands of ceil(65 / 3) = 22 -> 32 rows
+    ("strip32", 64, 70, 255): (32, 3, 6, 16, 15),
+    ("strip32", 61, 67, 257): (34, 2, 33, 17, 1),        # 3072 / 1037 = 2 bands of 34
+    ("strip32", 8, 3972, 33): (32, 125, 4, 3, 1),        # 3072 / 24 = 128 bands of ceil(3972 / 128) = 32 rows
+    ("strip32p", 1024, 32, 32): (32, 1, 32, 2, 16),
+    ("strip32p", 64, 65, 255): (33, 2, 32, 16, 15),      # 2048 / 1024 = 2 bands of 33
+    ("strip32p", 61, 67, 257): (67, 1, 67, 17, 1),       # 2048 / 1037 = 1 band
+    ("stript", 1024, 16, 16): (16, 1, 16, 1, 16),
+    ("stript", 908, 17, 17): (17, 1, 17, 2, 1),
+    ("stript", 8, 133, 250): (34, 4, 31, 16, 10),        # 512 / 128 = 4 bands of 34
+    ("striptp", 1024, 16, 16): (16, 1, 16, 1, 16),
+    ("striptp", 908, 17, 17): (17, 1, 17, 2, 1),
+    ("striptp", 8, 133, 250): (67, 2, 66, 16, 10),       # 256 / 128 = 2 bands of 67
+    ("strips2", 2048, 8, 16): (8, 1, 8, 1, 16),
+    ("strips2", 1821, 9, 16): (9, 1, 9, 1, 16),
+    ("strips2", 8, 131, 256): (33, 4, 32, 16, 16),       # 512 / 128 = 4 bands of 33
+    ("strips2p", 2048, 8, 16): (8, 1, 8, 1, 16),
+    ("strips2p", 8, 131, 256): (66, 2, 65, 16, 16),      # 256 / 128 = 2 bands of 66
+    ("strips2w", 1024, 8, 16): (8, 1, 8, 1, 16),
+    ("strips2w", 911, 9, 16): (9, 1, 9, 1, 16),
+    ("strips2w", 8, 129, 128): (65, 2, 64, 8, 16),       # 256 / (2 x 64) = 2 bands of 65
+}
+
+
+def test_band_plan_mirror_reproduces_the_hand_computed_plans():
+    """band_plan / strip_plan against the plans worked out by hand for 256 compute units (the table the GPU cases were chosen
+    from), and against a literal transcription of csrc/conv_dispatch.h on a sweep."""
+    assert set(k for k, _, _, _ in STRIP_CASES_CU256) == set(STRIP_PLAN)
+    for (kernel, b, rows, cols), want in STRIP_CASES_CU256.items():
+        assert strip_plan(kernel, 256, b, rows, cols) == want, (kernel, b, rows, cols)
+    # the GPU module's own case lists are these shapes, and on 256 compute units each meets the edge it is named for
+    import test_strip_exact_gpu as gpu
+    cases = [("strip32", c["b"], c["h"], c["w"], c["edge"]) for c in gpu.STRIP32.values()]
+    cases += [("strip32p", c["b"], c["h"], c["w"], c["edge"]) for c in gpu.STRIP32P.values()]
+    cases += [(c["kernel"], c["b"], c["rows"], c["cols"], c["edge"]) for d in (gpu.STRIDED, gpu.STRIDED_PAIR) for c in d.values()]
+    assert set(c[:4] for c in cases) == set(STRIP_CASES_CU256)
+    for kernel, b, rows, cols, edge in cases:
+        assert edge(gpu.Plan(*STRIP_CASES_CU256[(kernel, b, rows, cols)]), b), (kernel, b, rows, cols)
+
+    def c_plan(rows, min_band, slots, strips):
+        nb = slots // strips
+        if nb < 1:
+            nb = 1
+        band = (rows + nb - 1) // nb
+        if band < min_band:
+            band = min_band
+        return band, (rows + band - 1) // band
+    for rows in (8, 9, 31, 32, 33, 65, 133, 512, 3972):
+        for min_band in (8, 16, 32):
+            for slots in (104, 256, 512, 3072):
+                for strips in (1, 24, 128, 1037, 4096):
+                    band, nbands = band_plan(rows, min_band, slots, strips)
+                    assert (band, nbands) == c_plan(rows, min_band, slots, strips)
+                    assert band >= min_band and (nbands - 1) * band < rows <= nbands * band
+    assert band_plan(512, 32, 3072, 512) == (86, 6) and band_plan(65, 32, 3072, 1024) == (32, 3)
+    assert plan_edges(65, 255, 32) == (32, 3, 1, 16, 15) and plan_edges(64, 256, 32) == (32, 2, 32, 16, 16)
+
+
+@pytest.mark.parametrize("grid", [(65, 255, 32, 1), (67, 257, 34, 1), (32, 32, 32, 1), (17, 17, 17, 2), (133, 250, 34, 2), (9, 16, 9, 1)],
+                         ids=["65x255", "67x257", "32x32", "T17x17", "T133x250", "9x16"])
+def test_band_slabs_partition_the_grid(grid):
+    rows, cols, band, os_ = grid
+    ids, cnt = band_slabs(rows, cols, band, os_)
+    _, nbands, last_rows, nstrips, last_cols = plan_edges(rows, cols, band)
+    assert tuple(ids.shape) == (rows * os_, cols * os_) and cnt == nbands * nstrips
+    size = torch.bincount(ids.reshape(-1), minlength=cnt)
+    assert int(size.sum()) == rows * cols * os_ * os_ and int(size.min()) > 0 and int(ids.min()) == 0 and int(ids.max()) == cnt - 1
+    for band_i in range(nbands):
+        for strip in range(nstrips):
+            r = last_rows if band_i == nbands - 1 else band
+            c = last_cols if strip == nstrips - 1 else 16
+            assert int(size[band_i * nstrips + strip]) == r * c * os_ * os_
+            # a slab is ONE rectangle: rows of band band_i, columns of strip `strip` (x os: the four classes of its grid pixels)
+            blk = ids[band_i * band * os_:(band_i * band + r) * os_, strip * 16 * os_:(strip * 16 + c) * os_]
+            assert bool((blk == band_i * nstrips + strip).all())
+    # per-slab moments sum to the whole-sample moments, and a slab's moments are those of its pixels alone
+    rng = np.random.default_rng(rows)
+    acc = int_grid(rng, (2, rows * os_, cols * os_, 3), -50, 50)
+    sm = slab_moments_ref(acc, (ids, cnt))
+    assert torch.equal(sm.sum(1), moments_ref(acc))
+    only = torch.where((ids == cnt - 1)[None, :, :, None], acc, torch.zeros_like(acc))
+    assert torch.equal(sm[:, cnt - 1], moments_ref(only))
+
+
+@pytest.mark.parametrize("flipped", [False, True], ids=["forward", "flipped"])
+@pytest.mark.parametrize("pad_mode", [PAD_ZERO, PAD_REFLECT], ids=["zero", "reflect"])
+def test_conv3x3_f64_equals_conv_taps_ref(flipped, pad_mode):
+    rng = np.random.default_rng(31)
+    x = int_grid(rng, (3, 7, 18, 8), -4, 4)
+    w = int_grid(rng, (9, 6, 8), -4, 4)
+    taps = [pack_tap(1 - ky, 1 - kx, ky * 3 + kx) if flipped else pack_tap(ky - 1, kx - 1, ky * 3 + kx)
+            for ky in range(3) for kx in range(3)]
+    assert torch.equal(conv3x3_f64(x, w, flipped, pad_mode, chunk=2), conv_taps_ref(x, w, taps, 7, 18, 1, pad_mode))
+
+
+def test_strided_transposed_and_pair_f64_wrappers_equal_the_tap_references():
+    rng = np.random.default_rng(32)
+    x = int_grid(rng, (3, 10, 12, 8), -3, 3)
+    w = int_grid(rng, (9, 6, 8), -3, 3)
+    assert torch.equal(conv3x3_f64(x, w, stride=2, chunk=2), conv_taps_ref(x, w, _fwd_taps(3, 1), 5, 6, 2, PAD_ZERO))
+    xt = int_grid(rng, (3, 5, 7, 8), -3, 3)
+    assert torch.equal(convT3x3_f64(xt, w, chunk=2), conv_classes_ref(xt, w, convT_classes(3, 1), 5, 7, PAD_ZERO))
+    xp, wp, xtp = pair_grid(rng, (2, 10, 12, 32)), pair_grid(rng, (9, 8, 32)), pair_grid(rng, (2, 5, 7, 32))
+    flip = [pack_tap(1 - ky, 1 - kx, ky * 3 + kx) for ky in range(3) for kx in range(3)]
+    assert torch.equal(pair_f64(conv3x3_f64, xp, wp, flipped=True, pad_mode=PAD_REFLECT), conv_pair_ref(xp, wp, flip, 10, 12, 1, PAD_REFLECT))
+    assert torch.equal(pair_f64(conv3x3_f64, xp, wp, stride=2), conv_pair_ref(xp, wp, _fwd_taps(3, 1), 5, 6, 2, PAD_ZERO))
+    want = torch.zeros(2, 10, 14, 8, dtype=torch.float64)
+    for py, px, taps in convT_classes(3, 1):
+        place(want, conv_pair_ref(xtp, wp, taps, 5, 7, 1, PAD_ZERO), 2, py, px)
+    assert torch.equal(pair_f64(convT3x3_f64, xtp, wp), want)

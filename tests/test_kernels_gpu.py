@@ -658,7 +658,8 @@ def test_sliding_window_conv32_equals_the_halo_kernel(shape, dev):
     launches with >= 2^20 output pixels; the same launch restricted to one sample runs `conv_halo_kernel`.  Both accumulate the
     taps in list order with the same MFMA operand roles, so the batched launch must equal the per-sample launches BIT FOR BIT:
     reflect and zero padding, forward and flipped (backward-data) tap order, bias + LeakyReLU / ReLU epilogues, ragged strips
-    and bands; the InstanceNorm moments (other partial layout) agree after finalisation."""
+    and bands; the InstanceNorm moments (other partial layout) agree after finalisation.
+    Bit-exact per-sample, per-band and per-slab checks of this kernel against a float64 reference: tests/test_strip_exact_gpu.py."""
     from cta_gan_amd import ops
     b, h, w = shape
     assert b * h * w >= (1 << 20) and h * w < (1 << 20)
@@ -702,7 +703,8 @@ def test_sliding_window_transposed_conv_equals_the_class_kernels(shape, dev):
     `ctg_conv_igemm_classes` launches with >= 2^18 input pixels; the same launch restricted to one sample runs the merged parity
     classes on `conv_halo_kernel`.  Per class both accumulate (64-channel half, tap, k-step) in the same order with the same MFMA
     operand roles: the batched launch must equal the per-sample launches BIT FOR BIT, ragged strips and bands included; the
-    InstanceNorm moments (another partial layout) agree after finalisation; and the result matches F.conv_transpose2d."""
+    InstanceNorm moments (another partial layout) agree after finalisation; and the result matches F.conv_transpose2d.
+    Bit-exact per-sample, per-band and per-slab checks of this kernel against a float64 reference: tests/test_strip_exact_gpu.py."""
     from cta_gan_amd import ops
     from cta_gan_amd.engine import _convT_classes
     b, h, w = shape
@@ -740,7 +742,8 @@ def test_sliding_window_stride2_conv_equals_the_gather_kernel(shape, dev):
     wave's share of the weights in registers, whole-pixel stores through a staging tile) serves `ctg_conv_igemm` launches with
     >= 2^18 output pixels; the same launch restricted to one sample runs conv_igemm_kernel.  Both accumulate (tap, k-step) in the
     same order with the same MFMA operand roles: the batched launch must equal the per-sample launches BIT FOR BIT; the
-    InstanceNorm moments (another partial layout) agree after finalisation; and the result matches F.conv2d."""
+    InstanceNorm moments (another partial layout) agree after finalisation; and the result matches F.conv2d.
+    Bit-exact per-sample, per-band and per-slab checks of this kernel against a float64 reference: tests/test_strip_exact_gpu.py."""
     from cta_gan_amd import ops
     from cta_gan_amd.ops import pack_tap
     b, ho, wo = shape
@@ -774,7 +777,8 @@ def test_sliding_window_stride2_conv_equals_the_gather_kernel(shape, dev):
 def test_sliding_window_stride2_kernels_take_channel_slices(dev):
     """Both stride-2 sliding-window kernels address their operands through x_ld / y_ld: an input that is a channel slice of a wider
     buffer and an output that lands in a slice of a concat buffer give the same bits as dense tensors, and the bytes around the
-    output slice stay untouched."""
+    output slice stay untouched.
+    Bit-exact per-sample, per-band and per-slab checks of these kernels against a float64 reference: tests/test_strip_exact_gpu.py."""
     from cta_gan_amd import ops
     from cta_gan_amd.engine import _convT_classes
     from cta_gan_amd.ops import pack_tap
@@ -808,7 +812,8 @@ def test_sliding_window_wide_stride2_conv_equals_the_gather_kernel(shape, dev):
     """`conv_strips2_128_256_kernel` (the 128 -> 256 channel stride-2 3x3 conv: eight waves, half of the output channels per
     workgroup, each wave's 36 weight fragments in registers) serves `ctg_conv_igemm` launches with >= 2^17 output pixels; the same
     launch restricted to one sample runs conv_igemm_kernel.  Same (tap, k-step) order: BIT-identical outputs; moments agree after
-    finalisation; and the result matches F.conv2d."""
+    finalisation; and the result matches F.conv2d.
+    Bit-exact per-sample, per-band and per-slab checks of this kernel against a float64 reference: tests/test_strip_exact_gpu.py."""
     from cta_gan_amd import ops
     from cta_gan_amd.ops import pack_tap
     b, ho, wo = shape

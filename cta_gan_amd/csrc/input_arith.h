@@ -23,9 +23,14 @@ __device__ __forceinline__ float hu_windowed(short hu, double wmin, double dfac)
     return (float)((t - 0.5) / 0.5);
 }
 
-// image2: full 12-bit range -> [-1, 1]
+// image2: full 12-bit range -> [-1, 1].  `data = data1 + 1024` (datasets.py:38) runs on the int16 array SimpleITK hands back and
+// stays int16 in numpy: above 31743 it wraps to a negative value, which the clamp below then sends to 0 like air.  Reproduced (the
+// conversion of an out-of-range int to short is modular here): the whole int16 domain equals the reference bit for bit
+// (tests/test_metrics_exact_gpu.py).  This changes every caller above HU 31743: ctg_hu_to_inputs, series_inputs_kernel
+// (csrc/export.hip: the inference path's generator input) and SrcHu (csrc/augment.hip: the training loaders' augmentation).  No
+// CT stores such values; csrc/subtract.hip's `a = max(ct + 1024, 0)` is int32, does not wrap and differs from this there.
 __device__ __forceinline__ float hu_fullrange(short hu) {
-    double f = (double)hu + 1024.0;
+    double f = (double)(short)((int)hu + 1024);
     f = f < 0.0 ? 0.0 : f;
     f = f / 4095.0;
     return (float)((f - 0.5) / 0.5);

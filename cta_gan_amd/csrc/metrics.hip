@@ -5,7 +5,11 @@
 // The reference pulls every slice to the host and runs numpy; here one launch windows, masks and reduces a batch of
 // slices, a second turns the sums into the six numbers per slice.  All elementwise arithmetic follows the
 // reference's float32 operation order with explicitly rounded operations (no FMA contraction), so the masks --
-// which hang on exact comparisons (== 0, >= 0.3) -- are identical; the reductions accumulate in fp64.
+// which hang on exact comparisons (== 0, >= 0.3) -- are identical.  The reductions are double throughout: every term of
+// the MAE / PSNR / UQI sums is formed in double from the fp32 images (differences and products of two floats are exact
+// there) and accumulated in double per thread, per wave and per block, and the final kernel's closed forms are double.
+// (fp32 per-thread and per-wave sums, as this kernel first had them, cost UQI's s_xx - N m^2 every digit on a nearly
+// constant slice: tests/test_metrics_exact_gpu.py.)  SSIM is double from the 49-pixel window sums on.
 #include "common.h"
 #include "input_arith.h"
 #include "window_arith.h"
@@ -22,18 +26,19 @@ __global__ __launch_bounds__(256) void to_windowdata_kernel(const float* __restr
 }
 
 struct PairAcc {
-    float v[10];
+    double v[10];
     __device__ __forceinline__ void clear() {
 #pragma unroll
-        for (int i = 0; i < 10; ++i) v[i] = 0.f;
+        for (int i = 0; i < 10; ++i) v[i] = 0.0;
     }
     // x = generated, y = reference ("real"); background of y is exactly -1
-    __device__ __forceinline__ void add(float x, float y) {
-        const float d = x - y, ad = fabsf(d), d2 = d * d;
-        const bool m = y != -1.0f;
-        v[0] += m ? 1.f : 0.f;
-        v[1] += m ? ad : 0.f;
-        v[2] += m ? d2 : 0.f;
+    __device__ __forceinline__ void add(float xf, float yf) {
+        const double x = (double)xf, y = (double)yf;
+        const double d = x - y, ad = fabs(d), d2 = d * d;
+        const bool m = yf != -1.0f;
+        v[0] += m ? 1.0 : 0.0;
+        v[1] += m ? ad : 0.0;
+        v[2] += m ? d2 : 0.0;
         v[3] += ad;
         v[4] += d2;
         v[5] += x;
@@ -44,12 +49,18 @@ struct PairAcc {
     }
 };
 
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
 __global__ __launch_bounds__(256) void window_metrics_partial_kernel(const float* __restrict__ fake,
                                                                      const float* __restrict__ real,
                                                                      const float* __restrict__ wc,
                                                                      const float* __restrict__ ww, long HW,
                                                                      double* __restrict__ part, int aliased) {
-    __shared__ float red[4][MET_NSUM];
+    __shared__ double red[4][MET_NSUM];
     const int n = blockIdx.y;
     const WinParams p = win_params(wc[n], ww[n]);
     PairAcc aw, ar;   // windowed pair (c, b) and raw pair (fake*cc, real*bb)
@@ -64,14 +75,13 @@ __global__ __launch_bounds__(256) void window_metrics_partial_kernel(const float
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int k = 0; k < 10; ++k) {
-        const float a = wave_sum(aw.v[k]), b = wave_sum(ar.v[k]);
+        const double a = wave_sum_f64(aw.v[k]), b = wave_sum_f64(ar.v[k]);
         if (lane == 0) { red[wave][k] = a; red[wave][10 + k] = b; }
     }
     __syncthreads();
     if (threadIdx.x < MET_NSUM) {
         const int k = threadIdx.x;
-        part[((size_t)n * gridDim.x + blockIdx.x) * MET_NSUM + k] =
-            (double)red[0][k] + (double)red[1][k] + (double)red[2][k] + (double)red[3][k];
+        part[((size_t)n * gridDim.x + blockIdx.x) * MET_NSUM + k] = red[0][k] + red[1][k] + red[2][k] + red[3][k];
     }
 }
 
@@ -103,7 +113,7 @@ __global__ void window_metrics_final_kernel(const double* __restrict__ part, int
 extern "C" int ctg_to_windowdata(const float* img, const float* wc, const float* ww, float* out, int B, long HW,
                                  void* stream) {
     CTG_ENTER();
-    if (img == nullptr || wc == nullptr || ww == nullptr || out == nullptr || B < 1 || HW < 1) return CTG_EINVAL;
+    if (img == nullptr || wc == nullptr || ww == nullptr || out == nullptr || B < 1 || B > 65535 || HW < 1) return CTG_EINVAL;
     const int blocks = (int)((HW + 255) / 256 < 1024 ? (HW + 255) / 256 : 1024);
     hipLaunchKernelGGL(to_windowdata_kernel, dim3(blocks, B), dim3(256), 0, (hipStream_t)stream, img, wc, ww, out, HW);
     return ctg_launch_status();
@@ -114,7 +124,7 @@ extern "C" int ctg_window_metrics(const float* fake, const float* real, const fl
     CTG_ENTER();
     if (fake == nullptr || real == nullptr || wc == nullptr || ww == nullptr || part == nullptr || out == nullptr)
         return CTG_EINVAL;
-    if (B < 1 || HW < 2 || nblk < 1 || nblk > 4096) return CTG_EINVAL;
+    if (B < 1 || B > 65535 || HW < 2 || nblk < 1 || nblk > 4096) return CTG_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(window_metrics_partial_kernel, dim3(nblk, B), dim3(256), 0, st, fake, real, wc, ww, HW, part,
                        aliased);

@@ -60,23 +60,27 @@ __device__ __forceinline__ float window_one(float v, const WinParams p) { return
 // mode 1, ctg_window_pairs): the same bits.
 struct MaskedPixel { float c, b, fm, rm; };
 
+// numpy's pair of masked assignments `m[m < 0.3] = 0; m[m >= 0.3] = 1`: a NaN meets neither comparison and stays NaN, so a NaN
+// sample makes its pixel NaN in every image its mask multiplies (HdTrainer.py:1010-1011, 1016-1017)
+__device__ __forceinline__ float threshold_mask(float v) { return v >= 0.3f ? 1.f : (v < 0.3f ? 0.f : v); }
+
 __device__ __forceinline__ MaskedPixel masked_pixel(float f, float r, const WinParams p, int aliased) {
     MaskedPixel o;
     // b = W(real); bb = b >= 0.3; b = b*bb; b[b == 0] = -1
     float b = window_one(r, p);
-    const float bb = b >= 0.3f ? 1.f : 0.f;
+    const float bb = threshold_mask(b);
     b = __fmul_rn(b, bb);
     if (b == 0.f) b = -1.f;
     // c = W(fake)*bb; cc = c >= 0.3; c = c*cc; c[c == 0] = -1
     float c = __fmul_rn(window_one(f, p), bb);
-    const float cc = c >= 0.3f ? 1.f : 0.f;
+    const float cc = threshold_mask(c);
     c = __fmul_rn(c, cc);
     if (c == 0.f) c = -1.f;
     if (aliased) {
         // trainer/CycTrainer.py:288-298 writes `bb = b` / `cc = c` WITHOUT a copy, so thresholding the masks also
-        // thresholds b and c: its windowed pair is the two binary masks mapped to +-1
-        b = bb != 0.f ? 1.f : -1.f;
-        c = cc != 0.f ? 1.f : -1.f;
+        // thresholds b and c: its windowed pair is the two binary masks mapped to +-1 (mask * mask: a NaN mask stays NaN)
+        b = bb == 0.f ? -1.f : __fmul_rn(bb, bb);
+        c = cc == 0.f ? -1.f : __fmul_rn(cc, cc);
     }
     o.c = c;
     o.b = b;

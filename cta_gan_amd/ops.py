@@ -1433,6 +1433,11 @@ def to_windowdata(img, wc, ww):
     return out
 
 
+def window_metrics_nblk(hw):
+    """Workgroups per slice of ctg_window_metrics for slices of hw pixels: one per 4096 pixels, at most 64."""
+    return int(max(1, min(64, hw // 4096)))
+
+
 def window_metrics(fake, real, wc, ww, aliased=False):
     """Windowed and raw MAE / PSNR / UQI of B slices (HdTrainer.py:1008-1050, 1089-1125): fake, real (B, ..., H, W)
     fp32 on the GPU -> float64 tensor [B, 2, 3] = {windowed, raw} x {MAE, PSNR, UQI} (on the GPU, no sync).
@@ -1444,7 +1449,7 @@ def window_metrics(fake, real, wc, ww, aliased=False):
     assert f.shape == r.shape
     b = f.shape[0]
     hw = f.numel() // b
-    nblk = int(max(1, min(64, hw // 4096)))
+    nblk = window_metrics_nblk(hw)
     part = torch.empty((b, nblk, 20), dtype=torch.float64, device=f.device)
     out = torch.empty((b, 2, 3), dtype=torch.float64, device=f.device)
     wcv, wwv = _win_vec(wc, b, f.device), _win_vec(ww, b, f.device)

@@ -328,7 +328,10 @@ int ctg_avgpool_bwd(const float* gout, int B, int HW, float* dx, void* stream);
  * CycTrainer.py:34-57) over B slices of HW pixels with per-slice window centre / width; and the windowed + raw
  * MAE / PSNR / UQI of HdTrainer.py:1008-1050,1089-1125: out[B][2][3] doubles = {windowed, raw} x {MAE, PSNR, UQI};
  * part = B*nblk*20 doubles of workspace.  aliased = 1 reproduces trainer/CycTrainer.py:288-298, where `bb = b` / `cc = c`
- * are aliases and the windowed pair degenerates to the two +-1 masks. ---- */
+ * are aliases and the windowed pair degenerates to the two +-1 masks.  Both entries: B <= 65535 (B is a grid dimension),
+ * otherwise CTG_EINVAL; ctg_window_metrics: HW >= 2, 1 <= nblk <= 4096.  The sums behind `out` are double from the first
+ * addition (every term formed in double from the fp32 images); a NaN sample makes its slice's numbers NaN, MAE included
+ * (the reference's nanmean MAE is finite: a deliberate difference). ---- */
 int ctg_to_windowdata(const float* img, const float* wc, const float* ww, float* out, int B, long HW, void* stream);
 /* Mean structural similarity of B slice pairs [B][H][W] (ABI 9): what skimage.measure.compare_ssim(x, y) returns with its
  * defaults (7x7 uniform window, sample covariance, K1 0.01, K2 0.03, float64) -- the validation pass of every trainer's train()
@@ -342,7 +345,11 @@ int ctg_window_metrics(const float* fake, const float* real, const float* wc, co
                        int nblk, int aliased, double* part, double* out, void* stream);
 /* input pipeline arithmetic (section 8f rank 2): read_ori_w after the DICOM read (trainer/datasets.py:36-71): raw HU
  * (int16, SimpleITK convention) -> windowed image (centre wc, width ww; the reference hard-codes 50 / 400) and the
- * full-range image, both in [-1, 1]; Resize = F.interpolate(mode="nearest") (trainer/utils.py:13-32) on B planes. */
+ * full-range image, both in [-1, 1]; Resize = F.interpolate(mode="nearest") (trainer/utils.py:13-32) on B planes.
+ * `full` wraps above HU 31743 as the reference does (`data1 + 1024` on the reader's int16 array stays int16 in numpy): such a
+ * value becomes negative and is clamped to -1 like air.  The same arithmetic (csrc/input_arith.h: hu_fullrange) serves
+ * ctg_series_inputs and ctg_hu_affine_inputs; ctg_subtract_slices' `a = max(ct_hu + 1024, 0)` is int32 and does NOT wrap, so
+ * above HU 31743 it is no longer the stored value ctg_series_inputs fed the generator (no CT holds such values). */
 int ctg_hu_to_inputs(const short* hu, float wc, float ww, float* win, float* full, long n, void* stream);
 int ctg_resize_nearest(const float* src, int B, int Hi, int Wi, float* dst, int Ho, int Wo, void* stream);
 /* training augmentation of every loader (ABI 12; trainer/HdTrainer.py:130-142,641-653, CycTrainer.py:91-99, p2pTrainer.py:81-89,

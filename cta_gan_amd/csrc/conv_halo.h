@@ -109,6 +109,56 @@ __device__ __forceinline__ void add_bf16x8(float (&f)[8], const bf16_t* p) {
     }
 }
 
+// The activation of an epilogue is wave-uniform, so it is decided ONCE per staging loop and not per accumulator element:
+// act_switch() calls the loop body with the activation as a compile-time constant (ACT_NONE / ACT_RELU / ACT_LRELU: the
+// body is straight-line, the expressions are those of act_apply) or with CONV_ACT_RT, which keeps act_apply's run-time
+// switch for tanh / sigmoid (and its identity for any other value).  Left to the compiler, the switch inside the unrolled
+// loops became a compare-and-branch ladder around inlined tanh and sigmoid bodies for every one of a lane's 64 accumulators.
+#define CONV_ACT_RT (-1)
+template <int ACT> __device__ __forceinline__ float act_apply_c(float x, int act) {
+    if constexpr (ACT == ACT_NONE) return x;
+    else if constexpr (ACT == ACT_RELU) return x > 0.f ? x : 0.f;
+    else if constexpr (ACT == ACT_LRELU) return x > 0.f ? x : LRELU_SLOPE * x;
+    else return act_apply(x, act);
+}
+template <typename F> __device__ __forceinline__ void act_switch(int act, F&& f) {
+    if (act == ACT_NONE) f(std::integral_constant<int, ACT_NONE>{});
+    else if (act == ACT_RELU) f(std::integral_constant<int, ACT_RELU>{});
+    else if (act == ACT_LRELU) f(std::integral_constant<int, ACT_LRELU>{});
+    else f(std::integral_constant<int, CONV_ACT_RT>{});
+}
+// The mask of an InstanceNorm-backward sum, g * act'(xhat), without a branch: the (wave-uniform) activation only chooses what
+// a pixel with xhat <= 0 contributes -- g itself (none), +0 (ReLU) or LRELU_SLOPE * g (LeakyReLU), the very values of the
+// compare-and-branch ladder this replaces (any other activation value is the identity, as before) -- through a factor and a
+// bit mask that are set up once per workgroup: one multiply, one AND, one compare and one select per element.
+struct GradMask {
+    float slope;
+    unsigned keep;
+    __device__ __forceinline__ explicit GradMask(int bact)
+        : slope(bact == ACT_LRELU ? LRELU_SLOPE : 1.f), keep(bact == ACT_RELU ? 0u : 0xffffffffu) {}
+    __device__ __forceinline__ float apply(float g, float xh) const {
+        return xh > 0.f ? g : __uint_as_float(__float_as_uint(slope * g) & keep);
+    }
+};
+
+// Sum of the squares of a lane's TM pixels for the InstanceNorm moments, with the rounding sequence written out.  Left to
+// fp-contraction, `s2 += v * v` over the unrolled pixels became v0 v0 + v1 v1 with ONE of the two products fused into the add --
+// which one, the compiler chose per instantiation (the other product is rounded first), and an unrelated change further down the
+// kernel flipped the choice: the moments moved by an ulp.  V1_FIRST = round v1 v1, then fma(v0, v0, .): what the compile-time
+// 3x3 instantiations (all but the split-pair FUSE ones) have always computed; the others round v0 v0 first.  Every further pixel
+// is one fma, in order.
+template <int N, bool V1_FIRST> __device__ __forceinline__ float pinned_sumsq(const float (&v)[N]) {
+#pragma clang fp contract(off)
+    if constexpr (N == 1) {
+        return v[0] * v[0];
+    } else {
+        float s = V1_FIRST ? __fmaf_rn(v[0], v[0], v[1] * v[1]) : __fmaf_rn(v[1], v[1], v[0] * v[0]);
+#pragma unroll
+        for (int k = 2; k < N; ++k) s = __fmaf_rn(v[k], v[k], s);
+        return s;
+    }
+}
+
 #define HALO_W 16  // output tile is TH x HALO_W pixels (one MFMA pixel fragment = one 16-pixel tile row)
 
 // ABUF = halo buffers: 2 prefetches the next channel slice's halo behind the tap steps (one workgroup per CU);
@@ -402,7 +452,7 @@ void conv_halo_kernel(const ConvArgs a) {
         float* red = reinterpret_cast<float*>(smem);   // [WM][BN][2]; the ring buffers are free after the last barrier
 #pragma unroll
         for (int nt = 0; nt < TN; ++nt) {   // one 16-channel group at a time: 8 live sums, not 8*TN
-            float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
+            float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4], vq[4][TM];
 #pragma unroll
             for (int mt = 0; mt < TM; ++mt) {
                 const bool valid = (y0 + wm * TM + mt < a.Hs) && (x0 + (lane & 15) < a.Ws);
@@ -410,9 +460,11 @@ void conv_halo_kernel(const ConvArgs a) {
                 for (int r = 0; r < 4; ++r) {
                     const float v = valid ? acc[mt][nt][r] : 0.f;
                     s1[r] += v;
-                    s2[r] += v * v;
+                    vq[r][mt] = v;
                 }
             }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) s2[r] = pinned_sumsq<TM, KWC == 3 && !(FUSE && std::is_same<OutT, bfpair_t>::value)>(vq[r]);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 s1[r] = row16_sum_to_lane15(s1[r]);
@@ -521,6 +573,7 @@ void conv_halo_kernel(const ConvArgs a) {
             }
         __syncthreads();                 // smr is read: the staging tiles below reuse the memory
     }
+    const int epi_act = NIE ? a.nie_act : a.act;     // wave-uniform: decided once per staging loop (act_switch)
     if constexpr (std::is_same<OutT, bfpair_t>::value) {
         // split-pair result: the UNROUNDED fp32 accumulators are staged through LDS in NR rounds (64 channels per round at most)
         // and leave as whole 16-byte chunks of the hi and of the lo plane; residual / frame fold / InstanceNorm-backward sums
@@ -539,6 +592,7 @@ void conv_halo_kernel(const ConvArgs a) {
         const bf16_t* __restrict__ F = (const bf16_t*)a.fold;
         const bf16_t* __restrict__ Z = (const bf16_t*)a.bz;
         const bool bst = FUSE && a.bstats != nullptr;
+        const GradMask bmask(a.bact);
         const int y_lo = a.y_ld >> 1, r_lo = a.res_ld >> 1, f_lo = a.fold_ld >> 1, z_lo = a.bz_ld >> 1;
         // A round stages TN / WN of EVERY wave's channel tiles (not all tiles of the waves with wn == rd): each wave's live
         // accumulators halve with every round, which is what keeps the fused store loop (residual, fold, InstanceNorm input,
@@ -551,7 +605,8 @@ void conv_halo_kernel(const ConvArgs a) {
 #pragma unroll
         for (int rd = 0; rd < NR; ++rd) {
             if (rd) __syncthreads();              // the previous round's readers are done with the staging tile
-            {
+            act_switch(epi_act, [&](auto AC) __attribute__((always_inline)) {
+                constexpr int ACT = decltype(AC)::value;
 #pragma unroll
                 for (int ntl = 0; ntl < TNR; ++ntl) {
                     const int nt = rd * TNR + ntl;
@@ -566,13 +621,13 @@ void conv_halo_kernel(const ConvArgs a) {
                         f32x4 o;
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
-                            if constexpr (NIE) o[r] = act_apply((acc[mt][nt][r] - nmr[nt][r]) * nrr[nt][r], a.nie_act);
-                            else o[r] = act_apply(acc[mt][nt][r] + bv[r], a.act);
+                            if constexpr (NIE) o[r] = act_apply_c<ACT>((acc[mt][nt][r] - nmr[nt][r]) * nrr[nt][r], epi_act);
+                            else o[r] = act_apply_c<ACT>(acc[mt][nt][r] + bv[r], epi_act);
                         }
                         *reinterpret_cast<f32x4*>(st + prow * RS + ((wn * TNR + ntl) * 16 + co_l) * 4) = o;
                     }
                 }
-            }
+            });
             __syncthreads();
             const int chl = chan_of((tid % CPR) * 8, rd);      // the thread's channel chunk inside the N tile, every trip
             float bs1[8], bs2[8], bmu[8], brs[8];
@@ -644,9 +699,7 @@ void conv_halo_kernel(const ConvArgs a) {
 #pragma unroll
                             for (int e = 0; e < 8; ++e) {
                                 const float xh = (zf[e] - bmu[e]) * brs[e];
-                                float gg = (float)hi[e] + (float)lo[e];
-                                if (a.bact == ACT_RELU) gg = xh > 0.f ? gg : 0.f;
-                                else if (a.bact == ACT_LRELU) gg = xh > 0.f ? gg : LRELU_SLOPE * gg;
+                                const float gg = bmask.apply((float)hi[e] + (float)lo[e], xh);
                                 bs1[e] += gg;
                                 bs2[e] += gg * xh;
                             }
@@ -682,43 +735,88 @@ void conv_halo_kernel(const ConvArgs a) {
     } else if constexpr (sizeof(OutT) == 2) {
         constexpr int RS = BN * 2 + 16;
         char* st = smem;
+        act_switch(epi_act, [&](auto AC) __attribute__((always_inline)) {
+            constexpr int ACT = decltype(AC)::value;
 #pragma unroll
-        for (int nt = 0; nt < TN; ++nt) {
-            const int co = (wn * TN + nt) * 16 + co_l;
-            float bv[4];
+            for (int nt = 0; nt < TN; ++nt) {
+                const int co = (wn * TN + nt) * 16 + co_l;
+                float bv[4];
 #pragma unroll
-            for (int r = 0; r < 4; ++r)
-                bv[r] = (a.bias != nullptr && n0 + co + r < a.Cout) ? a.bias[n0 + co + r] : 0.f;
+                for (int r = 0; r < 4; ++r)
+                    bv[r] = (a.bias != nullptr && n0 + co + r < a.Cout) ? a.bias[n0 + co + r] : 0.f;
 #pragma unroll
-            for (int mt = 0; mt < TM; ++mt) {
-                const int prow = (wm * TM + mt) * HALO_W + (lane & 15);
-                bf16x4 o;
+                for (int mt = 0; mt < TM; ++mt) {
+                    const int prow = (wm * TM + mt) * HALO_W + (lane & 15);
+                    bf16x4 o;
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    if constexpr (NIE) o[r] = (bf16_t)act_apply((acc[mt][nt][r] - nmr[nt][r]) * nrr[nt][r], a.nie_act);
-                    else o[r] = (bf16_t)act_apply(acc[mt][nt][r] + bv[r], a.act);
+                    for (int r = 0; r < 4; ++r) {
+                        if constexpr (NIE) o[r] = (bf16_t)act_apply_c<ACT>((acc[mt][nt][r] - nmr[nt][r]) * nrr[nt][r], epi_act);
+                        else o[r] = (bf16_t)act_apply_c<ACT>(acc[mt][nt][r] + bv[r], epi_act);
+                    }
+                    *reinterpret_cast<bf16x4*>(st + prow * RS + co * 2) = o;
                 }
-                *reinterpret_cast<bf16x4*>(st + prow * RS + co * 2) = o;
             }
-        }
+        });
         OutT* __restrict__ Y = (OutT*)a.y;
         const bf16_t* __restrict__ R = (const bf16_t*)a.res;
         const bf16_t* __restrict__ F = (const bf16_t*)a.fold;
         constexpr int CPR = BN / 8;
         constexpr int NIT = BM * CPR / NTH;
+        // Trip `it` of a thread is the pixel (oyb + RPT it, ox), channel chunk ch: the column and the chunk never change and the
+        // row is wave-uniform, so every global address of the store loop is ONE base per thread plus a wave-uniform step per trip
+        // (rebuilt per trip they cost 5 v_mul_lo_u32 and 2 v_mad_u64_u32 for each 16-byte access) and the row tests are scalar.
+        constexpr int RPT = NTH / (CPR * HALO_W);      // tile rows per trip
+        static_assert(NTH % (CPR * HALO_W) == 0 && (CPR * HALO_W) % 64 == 0, "store loop: whole tile rows per trip, one row per wave");
+        const int ch = (tid % CPR) * 8;
+        const int prow0 = tid / CPR;
+        const int oyb = y0 + __builtin_amdgcn_readfirstlane(tid / (CPR * HALO_W)), ox = x0 + prow0 % HALO_W;
+        const bool col_ok = ox < a.Ws && n0 + ch < a.Cout;
+        OutT* const yp0 = Y + (((size_t)n * a.Ho + (oyb * a.os + oy0_)) * a.Wo + (ox * a.os + ox0_)) * a.y_ld + n0 + ch;
+        const size_t y_step = (size_t)RPT * a.os * a.Wo * a.y_ld;
+        const size_t pix0 = ((size_t)n * a.Hs + oyb) * a.Ws + ox;      // FUSE: output grid == tile grid
+        const bf16_t* const zero16 = (const bf16_t*)g_zero_chunk;
         u32x4 rv[FUSE ? NIT : 1], zv[FUSE ? NIT : 1];   // residual / InstanceNorm-input chunks of the thread's pixels
         if constexpr (FUSE) {   // the residual chunks are requested before the staging barrier and land behind it
+            const bf16_t* const rp0 = R + pix0 * a.res_ld + n0 + ch;
+            const bf16_t* const zp0 = (const bf16_t*)a.bz + pix0 * a.bz_ld + n0 + ch;
+            const size_t r_step = (size_t)RPT * a.Ws * a.res_ld, z_step = (size_t)RPT * a.Ws * a.bz_ld;
 #pragma unroll
             for (int it = 0; it < NIT; ++it) {
-                const int cidx = tid + NTH * it;
-                const int prow = cidx / CPR, ch = (cidx % CPR) * 8;
-                const int oy = y0 + prow / HALO_W, ox = x0 + prow % HALO_W;
-                const bool ok = R != nullptr && oy < a.Hs && ox < a.Ws && n0 + ch < a.Cout;
-                rv[it] = *reinterpret_cast<const u32x4*>(
-                    ok ? R + (((size_t)n * a.Hs + oy) * a.Ws + ox) * a.res_ld + n0 + ch : (const bf16_t*)g_zero_chunk);
-                const bool okz = a.bstats != nullptr && oy < a.Hs && ox < a.Ws && n0 + ch < a.Cout;
-                zv[it] = *reinterpret_cast<const u32x4*>(
-                    okz ? (const bf16_t*)a.bz + (((size_t)n * a.Hs + oy) * a.Ws + ox) * a.bz_ld + n0 + ch : (const bf16_t*)g_zero_chunk);
+                const bool in = col_ok && oyb + RPT * it < a.Hs;
+                rv[it] = *reinterpret_cast<const u32x4*>(R != nullptr && in ? rp0 + it * r_step : zero16);
+                zv[it] = *reinterpret_cast<const u32x4*>(a.bstats != nullptr && in ? zp0 + it * z_step : zero16);
+            }
+        }
+        // Frame fold.  Only the workgroups whose tile touches row 1 / Hs - 2 or column 1 / Ws - 2 have anything to fold (fold_tile,
+        // workgroup-uniform).  The frame-COLUMN chunk is the operand a thread needs in every one of its trips (its column never
+        // changes): loaded at its point of use it cost a full memory latency per trip behind an s_waitcnt vmcnt(0) that also drained
+        // the stores of the trips before, in the two waves the workgroup then waits for.  It is requested one trip ahead -- that of
+        // trip 0 here, before the staging barrier; a lane without one reads the zero chunk -- while the ADD stays conditional
+        // (-0 + 0 would store +0).  The frame-row and corner chunks are needed in at most two trips of a wave (wave-uniform
+        // rows 1 and Hs - 2) and stay loads at their point of use: holding them one trip ahead as well spilled registers.
+        bool fold_tile = false;
+        const bf16_t* fn0 = zero16;
+        size_t f_pitch = 0;
+        int ex = -1;
+        u32x4 fcol = {};
+        auto fold_ey = [&](int it) __attribute__((always_inline)) {      // wave-uniform: the frame row trip `it` folds, or -1
+            const int oy = oyb + RPT * it;
+            return oy >= a.Hs ? -1 : (oy == 1 ? 0 : (oy == a.Hs - 2 ? a.Hs + 1 : -1));
+        };
+        auto fold_col_request = [&](int it) __attribute__((always_inline)) {
+            const bool colf = col_ok && ex >= 0 && oyb + RPT * it < a.Hs;
+            fcol = *reinterpret_cast<const u32x4*>(colf ? fn0 + (size_t)(oyb + RPT * it + 1) * f_pitch + (size_t)ex * a.fold_ld : zero16);
+        };
+        if constexpr (FUSE) {
+            if (F != nullptr) {
+                const int yl = min(y0 + TH, a.Hs), xl = min(x0 + HALO_W, a.Ws);       // the tile's valid pixels: [y0, yl) x [x0, xl)
+                fold_tile = (y0 <= 1 && 1 < yl) || (y0 <= a.Hs - 2 && a.Hs - 2 < yl) || (x0 <= 1 && 1 < xl) || (x0 <= a.Ws - 2 && a.Ws - 2 < xl);
+            }
+            if (fold_tile) {
+                fn0 = F + (size_t)n * (a.Hs + 2) * (a.Ws + 2) * a.fold_ld + n0 + ch;
+                f_pitch = (size_t)(a.Ws + 2) * a.fold_ld;
+                ex = ox == 1 ? 0 : (ox == a.Ws - 2 ? a.Ws + 1 : -1);
+                fold_col_request(0);
             }
         }
         const bool bst = FUSE && a.bstats != nullptr;
@@ -726,58 +824,58 @@ void conv_halo_kernel(const ConvArgs a) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) { bs1[e] = 0.f; bs2[e] = 0.f; bmu[e] = 0.f; brs[e] = 0.f; }
         if constexpr (FUSE) {
-            static_assert(NTH % CPR == 0, "a thread keeps its channel chunk over the store loop");
-            const int chl = (tid % CPR) * 8;
-            if (bst && n0 + chl < a.Cout) {
+            if (bst && n0 + ch < a.Cout) {
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
-                    bmu[e] = a.bmean[(size_t)n * a.Cout + n0 + chl + e];
-                    brs[e] = a.brstd[(size_t)n * a.Cout + n0 + chl + e];
+                    bmu[e] = a.bmean[(size_t)n * a.Cout + n0 + ch + e];
+                    brs[e] = a.brstd[(size_t)n * a.Cout + n0 + ch + e];
                 }
             }
         }
         __syncthreads();
+        const GradMask bmask(a.bact);
+        const char* const sp0 = st + prow0 * RS + ch * 2;
 #pragma unroll
         for (int it = 0; it < NIT; ++it) {
-            const int cidx = tid + NTH * it;
-            const int prow = cidx / CPR, ch = (cidx % CPR) * 8;
-            const int oy = y0 + prow / HALO_W, ox = x0 + prow % HALO_W;
-            if (oy < a.Hs && ox < a.Ws && n0 + ch < a.Cout) {
-                OutT* yp = Y + (((size_t)n * a.Ho + (oy * a.os + oy0_)) * a.Wo + (ox * a.os + ox0_)) * a.y_ld + n0 + ch;
-                u32x4 v = *reinterpret_cast<const u32x4*>(st + prow * RS + ch * 2);
+            if (oyb + RPT * it < a.Hs && col_ok) {
                 if constexpr (FUSE) {   // own instantiation: launches without res / fold run the plain store loop
+                    u32x4 v = *reinterpret_cast<const u32x4*>(sp0 + it * (RPT * HALO_W * RS));
                     float f[8], g[8];
                     unpack_bf16x8(v, f);
                     unpack_bf16x8(rv[it], g);
 #pragma unroll
                     for (int e = 0; e < 8; ++e) f[e] += g[e];
-                    if (F != nullptr) {
-                        const int ey = oy == 1 ? 0 : (oy == a.Hs - 2 ? a.Hs + 1 : -1);
-                        const int ex = ox == 1 ? 0 : (ox == a.Ws - 2 ? a.Ws + 1 : -1);
-                        const OutT* Fn = F + (size_t)n * (a.Hs + 2) * (a.Ws + 2) * a.fold_ld + n0 + ch;
-                        if (ey >= 0) add_bf16x8(f, Fn + ((size_t)ey * (a.Ws + 2) + ox + 1) * a.fold_ld);
-                        if (ex >= 0) add_bf16x8(f, Fn + ((size_t)(oy + 1) * (a.Ws + 2) + ex) * a.fold_ld);
-                        if (ey >= 0 && ex >= 0) add_bf16x8(f, Fn + ((size_t)ey * (a.Ws + 2) + ex) * a.fold_ld);
+                    if (fold_tile) {
+                        const int ey = fold_ey(it);
+                        if (ey >= 0) add_bf16x8(f, fn0 + (size_t)ey * f_pitch + (size_t)(ox + 1) * a.fold_ld);
+                        if (ex >= 0) {
+                            unpack_bf16x8(fcol, g);
+#pragma unroll
+                            for (int e = 0; e < 8; ++e) f[e] += g[e];
+                        }
+                        if (ey >= 0 && ex >= 0) add_bf16x8(f, fn0 + (size_t)ey * f_pitch + (size_t)ex * a.fold_ld);
+                        // the next trip's column chunk, behind this trip's adds: it lands while the trip converts, sums and stores
+                        // (a trip that is skipped -- row beyond the grid, column or chunk out of range -- has no successor that is not)
+                        if (it + 1 < NIT) fold_col_request(it + 1);
                     }
                     bf16x8 o;
 #pragma unroll
                     for (int e = 0; e < 8; ++e) o[e] = (bf16_t)f[e];
-                    v = __builtin_bit_cast(u32x4, o);
                     if (bst) {   // InstanceNorm-backward sums of the STORED (rounded) gradient; ch is the same in every trip
                         float zf[8];
                         unpack_bf16x8(zv[it], zf);
 #pragma unroll
                         for (int e = 0; e < 8; ++e) {
                             const float xh = (zf[e] - bmu[e]) * brs[e];
-                            float gg = (float)o[e];
-                            if (a.bact == ACT_RELU) gg = xh > 0.f ? gg : 0.f;
-                            else if (a.bact == ACT_LRELU) gg = xh > 0.f ? gg : LRELU_SLOPE * gg;
+                            const float gg = bmask.apply((float)o[e], xh);
                             bs1[e] += gg;
                             bs2[e] += gg * xh;
                         }
                     }
+                    *reinterpret_cast<u32x4*>(yp0 + it * y_step) = __builtin_bit_cast(u32x4, o);
+                } else {
+                    *reinterpret_cast<u32x4*>(yp0 + it * y_step) = *reinterpret_cast<const u32x4*>(sp0 + it * (RPT * HALO_W * RS));
                 }
-                *reinterpret_cast<u32x4*>(yp) = v;
             }
         }
         if constexpr (FUSE) {
@@ -808,11 +906,18 @@ void conv_halo_kernel(const ConvArgs a) {
     } else {
         OutT* __restrict__ Y = (OutT*)a.y;
         const bool vec_ok = ((a.Cout & 3) == 0) && ((a.y_ld & 3) == 0);
+        // the wave's pixel rows are consecutive: one base address per lane, a wave-uniform step per row
+        OutT* const yp0 = Y + (((size_t)n * a.Ho + ((y0 + wm * TM) * a.os + oy0_)) * a.Wo + ((x0 + (lane & 15)) * a.os + ox0_)) * a.y_ld;
+        const size_t y_step = (size_t)a.os * a.Wo * a.y_ld;
+        // The FUSE instantiations keep the run-time switch (CONV_ACT_RT): with four copies of their residual / fold loop the kernel
+        // argument block ended up in scratch memory (624 bytes per lane); they serve no launch of the bf16 or split-pair step.
+        auto store_rows = [&](auto AC) __attribute__((always_inline)) {
+        constexpr int ACT = decltype(AC)::value;
 #pragma unroll
         for (int mt = 0; mt < TM; ++mt) {
             const int oy = y0 + wm * TM + mt, ox = x0 + (lane & 15);
             if (oy >= a.Hs || ox >= a.Ws) continue;
-            OutT* yp = Y + (((size_t)n * a.Ho + (oy * a.os + oy0_)) * a.Wo + (ox * a.os + ox0_)) * a.y_ld;
+            OutT* yp = yp0 + mt * y_step;
 #pragma unroll
             for (int nt = 0; nt < TN; ++nt) {
                 const int co = n0 + (wn * TN + nt) * 16 + co_l;
@@ -821,7 +926,7 @@ void conv_halo_kernel(const ConvArgs a) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const float b = (a.bias != nullptr && co + r < a.Cout) ? a.bias[co + r] : 0.f;
-                    v[r] = act_apply(acc[mt][nt][r] + b, a.act);
+                    v[r] = act_apply_c<ACT>(acc[mt][nt][r] + b, epi_act);
                 }
                 if (FUSE && a.res != nullptr) {
                     const float* rp = (const float*)a.res + (((size_t)n * a.Hs + oy) * a.Ws + ox) * a.res_ld + co;
@@ -850,6 +955,9 @@ void conv_halo_kernel(const ConvArgs a) {
                 }
             }
         }
+        };
+        if constexpr (FUSE) store_rows(std::integral_constant<int, CONV_ACT_RT>{});
+        else act_switch(epi_act, store_rows);
     }
 }
 

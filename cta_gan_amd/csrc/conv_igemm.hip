@@ -376,22 +376,25 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_igemm_kernel(const ConvArgs
         for (int rd = 0; rd < WN; ++rd) {
             if (rd) __syncthreads();
             if (wn == rd) {
+                act_switch(a.act, [&](auto AC) __attribute__((always_inline)) {      // the activation, decided once (conv_halo.h)
+                    constexpr int ACT = decltype(AC)::value;
 #pragma unroll
-                for (int nt = 0; nt < TN; ++nt) {
-                    const int co = (wn * TN + nt) * 16 + co_l;
-                    float bv[4];
+                    for (int nt = 0; nt < TN; ++nt) {
+                        const int co = (wn * TN + nt) * 16 + co_l;
+                        float bv[4];
 #pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        bv[r] = (a.bias != nullptr && n0 + co + r < a.Cout) ? a.bias[n0 + co + r] : 0.f;
+                        for (int r = 0; r < 4; ++r)
+                            bv[r] = (a.bias != nullptr && n0 + co + r < a.Cout) ? a.bias[n0 + co + r] : 0.f;
 #pragma unroll
-                    for (int mt = 0; mt < TM; ++mt) {
-                        const int prow = (wm * TM + mt) * 16 + (lane & 15);
-                        f32x4 o;
+                        for (int mt = 0; mt < TM; ++mt) {
+                            const int prow = (wm * TM + mt) * 16 + (lane & 15);
+                            f32x4 o;
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) o[r] = act_apply(acc[mt][nt][r] + bv[r], a.act);
-                        *reinterpret_cast<f32x4*>(st + prow * RS + (nt * 16 + co_l) * 4) = o;
+                            for (int r = 0; r < 4; ++r) o[r] = act_apply_c<ACT>(acc[mt][nt][r] + bv[r], a.act);
+                            *reinterpret_cast<f32x4*>(st + prow * RS + (nt * 16 + co_l) * 4) = o;
+                        }
                     }
-                }
+                });
             }
             __syncthreads();
 #pragma unroll
@@ -422,22 +425,25 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_igemm_kernel(const ConvArgs
         // bf16: stage the tile [pixel][co] in LDS (row pitch padded by 16 B), then whole 16-byte chunks leave
         constexpr int RS = BN * 2 + 16;
         char* st = smem;
+        act_switch(a.act, [&](auto AC) __attribute__((always_inline)) {
+            constexpr int ACT = decltype(AC)::value;
 #pragma unroll
-        for (int nt = 0; nt < TN; ++nt) {
-            const int co = (wn * TN + nt) * 16 + co_l;
-            float bv[4];
+            for (int nt = 0; nt < TN; ++nt) {
+                const int co = (wn * TN + nt) * 16 + co_l;
+                float bv[4];
 #pragma unroll
-            for (int r = 0; r < 4; ++r)
-                bv[r] = (a.bias != nullptr && n0 + co + r < a.Cout) ? a.bias[n0 + co + r] : 0.f;
+                for (int r = 0; r < 4; ++r)
+                    bv[r] = (a.bias != nullptr && n0 + co + r < a.Cout) ? a.bias[n0 + co + r] : 0.f;
 #pragma unroll
-            for (int mt = 0; mt < TM; ++mt) {
-                const int prow = (wm * TM + mt) * 16 + (lane & 15);
-                bf16x4 o;
+                for (int mt = 0; mt < TM; ++mt) {
+                    const int prow = (wm * TM + mt) * 16 + (lane & 15);
+                    bf16x4 o;
 #pragma unroll
-                for (int r = 0; r < 4; ++r) o[r] = (bf16_t)act_apply(acc[mt][nt][r] + bv[r], a.act);
-                *reinterpret_cast<bf16x4*>(st + prow * RS + co * 2) = o;
+                    for (int r = 0; r < 4; ++r) o[r] = (bf16_t)act_apply_c<ACT>(acc[mt][nt][r] + bv[r], a.act);
+                    *reinterpret_cast<bf16x4*>(st + prow * RS + co * 2) = o;
+                }
             }
-        }
+        });
         __syncthreads();
         OutT* __restrict__ Y = (OutT*)a.y;
         constexpr int CPR = BN / 8;  // 16-byte chunks per pixel row of the tile
@@ -456,6 +462,8 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_igemm_kernel(const ConvArgs
     } else {
         OutT* __restrict__ Y = (OutT*)a.y;
         const bool vec_ok = ((a.Cout & 3) == 0) && ((a.y_ld & 3) == 0);
+        act_switch(a.act, [&](auto AC) __attribute__((always_inline)) {
+        constexpr int ACT = decltype(AC)::value;
 #pragma unroll
         for (int mt = 0; mt < TM; ++mt) {
             const int m = m0 + (wm * TM + mt) * 16 + (lane & 15);
@@ -471,7 +479,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_igemm_kernel(const ConvArgs
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const float b = (a.bias != nullptr && co + r < a.Cout) ? a.bias[co + r] : 0.f;
-                    v[r] = act_apply(acc[mt][nt][r] + b, a.act);
+                    v[r] = act_apply_c<ACT>(acc[mt][nt][r] + b, a.act);
                 }
                 if (vec_ok) {
                     *reinterpret_cast<f32x4*>(yp + co) = f32x4{v[0], v[1], v[2], v[3]};
@@ -482,6 +490,7 @@ __global__ __launch_bounds__(WM * WN * 64) void conv_igemm_kernel(const ConvArgs
                 }
             }
         }
+        });
     }
 }
 

@@ -84,6 +84,8 @@ SIGNATURES = {
     "ctg_project_finish": "piliiiffippp",
     "ctg_project_rotate": "piiiiipiiiiiffippp",
     "ctg_subtract_slices": "ppiiiiiiiiffppp",
+    "ctg_project_slabs_inplane": "piiiiiiiiiffippp",
+    "ctg_project_accumulate_sliding": "piiiiiiiipp",
     "ctg_window_pairs": "ppppilipp",
     "ctg_maxpool3s2_fwd": "pipiiiiip",
     "ctg_lpips_layer": "pipiliippp",

@@ -22,6 +22,13 @@ generator writes on its input's pixel grid, so the pair is registered by constru
 contrast-enhancement map and bone cancels without a segmentation.  One launch per chunk (`ops.subtract_slices`: 3 x 3 in-plane
 median, a floor and a band on the input HU), from the two chunks that are on the device anyway; `project_source="sub"` hands
 that chunk to the projector and the rotator instead of the synthesized one: the bone-free MIP and rotating MIP.
+
+Sliding thin slabs (`SeriesSlabs`, `slab_volume`, `SeriesTranslator(slabs=...)`): the mode a CTA is read in.  A slab of T voxels
+is projected and moved on by S <= T voxels (`slab_windows`), along the axial, the coronal or the sagittal axis, so a vessel that
+runs obliquely stays connected from one slab to the next.  A coronal or sagittal slab row depends on one slice only, so every
+chunk finishes its own rows of every slab plane in one launch per axis (`ops.project_slabs_inplane`); the axial slabs are int32
+accumulators (`ops.project_accumulate_sliding`) finished by `ops.project_finish`.  S = 1 makes about one plane per voxel of the
+axis: `SeriesSlabs.nbytes` says what that costs before anything runs.
 """
 from __future__ import annotations
 
@@ -59,6 +66,21 @@ def slab_plan(n, thick):
         raise ValueError("slab_plan: n >= 1 and thick >= 1 expected, got n=%d thick=%d" % (n, thick))
     s = (n + thick - 1) // thick
     return s, n - (s - 1) * thick
+
+
+def slab_windows(length, thick, step):
+    """(J, thick_clipped, last_len): the sliding slabs along an axis of `length` voxels, `thick` >= 1 voxels each, moved on by
+    `step` voxels, 1 <= step <= thick (checked against the thick given; thick is clipped to the axis afterwards, as
+    `SeriesProjector` clips its slab).  Slab j covers [j step, min(j step + thick, length)); J = 1 if length <= thick, else
+    ceil((length - thick) / step) + 1.  Only the last slab can be short: last_len <= thick_clipped voxels.  With step == thick
+    this is `slab_plan`."""
+    length, thick, step = int(length), int(thick), int(step)
+    if length < 1 or thick < 1 or not 1 <= step <= thick:
+        raise ValueError("slab_windows: length >= 1 and 1 <= step <= thick expected, got length=%d thick=%d step=%d"
+                         % (length, thick, step))
+    j = ops.slab_count(length, thick, step)
+    thick = min(thick, length)
+    return j, thick, min(thick, length - (j - 1) * step)
 
 
 def aspect_rows(n, aspect):
@@ -143,6 +165,116 @@ def project_volume(volume, mode="max", slab=None, wc=50.0, ww=400.0, hu=False, b
 def _projections_to_host(out, is_np):
     conv = (lambda t: t.cpu().numpy()) if is_np else (lambda t: t.cpu())
     return {a: {k: None if t is None else conv(t) for k, t in d.items()} for a, d in out.items()}
+
+
+def _per_axis(value, axes, what):
+    """`thick` / `step` of SeriesSlabs: one int for every axis, or {axis: int} with an entry for each axis kept."""
+    if isinstance(value, dict):
+        if any(a not in value for a in axes):
+            raise ValueError("SeriesSlabs: %s %r has no entry for every axis of %s" % (what, value, axes))
+        return {a: int(value[a]) for a in axes}
+    return {a: int(value) for a in axes}
+
+
+class SeriesSlabs:
+    """Sliding thin-slab projections (STS-MIP / MinIP / mean) of an int16 volume [n, h, w] that arrives in chunks on the device:
+    slabs of `thick` voxels moved on by `step` voxels (`slab_windows`; step=None: thick, slabs that do not overlap) along "axial"
+    [J_a, h, w] (over slices), "coronal" [J_c, n, w] (over the rows of the slab) and "sagittal" [J_s, n, h] (over its columns).
+    thick / step: an int for every axis or {axis: int} -- slice spacing and pixel spacing differ, so the axes want different
+    counts.  mode "max", "min" or "mean" (the exact sum divided toward zero by the slab's own length); level=False skips the
+    8-bit planes of the window (wc, ww, hu).  `update(pix_chunk, n0)` in any order, every slice once: a chunk finishes its own
+    rows of every coronal and sagittal plane (`ops.project_slabs_inplane`) and is combined into the int32 axial accumulators
+    (`ops.project_accumulate_sliding`); `result()` -> {axis: {"values": int16, "level": uint8 or None}} on the device finishes
+    the axial ones (`ops.project_finish`); `reset()` refills only those.  `nbytes`: the device bytes of the outputs and the axial
+    accumulators, known before the first chunk -- step = 1 makes J about the axis' length, so every axis then costs about a
+    whole volume (and the axial one its int32 accumulators on top).  Exact integer arithmetic on the current stream: equal to
+    numpy bit for bit."""
+
+    def __init__(self, n, h, w, thick, step=None, mode="max", axes=AXES, wc=50.0, ww=400.0, hu=False, level=True, device=None):
+        if mode not in PROJECTIONS:
+            raise ValueError("SeriesSlabs: mode %r is not one of %s" % (mode, PROJECTIONS))
+        axes = tuple(axes)
+        if not axes or any(a not in AXES for a in axes):
+            raise ValueError("SeriesSlabs: axes %r, a non-empty choice of %s expected" % (axes, AXES))
+        self.n, self.h, self.w = int(n), int(h), int(w)
+        if min(self.n, self.h, self.w) < 1:
+            raise ValueError("SeriesSlabs: a volume of at least one voxel expected")
+        self.mode, self.axes = mode, tuple(a for a in AXES if a in axes)
+        self.code = ops.PROJECT_MODES[mode]
+        self.given = _per_axis(thick, self.axes, "thick")      # what the kernels validate `step` against
+        self.step = dict(self.given) if step is None else _per_axis(step, self.axes, "step")
+        extent = {"axial": self.n, "coronal": self.h, "sagittal": self.w}
+        self.slabs, self.thick, self.last_len = {}, {}, {}
+        for a in self.axes:
+            self.slabs[a], self.thick[a], self.last_len[a] = slab_windows(extent[a], self.given[a], self.step[a])
+        self.hu, self.window, self.want_level = bool(hu), (float(wc), float(ww)), bool(level)
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("SeriesSlabs: a GPU device is required (no CPU fallback)")
+        shapes = {"coronal": (self.n, self.w), "sagittal": (self.n, self.h)}
+        self.values = {a: torch.empty((self.slabs[a],) + shapes[a], dtype=torch.int16, device=self.device)
+                       for a in self.axes if a != "axial"}
+        self.level = {a: torch.empty(t.shape, dtype=torch.uint8, device=self.device) if self.want_level else None
+                      for a, t in self.values.items()}
+        self.acc = None
+        if "axial" in self.axes:
+            self.acc = torch.empty((self.slabs["axial"], self.h, self.w), dtype=torch.int32, device=self.device)
+        per_item = 2 + (1 if self.want_level else 0)
+        self.nbytes = sum(t.numel() * per_item for t in self.values.values())
+        if self.acc is not None:
+            self.nbytes += self.acc.numel() * (4 + per_item)
+        self.reset()
+
+    def reset(self):
+        """For the next volume of the same shape: only the axial accumulators are refilled (every update writes whole rows of
+        the coronal and sagittal planes)."""
+        if self.acc is not None:
+            self.acc.fill_(ops.PROJECT_IDENTITY[self.code])
+
+    def update(self, pix_chunk, n0):
+        k = pix_chunk.shape[0]
+        if tuple(pix_chunk.shape[1:]) != (self.h, self.w) or int(n0) < 0 or int(n0) + k > self.n:
+            raise RuntimeError("SeriesSlabs: chunk %s at slice %d does not lie in the volume (%d, %d, %d)"
+                               % (tuple(pix_chunk.shape), int(n0), self.n, self.h, self.w))
+        if k < 1:
+            return
+        for a in self.values:
+            ops.project_slabs_inplane(pix_chunk, int(n0), a, self.given[a], self.step[a], self.code, values=self.values[a],
+                                      level=self.level[a], wc=self.window[0], ww=self.window[1], hu=self.hu)
+        if self.acc is not None:
+            ops.project_accumulate_sliding(pix_chunk, int(n0), self.n, self.given["axial"], self.step["axial"], self.code, self.acc)
+
+    def result(self):
+        out = {}
+        for a in self.axes:
+            if a == "axial":
+                values, lvl = ops.project_finish(self.acc, self.code, self.thick[a], self.last_len[a], wc=self.window[0],
+                                                 ww=self.window[1], hu=self.hu, want_level=self.want_level)
+                out[a] = {"values": values, "level": lvl}
+            else:
+                out[a] = {"values": self.values[a], "level": self.level[a]}
+        return out
+
+
+def slab_volume(volume, thick, step=None, mode="max", axes=AXES, wc=50.0, ww=400.0, hu=False, level=True, batch=64, device=None):
+    """The sliding thin-slab projections of a volume that already exists, the twin of `project_volume`: int16 [N, H, W], a host
+    array / CPU tensor (chunks of `batch` slices cross PCIe one after another) or a device tensor.  Arguments as `SeriesSlabs`.
+    Returns what `SeriesSlabs.result` returns, of the input's kind (numpy arrays, CPU tensors or device tensors)."""
+    is_np = isinstance(volume, np.ndarray)
+    vol = torch.from_numpy(np.ascontiguousarray(volume)) if is_np else volume
+    if not torch.is_tensor(vol) or vol.dtype != torch.int16 or vol.dim() != 3:
+        raise RuntimeError("slab_volume: an int16 volume [N, H, W] expected")
+    if int(batch) < 1:
+        raise ValueError("slab_volume: batch >= 1 expected")
+    on_host = not vol.is_cuda
+    n, h, w = vol.shape
+    slabs = SeriesSlabs(n, h, w, thick, step=step, mode=mode, axes=axes, wc=wc, ww=ww, hu=hu, level=level,
+                        device=device if on_host else vol.device)
+    with torch.cuda.device(slabs.device):
+        for s, e, _ in plan_chunks(n, batch):
+            slabs.update(vol[s:e].to(slabs.device) if on_host else vol[s:e], s)
+        out = slabs.result()
+    return _projections_to_host(out, is_np) if on_host else out
 
 
 def default_detector(h, w):
@@ -313,6 +445,9 @@ class SeriesTranslator:
     sub_ct_range) and "sub_level" (uint8 in sub_window = (wc, ww) of a HU difference, None with level=False).
     project_source="sub" (needs subtract=True) projects and rotates the subtraction volume instead of the synthesized one, its
     levels in sub_window with hu=True: the bone-free MIP.  Without `subtract` nothing of this is allocated or launched.
+    slabs = a dict of `SeriesSlabs` keyword arguments (thick, and any of step, mode, axes) adds "slabs": {axis: {"values":
+    int16 [J, ...], "level": uint8}}, the sliding thin-slab projections of the same source in the same window, copied back once
+    after the last chunk; with slabs=None nothing of it is allocated or launched.
 
     size: the side(s) the generator runs at (None: the volume's own); a volume of another size is resized (nearest) on the way
     in and comes back at its own size.  wc / ww: the window of the 8-bit level; hu: pixels minus 1024 (SimpleITK) instead of
@@ -321,7 +456,7 @@ class SeriesTranslator:
 
     def __init__(self, generator, batch=16, size=None, wc=50.0, ww=400.0, hu=False, level=True, device=None, project=None,
                  slab=None, rotate=None, rotate_mode=None, subtract=False, sub_median=True, sub_floor=0, sub_ct_range=(None, None),
-                 sub_window=(150.0, 300.0), project_source="cta"):
+                 sub_window=(150.0, 300.0), project_source="cta", slabs=None):
         if int(batch) < 1:
             raise ValueError("SeriesTranslator: batch >= 1 expected")
         if project_source not in PROJECT_SOURCES or (project_source == "sub" and not subtract):
@@ -340,6 +475,10 @@ class SeriesTranslator:
             raise ValueError("SeriesTranslator: rotate needs at least one angle and a rotate_mode of %s, got %r"
                              % (PROJECTIONS, self.rotate_mode))
         self._rotator = self._rot_host = None
+        self.slabs = None if slabs is None else dict(slabs)
+        if self.slabs is not None and ("thick" not in self.slabs or set(self.slabs) - {"thick", "step", "mode", "axes"}):
+            raise ValueError("SeriesTranslator: slabs %r: a dict with 'thick' and any of 'step', 'mode', 'axes' expected" % (slabs,))
+        self._slabber = self._slab_host = None
         self.window = (float(wc), float(ww))
         self._projector = self._proj_host = None
         self.generator = generator
@@ -398,6 +537,7 @@ class SeriesTranslator:
             cur = torch.cuda.current_stream()
             proj = self._projector_for(n, h, w)
             rot = self._rotator_for(n, h, w)
+            slb = self._slabber_for(n, h, w)
             in_free = [None] * SLOTS       # event: the slot's H2D copy has drained, the host may rewrite it
             pending = [None] * SLOTS       # (event, start, stop): the slot's D2H copy, not yet moved into the result
 
@@ -449,6 +589,8 @@ class SeriesTranslator:
                         proj.update(src, s)
                     if rot is not None:
                         rot.update(src, s)
+                    if slb is not None:
+                        slb.update(src, s)
                 computed = torch.cuda.Event()
                 computed.record(cur)
                 drain(slot)                          # the chunk that used this slot last: its D2H started two chunks ago
@@ -478,6 +620,11 @@ class SeriesTranslator:
                 rot_staged = self._stage_rotation(rot.result())
                 rot_done = torch.cuda.Event()
                 rot_done.record(cur)
+            slab_done = None
+            if slb is not None:       # the finished slab planes of every axis, staged the same way
+                slab_staged = self._stage_slabs(slb.result())
+                slab_done = torch.cuda.Event()
+                slab_done.record(cur)
             for slot in sorted(range(SLOTS), key=lambda q: pending[q][1] if pending[q] else -1):
                 drain(slot)
             projections = None
@@ -493,6 +640,12 @@ class SeriesTranslator:
                 stats["wait"] += clock() - t0
                 rotation = {k: t.clone().numpy() if is_np else t.clone() for k, t in rot_staged.items()}
                 rotation["angles"] = np.array(rot.angles, dtype=np.float64) if is_np else torch.tensor(rot.angles, dtype=torch.float64)
+            slab_out = None
+            if slab_done is not None:
+                t0 = clock()
+                slab_done.synchronize()
+                stats["wait"] += clock() - t0
+                slab_out = {a: {k: t.clone().numpy() if is_np else t.clone() for k, t in d.items()} for a, d in slab_staged.items()}
         # the forwards above ran fused conv + InstanceNorm launches: none may have given up (raises)
         ops.nie_check("series inference")
         stats["total"] = clock() - t_call
@@ -501,6 +654,8 @@ class SeriesTranslator:
             out["projections"] = projections
         if rotation is not None:
             out["rotation"] = rotation
+        if slab_out is not None:
+            out["slabs"] = slab_out
         return out
 
     def _stage_projections(self, dev):
@@ -522,6 +677,29 @@ class SeriesTranslator:
         for k, t in dev.items():
             self._rot_host[k].copy_(t, non_blocking=True)
         return self._rot_host
+
+    def _stage_slabs(self, dev):
+        """Start the copies of the finished slab planes into page-locked buffers (kept between calls on volumes of one shape)."""
+        shapes = {a: tuple(d["values"].shape) for a, d in dev.items()}
+        if self._slab_host is None or {a: tuple(d["values"].shape) for a, d in self._slab_host.items()} != shapes:
+            self._slab_host = {a: {k: torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for k, t in d.items()}
+                               for a, d in dev.items()}
+        for a, d in dev.items():
+            for k, t in d.items():
+                self._slab_host[a][k].copy_(t, non_blocking=True)
+        return self._slab_host
+
+    def _slabber_for(self, n, h, w):
+        """The `SeriesSlabs` of an (n, h, w) volume, kept between calls on volumes of one shape; None without `slabs`."""
+        if self.slabs is None:
+            return None
+        s = self._slabber
+        if s is None or (s.n, s.h, s.w) != (n, h, w):
+            wc, ww = self._view_window()
+            s = self._slabber = SeriesSlabs(n, h, w, wc=wc, ww=ww, hu=self._view_hu(), device=self.device, **self.slabs)
+        else:
+            s.reset()
+        return s
 
     def _rotator_for(self, n, h, w):
         """The rotator of an (n, h, w) volume, kept between calls on volumes of one shape; None without `rotate`."""

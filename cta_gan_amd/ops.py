@@ -1829,8 +1829,101 @@ def project_rotate(pix, n0, coef, t, mode, values=None, level=None, fill=None, w
                                       _p(values), _p(level), _stream()), "ctg_project_rotate")
 
 
+# ---------------------------------------------------------------------------- sliding thin slabs (csrc/project_slabs.hip)
+SLAB_AXES = {"coronal": 0, "sagittal": 1}      # the in-plane axes of `project_slabs_inplane`
+SLAB_MAX_DIM = 65535
+
+
+def slab_count(length, thick, step):
+    """J of the slab rule (csrc/project_slabs.hip): slabs of min(thick, length) voxels every `step` voxels along `length`."""
+    length, thick, step = int(length), int(thick), int(step)
+    thick = min(thick, length)
+    return 1 if length <= thick else -((thick - length) // step) + 1
+
+
+def _slab_args(what, x, n0, thick, step, extra=()):
+    k, h, w = x.shape
+    if not (1 <= min((k, h, w) + tuple(extra)) and max((k, h, w) + tuple(extra)) <= SLAB_MAX_DIM):
+        raise RuntimeError("%s: K, H, W, N in 1 .. %d expected, got %s" % (what, SLAB_MAX_DIM, (k, h, w) + tuple(extra)))
+    if not 1 <= thick <= SLAB_MAX_DIM or not 1 <= step <= thick:
+        raise RuntimeError("%s: 1 <= step <= thick <= %d expected, got thick=%d step=%d" % (what, SLAB_MAX_DIM, thick, step))
+    if n0 < 0:
+        raise RuntimeError("%s: n0 >= 0 expected, got %d" % (what, n0))
+
+
+def project_slabs_inplane(pix, n0, axis, thick, step, mode, values=None, level=None, wc=50.0, ww=400.0, hu=False):
+    """One chunk of an int16 volume into its sliding thin-slab projections along an in-plane axis, in place: pix (K, H, W) int16
+    on the GPU (a contiguous view is taken as it is: 2-byte alignment is enough) = slices n0 .. n0+K-1; axis "coronal" / 0 (slabs
+    of `thick` rows every `step` rows, out (J, N, W)) or "sagittal" / 1 (slabs of columns, out (J, N, H)); 1 <= step <= thick,
+    thick is clipped to the axis, J = `slab_count`; mode 0 / "max", 1 / "min", 2 / "mean" (the sum / the slab's own length,
+    truncated toward zero).  values int16 and level uint8 on the GPU, either None: the call writes rows n0 .. n0+K-1 of every
+    plane and nothing else, the 8-bit level of the window (wc, ww, hu) in the same pass.  Exact integer arithmetic: equal to
+    numpy bit for bit."""
+    lib = _lib.load()
+    if not torch.is_tensor(pix) or not pix.is_cuda:
+        raise RuntimeError("project_slabs_inplane: CPU tensors are not supported (no CPU fallback)")
+    if pix.dtype != torch.int16 or pix.dim() != 3:
+        raise RuntimeError("project_slabs_inplane: pix must be int16 (K, H, W), got %s %s" % (pix.dtype, tuple(pix.shape)))
+    code = _project_mode(mode, "project_slabs_inplane")
+    ax = SLAB_AXES.get(axis, axis) if isinstance(axis, str) else axis
+    if isinstance(ax, bool) or not isinstance(ax, int) or ax not in (0, 1):
+        raise RuntimeError("project_slabs_inplane: axis 0 / 'coronal' or 1 / 'sagittal' expected, got %r" % (axis,))
+    if values is None and level is None:
+        raise RuntimeError("project_slabs_inplane: values, level or both expected")
+    for t, dtype, name in ((values, torch.int16, "values"), (level, torch.uint8, "level")):
+        if t is not None and (not torch.is_tensor(t) or not t.is_cuda or t.dtype != dtype or not t.is_contiguous() or t.dim() != 3):
+            raise RuntimeError("project_slabs_inplane: %s must be a contiguous %s tensor (J, N, L) on the GPU" % (name, dtype))
+    out = values if values is not None else level
+    if values is not None and level is not None and values.shape != level.shape:
+        raise RuntimeError("project_slabs_inplane: values %s and level %s differ in shape" % (tuple(values.shape), tuple(level.shape)))
+    if any(t is not None and t.device != pix.device for t in (values, level)):
+        raise RuntimeError("project_slabs_inplane: pix, values and level must live on one device")
+    x = pix.contiguous()
+    k, h, w = x.shape
+    n0, thick, step = int(n0), int(thick), int(step)
+    j, n, line = out.shape
+    if k < 1 or n0 < 0 or n0 + k > n:
+        raise RuntimeError("project_slabs_inplane: chunk of %d slices at slice %d does not lie in the volume of %d" % (k, n0, n))
+    _slab_args("project_slabs_inplane", x, n0, thick, step, (n,))
+    length, other = (h, w) if ax == 0 else (w, h)
+    if (j, line) != (slab_count(length, thick, step), other):
+        raise RuntimeError("project_slabs_inplane: outputs of shape %s, (%d, N, %d) expected for thick=%d step=%d along %d"
+                           % (tuple(out.shape), slab_count(length, thick, step), other, thick, step, length))
+    _lib.check(lib.ctg_project_slabs_inplane(_p(x), k, h, w, n0, n, ax, thick, step, code, float(wc), float(ww), int(bool(hu)),
+                                             _p(values), _p(level), _stream()), "ctg_project_slabs_inplane")
+
+
+def project_accumulate_sliding(pix, n0, n, thick, step, mode, axial):
+    """One chunk of an int16 volume of `n` slices into its sliding axial slabs, in place: pix (K, H, W) int16 on the GPU (a
+    contiguous view is taken as it is) = slices n0 .. n0+K-1; axial (J, H, W) int32 on the GPU, J = slab_count(n, thick, step),
+    filled with PROJECT_IDENTITY[mode] before the first chunk: slice m is combined into every slab j with
+    j step <= m < j step + thick.  Chunks in any order, every slice once; `project_finish(axial, mode, min(thick, n), last_len)`
+    finishes it.  With step == thick the accumulator equals `project_accumulate`'s bit for bit."""
+    lib = _lib.load()
+    if not torch.is_tensor(pix) or not pix.is_cuda:
+        raise RuntimeError("project_accumulate_sliding: CPU tensors are not supported (no CPU fallback)")
+    if pix.dtype != torch.int16 or pix.dim() != 3:
+        raise RuntimeError("project_accumulate_sliding: pix must be int16 (K, H, W), got %s %s" % (pix.dtype, tuple(pix.shape)))
+    code = _project_mode(mode, "project_accumulate_sliding")
+    if not torch.is_tensor(axial) or not axial.is_cuda or axial.dtype != torch.int32 or not axial.is_contiguous():
+        raise RuntimeError("project_accumulate_sliding: axial must be a contiguous int32 tensor on the GPU")
+    if axial.device != pix.device:
+        raise RuntimeError("project_accumulate_sliding: pix and axial must live on one device")
+    x = pix.contiguous()
+    k, h, w = x.shape
+    n0, n, thick, step = int(n0), int(n), int(thick), int(step)
+    if k < 1 or n0 < 0 or n0 + k > n:
+        raise RuntimeError("project_accumulate_sliding: chunk of %d slices at slice %d does not lie in the volume of %d" % (k, n0, n))
+    _slab_args("project_accumulate_sliding", x, n0, thick, step, (n,))
+    if tuple(axial.shape) != (slab_count(n, thick, step), h, w):
+        raise RuntimeError("project_accumulate_sliding: axial of shape %s, (%d, %d, %d) expected for thick=%d step=%d of %d slices"
+                           % (tuple(axial.shape), slab_count(n, thick, step), h, w, thick, step, n))
+    _lib.check(lib.ctg_project_accumulate_sliding(_p(x), k, h, w, n0, n, thick, step, code, _p(axial), _stream()),
+               "ctg_project_accumulate_sliding")
+
+
 # ---------------------------------------------------------------------------- subtraction volume (csrc/subtract.hip)
-INT_MIN = -2 ** 31      # `floor` of subtract_slices that keeps every difference
+INT_MIN = -2 ** 31     # `floor` of subtract_slices that keeps every difference
 
 
 def _subtract_band(ct_range):

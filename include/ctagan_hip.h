@@ -459,6 +459,33 @@ int ctg_project_rotate(const short* pix, int K, int H, int W, int n0, int N, con
 int ctg_subtract_slices(const short* cta, const short* ct_hu, int B, int H, int W, int cta_is_hu, int median, int floor, int ct_min,
                         int ct_max, float wc, float ww, short* sub, unsigned char* level, void* stream);
 
+/* ---- series inference, sliding thin-slab projections (added under ABI 15: purely additive, no existing signature or meaning
+ * moves, so the version stays 15): the projection of a slab of `thick` voxels that moves on by `step` voxels, along any of the
+ * three body axes, chunk by chunk behind ctg_export_slices (cta_gan_amd/infer.py: SeriesSlabs.update, SeriesTranslator(slabs=...),
+ * slab_volume).  The reference has no counterpart.
+ * One rule for every axis of extent L (N slices, H rows, W columns): 1 <= step <= thick is checked against the thick given, then
+ *   T = min(thick, L); slab j covers [j step, min(j step + T, L)); J = 1 if L <= T, else ceil((L - T) / step) + 1.  Only the last
+ *   slab can be short (its mean divides by its own length); step == thick is the plan of ctg_project_accumulate.
+ * ctg_project_slabs_inplane: pix = int16 [K][H][W], contiguous, 2-byte aligned (a view into a larger buffer is fine): slices
+ *   n0 .. n0+K-1 of a volume of N slices.  axis 0: coronal, slabs along y, out[j][n][x] = the reduction over the rows of slab j,
+ *   [J][N][W]; axis 1: sagittal, slabs along x, out[j][n][y] = the reduction over the columns of slab j, [J][N][H].  mode 0 max,
+ *   1 min, 2 mean = the exact sum / the slab's own length, C integer division (truncating toward zero).  values int16 and level
+ *   uint8 of that shape, either may be NULL (not both): one launch writes rows n0 .. n0+K-1 of all J planes and nothing else.
+ *   level = what ctg_project_finish gives that value for (wc, ww, hu), written in the same pass.  Integer arithmetic up to the
+ *   level: the same bits as numpy.
+ * ctg_project_accumulate_sliding: the axial slabs.  axial = int32 [J][H][W] that holds the mode's identity before the first chunk
+ *   (J from N, thick, step by the rule); slice n is combined into every slab that covers it, in place by a plain read-modify-write
+ *   (never first-writes; the calls of one volume are ordered on one stream, in any order, every slice once).  mode 0 max, 1 min,
+ *   2 sum.  With step == thick the accumulators equal ctg_project_accumulate's bit for bit; ctg_project_finish(axial, J, H W,
+ *   mode, T, the last slab's length, ...) finishes them.
+ *   CTG_EINVAL (both): a required pointer NULL or misaligned (pix, values 2 bytes; axial 4), K / H / W / N / thick outside
+ *   1 .. 65535 (a sum of fewer than 65536 int16 values stays inside int32), step outside 1 .. thick, mode outside 0 .. 2, axis
+ *   outside 0 .. 1, n0 < 0, n0 + K > N, a grid beyond 2^31 - 1 workgroups.  Nothing is launched then. ---- */
+int ctg_project_slabs_inplane(const short* pix, int K, int H, int W, int n0, int N, int axis, int thick, int step, int mode,
+                              float wc, float ww, int hu, short* values, unsigned char* level, void* stream);
+int ctg_project_accumulate_sliding(const short* pix, int K, int H, int W, int n0, int N, int thick, int step, int mode, int* axial,
+                                   void* stream);
+
 /* ---- LPIPS (AlexNet, lpips 0.1) of the test() loops (ABI 14): `loss_fn_alex = lpips.LPIPS(net='alex')` (trainer/HdTrainer.py:26-28)
  * and its calls `loss_fn_alex.forward(torch.tensor(c), torch.tensor(b))` on the windowed and on the raw masked pair of every slice
  * (HdTrainer.py:504-513, 531-536, 1029-1031, 1054-1056; the twins in CycTrainer.py, p2pTrainer.py, RegTrainer.py).  The five

@@ -5,6 +5,8 @@
                       [--level-dir DIR] [--hu] [--wc 50 --ww 400] [--batch 16] [--dtype bf16x3]
                       [--mip-dir DIR [--mip-mode max|min|mean] [--slab K] [--aspect R]]
                       [--rot-dir DIR [--rot-angles 36] [--rot-span 360] [--mip-mode max|min|mean] [--aspect R]]
+                      [--sts-dir DIR --sts-thick T[,Tc,Ts] [--sts-step S[,Sc,Ss]] [--sts-axes axial,coronal,sagittal]
+                       [--mip-mode max|min|mean] [--aspect R]]
                       [--sub-output sub.npy [--sub-level-dir DIR] [--sub-floor 0] [--sub-no-median] [--sub-ct-min HU]
                        [--sub-ct-max HU] [--sub-wc 150 --sub-ww 300] [--mip-source cta|sub]]
 
@@ -21,11 +23,16 @@ spacing / pixel spacing draws the coronal and sagittal PNGs with round(N R) rows
 axis (0 = coronal, 90 = sagittal; --mip-mode, --wc / --ww, --hu and --aspect as above), made on the device while the volume is
 made: rot_%03d.png, one 8-bit frame [round(N R), D] per angle with D = ceil(hypot(H, W)), and rotation.npz with values (int16
 [A, N, D]), level (uint8) and angles (degrees).
+--sts-dir: the sliding thin-slab projections of the synthesized volume, the mode a CTA is read in: slabs of --sts-thick voxels
+moved on by --sts-step voxels (default: the thickness, slabs that do not overlap; 1 <= step <= thick) along the --sts-axes.  One
+number serves every axis, three (axial, coronal, sagittal) give each axis its own: slice spacing and pixel spacing differ.
+axial_%03d.png [H, W], coronal_%03d.png [round(N R), W] and sagittal_%03d.png [round(N R), H], one per slab, in the window
+(--mip-mode, --wc / --ww, --hu and --aspect as above), and slabs.npz with the int16 values per axis.
 --sub-output: the subtraction volume, synthesized CTA minus the input CT (int16 [N, H, W] .npy of HU differences), made on the
 device while the volume is made: the pair is registered by construction, so bone cancels.  A 3 x 3 in-plane median unless
 --sub-no-median; differences below --sub-floor, and pixels whose input HU lies outside --sub-ct-min .. --sub-ct-max (default:
 open), become 0.  --sub-level-dir: one 8-bit PNG per slice in the window --sub-wc / --sub-ww of a HU difference.  --mip-source
-sub makes --mip-dir and --rot-dir show the subtraction volume (levels in the --sub window) instead of the synthesized one: the
+sub makes --mip-dir, --rot-dir and --sts-dir show the subtraction volume (levels in the --sub window) instead of the synthesized one: the
 bone-free MIP.
 DICOM reading and writing are not part of this build.
 """
@@ -54,6 +61,10 @@ def build_parser():
     parser.add_argument("--rot-dir", type=str, default=None, help="also write the rotating projection of the synthesized volume here")
     parser.add_argument("--rot-angles", type=int, default=36, help="view angles of the rotating projection (with --rot-dir)")
     parser.add_argument("--rot-span", type=float, default=360.0, help="degrees the view angles are spread over (with --rot-dir)")
+    parser.add_argument("--sts-dir", type=str, default=None, help="also write the sliding thin-slab projections here")
+    parser.add_argument("--sts-thick", type=str, default=None, help="voxels per slab: T, or T,Tc,Ts for axial,coronal,sagittal")
+    parser.add_argument("--sts-step", type=str, default=None, help="voxels a slab moves on: S or S,Sc,Ss (default: the thickness)")
+    parser.add_argument("--sts-axes", type=str, default="axial,coronal,sagittal", help="axes of --sts-dir, comma-separated")
     parser.add_argument("--sub-output", type=str, default=None, help="also write the subtraction volume (synthesized - input) here")
     parser.add_argument("--sub-level-dir", type=str, default=None, help="one 8-bit PNG per subtraction slice (with --sub-output)")
     parser.add_argument("--sub-floor", type=int, default=0, help="differences below this many HU become 0")
@@ -67,9 +78,44 @@ def build_parser():
     return parser
 
 
+STS_AXES = ("axial", "coronal", "sagittal")
+
+
+def _sts_counts(parser, text, flag):
+    """"T" or "T,Tc,Ts" -> {axis: int} over all three axes."""
+    try:
+        counts = [int(v) for v in text.split(",")]
+    except ValueError:
+        parser.error("%s: whole numbers expected, got %r" % (flag, text))
+    if len(counts) not in (1, 3) or min(counts) < 1:
+        parser.error("%s: one positive count, or three (axial,coronal,sagittal), expected, got %r" % (flag, text))
+    return dict(zip(STS_AXES, counts * 3 if len(counts) == 1 else counts))
+
+
+def sts_options(parser, opts):
+    """The `SeriesTranslator(slabs=...)` dict of --sts-dir (None without it); bad values end in parser.error."""
+    if opts.sts_dir is None:
+        if opts.sts_thick is not None or opts.sts_step is not None:
+            parser.error("--sts-thick and --sts-step need --sts-dir")
+        return None
+    if opts.sts_thick is None:
+        parser.error("--sts-dir needs --sts-thick")
+    axes = tuple(a for a in opts.sts_axes.split(",") if a)
+    if not axes or any(a not in STS_AXES for a in axes) or len(set(axes)) != len(axes):
+        parser.error("--sts-axes: a comma-separated choice of %s expected, got %r" % (", ".join(STS_AXES), opts.sts_axes))
+    thick = _sts_counts(parser, opts.sts_thick, "--sts-thick")
+    step = dict(thick) if opts.sts_step is None else _sts_counts(parser, opts.sts_step, "--sts-step")
+    for a in axes:
+        if step[a] > thick[a]:
+            parser.error("--sts-step: %s step %d above its thickness %d" % (a, step[a], thick[a]))
+    axes = tuple(a for a in STS_AXES if a in axes)
+    return {"thick": {a: thick[a] for a in axes}, "step": {a: step[a] for a in axes}, "mode": opts.mip_mode, "axes": axes}
+
+
 def parse_args(argv=None):
     parser = build_parser()
     opts = parser.parse_args(argv)
+    opts.sts = sts_options(parser, opts)
     if opts.sub_output is None and (opts.mip_source == "sub" or opts.sub_level_dir is not None):
         parser.error("--mip-source sub and --sub-level-dir need --sub-output")
     if opts.sub_ct_min is not None and opts.sub_ct_max is not None and opts.sub_ct_min > opts.sub_ct_max:
@@ -111,7 +157,7 @@ def main(argv=None):
                                  project_source=opts.mip_source,
                                  project=opts.mip_mode if opts.mip_dir is not None else None, slab=opts.slab,
                                  rotate=view_angles(opts.rot_angles, opts.rot_span) if opts.rot_dir is not None else None,
-                                 rotate_mode=opts.mip_mode)
+                                 rotate_mode=opts.mip_mode, slabs=opts.sts)
     out = translate(volume)
     np.save(opts.output, out["pix"])
     if opts.level_dir is not None:
@@ -149,6 +195,19 @@ def main(argv=None):
             Image.fromarray(np.ascontiguousarray(plane[rows])).save(os.path.join(opts.rot_dir, "rot_%03d.png" % i))
         np.savez(os.path.join(opts.rot_dir, "rotation.npz"), values=rot["values"], level=rot["level"], angles=rot["angles"])
         print("wrote %d views of the %s projection to %s" % (len(rot["angles"]), opts.mip_mode, opts.rot_dir), flush=True)
+    if opts.sts_dir is not None:
+        from PIL import Image
+        from cta_gan_amd.infer import aspect_rows
+        os.makedirs(opts.sts_dir, exist_ok=True)
+        slabs = out["slabs"]
+        rows = aspect_rows(volume.shape[0], opts.aspect)
+        for axis, d in slabs.items():
+            for i, plane in enumerate(d["level"]):
+                plane = plane if axis == "axial" else np.ascontiguousarray(plane[rows])
+                Image.fromarray(plane).save(os.path.join(opts.sts_dir, "%s_%03d.png" % (axis, i)))
+        np.savez(os.path.join(opts.sts_dir, "slabs.npz"), **{axis: d["values"] for axis, d in slabs.items()})
+        print("wrote the %s thin slabs (%s) to %s" % (opts.mip_mode, ", ".join("%s: %d" % (a, len(d["values"]))
+                                                                             for a, d in slabs.items()), opts.sts_dir), flush=True)
     print("wrote %s: %d slices of %d x %d%s" % (opts.output, volume.shape[0], volume.shape[1], volume.shape[2],
                                                "" if opts.level_dir is None else " (+ PNGs in %s)" % opts.level_dir), flush=True)
 

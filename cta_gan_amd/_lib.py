@@ -83,6 +83,7 @@ SIGNATURES = {
     "ctg_project_accumulate": "piiiiiipppp",
     "ctg_project_finish": "piliiiffippp",
     "ctg_project_rotate": "piiiiipiiiiiffippp",
+    "ctg_project_rotate_bilinear": "piiiiipiiiiiffippp",
     "ctg_subtract_slices": "ppiiiiiiiiffppp",
     "ctg_project_slabs_inplane": "piiiiiiiiiffippp",
     "ctg_project_accumulate_sliding": "piiiiiiiipp",

@@ -21,6 +21,16 @@
 // (scalar loads).  Whatever the interval says, a sample is read only after its own index passed the bounds check, and a sample
 // that fails it reads pixel 0 of the slice and is not counted: every address is inside the slice whatever the table holds.  The
 // fixed-point sums are formed in unsigned arithmetic (wraps, never undefined) and read as int32.
+//
+// Bilinear sampling (ctg_project_rotate_bilinear; LERP below) shares the table, the detector, the interval and the definition of
+// "counted" -- pixel (X >> 16, Y >> 16) in the slice, X and Y carrying the + 0.5 of the nearest rule -- so a ray's count and the
+// place of `fill` are those of nearest sampling.  The value of a counted sample is interpolated about the centre-based position
+//     Xc = X - 32768, Yc = Y - 32768:   x0 = Xc >> 16, fx = (Xc >> 8) & 255,   y0 = Yc >> 16, fy = (Yc >> 8) & 255
+//     v = ((p[ya][xa] (256 - fx) + p[ya][xb] fx) (256 - fy) + (p[yb][xa] (256 - fx) + p[yb][xb] fx) fy + 32768) >> 16
+// with xa = clamp(x0), xb = clamp(x0 + 1) to 0 .. W-1 and ya, yb likewise (the edge pixel replicated; x0 is -1 in the first half
+// pixel): four 16-bit loads, since only 2-byte alignment is promised.  The clamps keep every address inside the slice whatever
+// the table holds, and a sample that is not counted still reads pixel 0.  The weights sum to 65536, so v is an int16 value.
+// Oversampled rays (steps of 1 / s voxel) are a matter of the table and of T alone: both kernels take them as they are.
 #include "common.h"
 #include "window_arith.h"
 
@@ -57,7 +67,20 @@ template <int MODE> __device__ __forceinline__ int rot_op(int a, int b) {
     else return a + b;
 }
 
-template <int MODE>
+// The value of a bilinear sample from its four pixels and two 8-bit fractions.  |top|, |bot| <= 32768 * 256 = 2^23 and the two
+// weights of the second step sum to 256, so |top (256 - fy) + bot fy| <= 2^31 - reached only by four pixels of -32768 - and with
+// the rounding half the sum lies in [-2^31 + 32768, 2^31 - 32768]: int32 holds it with nothing to spare.  Formed in unsigned
+// arithmetic like the sums above and read as int32; the shift is arithmetic.
+__device__ __forceinline__ int rot_lerp(int p00, int p01, int p10, int p11, int fx, int fy) {
+    const unsigned wx = 256u - (unsigned)fx, wy = 256u - (unsigned)fy;
+    const unsigned top = (unsigned)p00 * wx + (unsigned)p01 * (unsigned)fx;
+    const unsigned bot = (unsigned)p10 * wx + (unsigned)p11 * (unsigned)fx;
+    return (int)(top * wy + bot * (unsigned)fy + 32768u) >> 16;
+}
+
+__device__ __forceinline__ int rot_clamp(int v, int last) { return v < 0 ? 0 : (v > last ? last : v); }
+
+template <int MODE, bool LERP>
 __global__ __launch_bounds__(ROT_THREADS) void project_rotate_kernel(const short* __restrict__ pix, int H, int W, int n0, int N,
                                                                      const int* __restrict__ coef, int A, int U, int T, int nseg,
                                                                      int fill, float wc, float ww, int add,
@@ -79,21 +102,48 @@ __global__ __launch_bounds__(ROT_THREADS) void project_rotate_kernel(const short
     unsigned X = X0 + c2 * (unsigned)t, Y = Y0 + c5 * (unsigned)t;
     const unsigned dX = c2 * ROT_TL, dY = c5 * ROT_TL;
     for (; t <= hi; t += ROT_TL * ROT_INFLIGHT) {
-        int raw[ROT_INFLIGHT];
         bool ok[ROT_INFLIGHT];
+        if constexpr (LERP) {
+            int p[ROT_INFLIGHT][4], fx[ROT_INFLIGHT], fy[ROT_INFLIGHT];      // 4 ROT_INFLIGHT gathers before the first is used
 #pragma unroll
-        for (int j = 0; j < ROT_INFLIGHT; ++j) {
-            const int xi = (int)X >> 16, yi = (int)Y >> 16;
-            ok[j] = t + j * ROT_TL <= hi && xi >= 0 && xi < W && yi >= 0 && yi < H;
-            raw[j] = slice[ok[j] ? yi * W + xi : 0];
-            X += dX;
-            Y += dY;
-        }
+            for (int j = 0; j < ROT_INFLIGHT; ++j) {
+                const int xi = (int)X >> 16, yi = (int)Y >> 16;
+                ok[j] = t + j * ROT_TL <= hi && xi >= 0 && xi < W && yi >= 0 && yi < H;
+                const int Xc = (int)(X - 32768u), Yc = (int)(Y - 32768u);
+                fx[j] = (Xc >> 8) & 255;
+                fy[j] = (Yc >> 8) & 255;
+                const int x0 = Xc >> 16, y0 = Yc >> 16;      // in -32768 .. 32767: x0 + 1 cannot wrap
+                const int xa = ok[j] ? rot_clamp(x0, W - 1) : 0, xb = ok[j] ? rot_clamp(x0 + 1, W - 1) : 0;
+                const int ra = ok[j] ? rot_clamp(y0, H - 1) * W : 0, rb = ok[j] ? rot_clamp(y0 + 1, H - 1) * W : 0;
+                p[j][0] = slice[ra + xa];
+                p[j][1] = slice[ra + xb];
+                p[j][2] = slice[rb + xa];
+                p[j][3] = slice[rb + xb];
+                X += dX;
+                Y += dY;
+            }
 #pragma unroll
-        for (int j = 0; j < ROT_INFLIGHT; ++j) {
-            if (!ok[j]) continue;
-            acc = rot_op<MODE>(acc, raw[j]);
-            ++cnt;
+            for (int j = 0; j < ROT_INFLIGHT; ++j) {
+                if (!ok[j]) continue;
+                acc = rot_op<MODE>(acc, rot_lerp(p[j][0], p[j][1], p[j][2], p[j][3], fx[j], fy[j]));
+                ++cnt;
+            }
+        } else {
+            int raw[ROT_INFLIGHT];
+#pragma unroll
+            for (int j = 0; j < ROT_INFLIGHT; ++j) {
+                const int xi = (int)X >> 16, yi = (int)Y >> 16;
+                ok[j] = t + j * ROT_TL <= hi && xi >= 0 && xi < W && yi >= 0 && yi < H;
+                raw[j] = slice[ok[j] ? yi * W + xi : 0];
+                X += dX;
+                Y += dY;
+            }
+#pragma unroll
+            for (int j = 0; j < ROT_INFLIGHT; ++j) {
+                if (!ok[j]) continue;
+                acc = rot_op<MODE>(acc, raw[j]);
+                ++cnt;
+            }
         }
     }
 #pragma unroll
@@ -109,18 +159,18 @@ __global__ __launch_bounds__(ROT_THREADS) void project_rotate_kernel(const short
     if (level != nullptr) level[o] = (unsigned char)(int)stored_level((float)(v + add), win_params(wc, ww));
 }
 
-template <int MODE>
+template <int MODE, bool LERP>
 static void rotate_launch(const short* pix, int K, int H, int W, int n0, int N, const int* coef, int A, int U, int T, int fill,
                           float wc, float ww, int hu, short* values, unsigned char* level, hipStream_t st) {
     const int nseg = (U + ROT_WG_U - 1) / ROT_WG_U;
-    hipLaunchKernelGGL(project_rotate_kernel<MODE>, dim3((unsigned)((long)K * nseg * A)), dim3(ROT_THREADS), 0, st, pix, H, W, n0, N,
+    hipLaunchKernelGGL((project_rotate_kernel<MODE, LERP>), dim3((unsigned)((long)K * nseg * A)), dim3(ROT_THREADS), 0, st, pix, H, W, n0, N,
                        coef, A, U, T, nseg, fill, wc, ww, hu ? 1024 : 0, values, level);
 }
 
-extern "C" int ctg_project_rotate(const short* pix, int K, int H, int W, int n0, int N, const int* coef, int A, int U, int T,
-                                  int mode, int fill, float wc, float ww, int hu, short* values, unsigned char* level,
-                                  void* stream) {
-    CTG_ENTER();
+// both entry points: the argument checks and the launch
+template <bool LERP>
+static int rotate_entry(const short* pix, int K, int H, int W, int n0, int N, const int* coef, int A, int U, int T, int mode, int fill,
+                        float wc, float ww, int hu, short* values, unsigned char* level, void* stream) {
     if (pix == nullptr || coef == nullptr || (values == nullptr && level == nullptr)) return CTG_EINVAL;
     if (K < 1 || n0 < 0 || N < 1 || n0 > N - K) return CTG_EINVAL;
     if (H < 1 || H > ROT_MAX_DIM || W < 1 || W > ROT_MAX_DIM || U < 1 || U > ROT_MAX_DIM || T < 1 || T > ROT_MAX_DIM) return CTG_EINVAL;
@@ -129,8 +179,22 @@ extern "C" int ctg_project_rotate(const short* pix, int K, int H, int W, int n0,
     // one workgroup per (slice, segment, angle): the grid's x dimension
     if ((long)K * ((U + ROT_WG_U - 1) / ROT_WG_U) * A > 0x7fffffffL) return CTG_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    if (mode == ROT_MAX) rotate_launch<ROT_MAX>(pix, K, H, W, n0, N, coef, A, U, T, fill, wc, ww, hu, values, level, st);
-    else if (mode == ROT_MIN) rotate_launch<ROT_MIN>(pix, K, H, W, n0, N, coef, A, U, T, fill, wc, ww, hu, values, level, st);
-    else rotate_launch<ROT_SUM>(pix, K, H, W, n0, N, coef, A, U, T, fill, wc, ww, hu, values, level, st);
+    if (mode == ROT_MAX) rotate_launch<ROT_MAX, LERP>(pix, K, H, W, n0, N, coef, A, U, T, fill, wc, ww, hu, values, level, st);
+    else if (mode == ROT_MIN) rotate_launch<ROT_MIN, LERP>(pix, K, H, W, n0, N, coef, A, U, T, fill, wc, ww, hu, values, level, st);
+    else rotate_launch<ROT_SUM, LERP>(pix, K, H, W, n0, N, coef, A, U, T, fill, wc, ww, hu, values, level, st);
     return ctg_launch_status();
+}
+
+extern "C" int ctg_project_rotate(const short* pix, int K, int H, int W, int n0, int N, const int* coef, int A, int U, int T,
+                                  int mode, int fill, float wc, float ww, int hu, short* values, unsigned char* level,
+                                  void* stream) {
+    CTG_ENTER();
+    return rotate_entry<false>(pix, K, H, W, n0, N, coef, A, U, T, mode, fill, wc, ww, hu, values, level, stream);
+}
+
+extern "C" int ctg_project_rotate_bilinear(const short* pix, int K, int H, int W, int n0, int N, const int* coef, int A, int U,
+                                           int T, int mode, int fill, float wc, float ww, int hu, short* values,
+                                           unsigned char* level, void* stream) {
+    CTG_ENTER();
+    return rotate_entry<true>(pix, K, H, W, n0, N, coef, A, U, T, mode, fill, wc, ww, hu, values, level, stream);
 }

@@ -13,9 +13,12 @@ levels (`ops.project_finish`) cross PCIe, once, after the last chunk.
 
 Rotating projections (`SeriesRotator`, `rotate_volume`, `SeriesTranslator(rotate=...)`): the same projection at any number of
 view angles about the cranio-caudal axis, what an angiography volume is read as first.  A row of a rotated view depends on one
-slice only, so every chunk finishes its own rows of every angle in one launch (`ops.project_rotate`): nearest sampling on a 16.16
-fixed-point grid, unit steps along the ray, integer arithmetic throughout.  Unit steps with nearest sampling visit about 82 % of
-the voxels at 45 degrees (a ray of slope 1 skips pixels between its samples); oversampled or bilinear steps are not built.
+slice only, so every chunk finishes its own rows of every angle in one launch (`ops.project_rotate`): samples on a 16.16
+fixed-point grid, integer arithmetic throughout.  The default is nearest sampling at unit steps, which visits about 82 % of the
+voxels at 45 degrees (a ray of slope 1 skips pixels between its samples), so a one-pixel vessel can vanish at some angles.
+`sampling="bilinear"` interpolates the four pixels around every sample (8-bit fractions, still exact integers) and
+`oversample=s` takes s steps per voxel, with either sampling: bilinear sees a one-pixel maximum at every angle, nearest at two
+steps per voxel at nearly every one.
 
 Subtraction (`subtract_volume`, `SeriesTranslator(subtract=True)`): the synthesized CTA minus the CT it was made from.  The
 generator writes on its input's pixel grid, so the pair is registered by construction: the difference of the stored values is the
@@ -290,39 +293,55 @@ def view_angles(count, span=360.0, start=0.0):
     return [float(start) + i * float(span) / count for i in range(count)]
 
 
-def rotation_coefficients(angle, h, w, u=None, t=None):
+def rotation_coefficients(angle, h, w, u=None, t=None, oversample=1):
     """The six 16.16 fixed-point coefficients (c0 .. c5) of the view at `angle` degrees about the axis through the centre
-    ((w-1)/2, (h-1)/2) of an h x w slice, for a detector of u columns and rays of t unit steps (default: `default_detector`):
-    sample (i, j) of the view is pixel x = (c0 + c1 i + c2 j) >> 16, y = (c3 + c4 i + c5 j) >> 16, the nearest pixel to
-        x = cx + (i - cu) cos - (j - ct) sin,   y = cy + (i - cu) sin + (j - ct) cos,   cu = (u-1)/2, ct = (t-1)/2.
+    ((w-1)/2, (h-1)/2) of an h x w slice, for a detector of u columns and rays of t voxels (default: `default_detector`) taken
+    in t s steps of 1 / s voxel, s = `oversample`: sample (i, j) of the view is pixel x = (c0 + c1 i + c2 j) >> 16,
+    y = (c3 + c4 i + c5 j) >> 16, the nearest pixel to
+        x = cx + (i - cu) cos - (j/s - ct) sin,   y = cy + (i - cu) sin + (j/s - ct) cos,   cu = (u-1)/2, ct = (t s - 1)/(2 s).
     0 degrees is the coronal view (rays along y, the detector along x), 90 the sagittal one.  float64, rounded by
-    floor(v * 65536 + 0.5)."""
-    h, w = int(h), int(w)
+    floor(v * 65536 + 0.5); s = 1 divides by exactly 1, so its six integers are those of unit steps.  The kernels are called
+    with T = t s steps."""
+    h, w, s = int(h), int(w), int(oversample)
     d = default_detector(h, w)
     u, t = d if u is None else int(u), d if t is None else int(t)
     if min(h, w, u, t) < 1 or max(h, w, u, t) > ops.ROTATE_MAX_DIM:
         raise ValueError("rotation_coefficients: h, w, u, t in 1 .. %d expected, got %d %d %d %d" % (ops.ROTATE_MAX_DIM, h, w, u, t))
+    if s < 1 or t * s > ops.ROTATE_MAX_DIM:
+        raise ValueError("rotation_coefficients: oversample >= 1 and t * oversample <= %d steps expected, got t = %d, "
+                         "oversample = %d: %d steps" % (ops.ROTATE_MAX_DIM, t, s, t * s))
     rad = math.radians(float(angle))
     cos, sin = math.cos(rad), math.sin(rad)
-    cx, cy, cu, ct = (w - 1) / 2.0, (h - 1) / 2.0, (u - 1) / 2.0, (t - 1) / 2.0
+    cx, cy, cu, ct = (w - 1) / 2.0, (h - 1) / 2.0, (u - 1) / 2.0, (t * s - 1) / (2.0 * s)
 
     def r(v):
         return int(math.floor(v * 65536.0 + 0.5))
 
-    return (r(cx - cu * cos + ct * sin + 0.5), r(cos), r(-sin), r(cy - cu * sin - ct * cos + 0.5), r(sin), r(cos))
+    return (r(cx - cu * cos + ct * sin + 0.5), r(cos), r(-sin / s), r(cy - cu * sin - ct * cos + 0.5), r(sin), r(cos / s))
+
+
+def _check_sampling(who, sampling, oversample):
+    if sampling not in ops.ROTATE_SAMPLINGS:
+        raise ValueError("%s: sampling %r is not one of %s" % (who, sampling, tuple(ops.ROTATE_SAMPLINGS)))
+    if isinstance(oversample, bool) or not isinstance(oversample, (int, np.integer)) or oversample < 1:
+        raise ValueError("%s: oversample: an integer >= 1 expected, got %r" % (who, oversample))
 
 
 class SeriesRotator:
     """Rotating projections of an int16 volume [n, h, w] that arrives in chunks on the device: one plane [n, U] per view angle
-    (degrees about the cranio-caudal axis; 0 = coronal, 90 = sagittal), mode "max", "min" or "mean" along rays of T unit steps.
-    detector: None (U = T = `default_detector`), an int or (U, T).  A ray that misses the slice gets `fill` (default: air, 0 or
+    (degrees about the cranio-caudal axis; 0 = coronal, 90 = sagittal), mode "max", "min" or "mean" along rays of T voxels.
+    detector: None (U = T = `default_detector`), an int or (U, T).  sampling: "nearest" or "bilinear"; oversample = s >= 1: a ray
+    takes `.steps` = T s steps of 1 / s voxel (`.t` stays T).  A ray that misses the slice gets `fill` (default: air, 0 or
     -1024 with `hu`); level=False skips the 8-bit planes of the window (wc, ww).  `update(pix_chunk, n0)` in any order, every
     slice once: a chunk finishes its own rows of every angle; `result()` -> {"values": int16 [A, n, U], "level": uint8 or None,
     "angles": float64 [A]} on the device.  Exact integer arithmetic on the current stream: equal to numpy bit for bit."""
 
-    def __init__(self, n, h, w, angles, mode="max", detector=None, fill=None, wc=50.0, ww=400.0, hu=False, level=True, device=None):
+    def __init__(self, n, h, w, angles, mode="max", detector=None, fill=None, wc=50.0, ww=400.0, hu=False, level=True, device=None,
+                 sampling="nearest", oversample=1):
         if mode not in PROJECTIONS:
             raise ValueError("SeriesRotator: mode %r is not one of %s" % (mode, PROJECTIONS))
+        _check_sampling("SeriesRotator", sampling, oversample)
+        self.sampling, self.oversample = sampling, int(oversample)
         self.n, self.h, self.w = int(n), int(h), int(w)
         if min(self.n, self.h, self.w) < 1:
             raise ValueError("SeriesRotator: a volume of at least one voxel expected")
@@ -331,13 +350,15 @@ class SeriesRotator:
             raise ValueError("SeriesRotator: 1 .. %d view angles expected, got %d" % (ops.ROTATE_MAX_DIM, len(self.angles)))
         d = default_detector(self.h, self.w)
         self.u, self.t = (d, d) if detector is None else _pair(detector)
+        self.steps = self.t * self.oversample
         self.mode, self.code = mode, ops.PROJECT_MODES[mode]
         self.hu, self.window = bool(hu), (float(wc), float(ww))
         self.fill = (-1024 if self.hu else 0) if fill is None else int(fill)
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("SeriesRotator: a GPU device is required (no CPU fallback)")
-        self.table = ops.RotateTable([rotation_coefficients(a, self.h, self.w, self.u, self.t) for a in self.angles], self.device)
+        self.table = ops.RotateTable([rotation_coefficients(a, self.h, self.w, self.u, self.t, self.oversample)
+                                      for a in self.angles], self.device)
         shape = (len(self.angles), self.n, self.u)
         self.values = torch.empty(shape, dtype=torch.int16, device=self.device)
         self.level = torch.empty(shape, dtype=torch.uint8, device=self.device) if level else None
@@ -353,18 +374,19 @@ class SeriesRotator:
                                % (tuple(pix_chunk.shape), int(n0), self.n, self.h, self.w))
         if k < 1:
             return
-        ops.project_rotate(pix_chunk, int(n0), self.table, self.t, self.code, values=self.values, level=self.level,
-                           fill=self.fill, wc=self.window[0], ww=self.window[1], hu=self.hu)
+        ops.project_rotate(pix_chunk, int(n0), self.table, self.steps, self.code, values=self.values, level=self.level,
+                           fill=self.fill, wc=self.window[0], ww=self.window[1], hu=self.hu, sampling=self.sampling)
 
     def result(self):
         return {"values": self.values, "level": self.level, "angles": self._angles}
 
 
 def rotate_volume(volume, angles, mode="max", detector=None, fill=None, wc=50.0, ww=400.0, hu=False, level=True, batch=64,
-                  device=None):
+                  device=None, sampling="nearest", oversample=1):
     """The rotating projections of a volume that already exists, the counterpart of `project_volume`: int16 [N, H, W], a host
     array / CPU tensor (chunks of `batch` slices cross PCIe one after another) or a device tensor; angles: degrees, or an int
-    count of views around the full circle (`view_angles`).  Returns what `SeriesRotator.result` returns, of the input's kind."""
+    count of views around the full circle (`view_angles`); sampling and oversample as `SeriesRotator`.  Returns what
+    `SeriesRotator.result` returns, of the input's kind."""
     is_np = isinstance(volume, np.ndarray)
     vol = torch.from_numpy(np.ascontiguousarray(volume)) if is_np else volume
     if not torch.is_tensor(vol) or vol.dtype != torch.int16 or vol.dim() != 3:
@@ -374,7 +396,7 @@ def rotate_volume(volume, angles, mode="max", detector=None, fill=None, wc=50.0,
     on_host = not vol.is_cuda
     n, h, w = vol.shape
     rot = SeriesRotator(n, h, w, _angle_list(angles), mode=mode, detector=detector, fill=fill, wc=wc, ww=ww, hu=hu, level=level,
-                        device=device if on_host else vol.device)
+                        device=device if on_host else vol.device, sampling=sampling, oversample=oversample)
     with torch.cuda.device(rot.device):
         for s, e, _ in plan_chunks(n, batch):
             rot.update(vol[s:e].to(rot.device) if on_host else vol[s:e], s)
@@ -440,7 +462,8 @@ class SeriesTranslator:
     slices per axial slab, None: the whole volume) adds "projections": {axis: {"values": int16, "level": uint8 or None}} of
     the synthesized volume (`SeriesProjector`), in the translator's own window and `hu` (their level whatever `level` says).
     rotate = an int count of views around the full circle, or a sequence of degrees (rotate_mode: "max" / "min" / "mean", default
-    `project` or "max") adds "rotation": {"values": int16 [A, N, D], "level": uint8, "angles": float64 [A]} (`SeriesRotator`).
+    `project` or "max"; rotate_sampling "nearest" / "bilinear" and rotate_oversample = steps per voxel, as `SeriesRotator`) adds
+    "rotation": {"values": int16 [A, N, D], "level": uint8, "angles": float64 [A]}.
     subtract=True adds "sub" (int16 [N, H, W]: synthesized minus input, `ops.subtract_slices` with sub_median, sub_floor,
     sub_ct_range) and "sub_level" (uint8 in sub_window = (wc, ww) of a HU difference, None with level=False).
     project_source="sub" (needs subtract=True) projects and rotates the subtraction volume instead of the synthesized one, its
@@ -456,7 +479,7 @@ class SeriesTranslator:
 
     def __init__(self, generator, batch=16, size=None, wc=50.0, ww=400.0, hu=False, level=True, device=None, project=None,
                  slab=None, rotate=None, rotate_mode=None, subtract=False, sub_median=True, sub_floor=0, sub_ct_range=(None, None),
-                 sub_window=(150.0, 300.0), project_source="cta", slabs=None):
+                 sub_window=(150.0, 300.0), project_source="cta", slabs=None, rotate_sampling="nearest", rotate_oversample=1):
         if int(batch) < 1:
             raise ValueError("SeriesTranslator: batch >= 1 expected")
         if project_source not in PROJECT_SOURCES or (project_source == "sub" and not subtract):
@@ -474,6 +497,8 @@ class SeriesTranslator:
         if self.rotate is not None and (self.rotate_mode not in PROJECTIONS or not self.rotate):
             raise ValueError("SeriesTranslator: rotate needs at least one angle and a rotate_mode of %s, got %r"
                              % (PROJECTIONS, self.rotate_mode))
+        _check_sampling("SeriesTranslator", rotate_sampling, rotate_oversample)
+        self.rotate_sampling, self.rotate_oversample = rotate_sampling, int(rotate_oversample)
         self._rotator = self._rot_host = None
         self.slabs = None if slabs is None else dict(slabs)
         if self.slabs is not None and ("thick" not in self.slabs or set(self.slabs) - {"thick", "step", "mode", "axes"}):
@@ -709,7 +734,7 @@ class SeriesTranslator:
         if r is None or (r.n, r.h, r.w) != (n, h, w):
             wc, ww = self._view_window()
             r = self._rotator = SeriesRotator(n, h, w, self.rotate, mode=self.rotate_mode, wc=wc, ww=ww, hu=self._view_hu(),
-                                              device=self.device)
+                                              device=self.device, sampling=self.rotate_sampling, oversample=self.rotate_oversample)
         return r
 
     def _projector_for(self, n, h, w):

@@ -1752,6 +1752,7 @@ def project_finish(acc, mode, div=1, div_last=None, wc=50.0, ww=400.0, hu=False,
 
 # ---------------------------------------------------------------------------- rotating projections (csrc/project_rotate.hip)
 ROTATE_MAX_DIM = 4096      # H, W, U, T and the number of angles: each term of the 16.16 fixed-point sum stays below 2^28
+ROTATE_SAMPLINGS = {"nearest": "ctg_project_rotate", "bilinear": "ctg_project_rotate_bilinear"}      # sampling -> entry point
 
 
 class RotateTable:
@@ -1786,10 +1787,12 @@ def _rotate_out(t, dtype, name):
         raise RuntimeError("project_rotate: %s must be a contiguous %s tensor (A, N, U) on the GPU" % (name, dtype))
 
 
-def project_rotate(pix, n0, coef, t, mode, values=None, level=None, fill=None, wc=50.0, ww=400.0, hu=False):
+def project_rotate(pix, n0, coef, t, mode, values=None, level=None, fill=None, wc=50.0, ww=400.0, hu=False, sampling="nearest"):
     """One chunk of an int16 volume into its rotating projections, in place: pix (K, H, W) int16 on the GPU (a contiguous view is
     taken as it is: 2-byte alignment is enough) = slices n0 .. n0+K-1; coef: a `RotateTable`, or a host table (A, 6) that is
-    checked and uploaded by this call; t: unit steps per ray; mode 0 / "max", 1 / "min", 2 / "mean".  values int16 and level uint8
+    checked and uploaded by this call; t: steps per ray (of 1 / s voxel when the table was made with oversample = s); mode 0 /
+    "max", 1 / "min", 2 / "mean"; sampling "nearest" (the pixel a sample falls in) or "bilinear" (the four pixels around it, 8-bit
+    fractions, the edge replicated: ctg_project_rotate_bilinear), one table serving both.  values int16 and level uint8
     on the GPU, both (A, N, U), either None: the call writes rows n0 .. n0+K-1 of every plane and nothing else -- the reduction of
     each slice along the ray of every detector column (csrc/project_rotate.hip has the sampling rule), `fill` (default: air, 0 or
     -1024 with hu) where a ray misses the slice, and the 8-bit window level of that value.  Exact integer arithmetic: equal to
@@ -1800,6 +1803,9 @@ def project_rotate(pix, n0, coef, t, mode, values=None, level=None, fill=None, w
     if pix.dtype != torch.int16 or pix.dim() != 3:
         raise RuntimeError("project_rotate: pix must be int16 (K, H, W), got %s %s" % (pix.dtype, tuple(pix.shape)))
     code = _project_mode(mode, "project_rotate")
+    if sampling not in ROTATE_SAMPLINGS:
+        raise RuntimeError("project_rotate: sampling %r is not one of %s" % (sampling, tuple(ROTATE_SAMPLINGS)))
+    entry = ROTATE_SAMPLINGS[sampling]
     if values is None and level is None:
         raise RuntimeError("project_rotate: values, level or both expected")
     _rotate_out(values, torch.int16, "values")
@@ -1825,8 +1831,8 @@ def project_rotate(pix, n0, coef, t, mode, values=None, level=None, fill=None, w
         raise RuntimeError("project_rotate: H, W, U, T in 1 .. %d expected, got %d %d %d %d" % (ROTATE_MAX_DIM, h, w, u, t))
     if not -32768 <= fill <= 32767:
         raise RuntimeError("project_rotate: fill %d is not an int16 value" % fill)
-    _lib.check(lib.ctg_project_rotate(_p(x), k, h, w, n0, n, _p(table.dev), a, u, t, code, fill, float(wc), float(ww), int(hu),
-                                      _p(values), _p(level), _stream()), "ctg_project_rotate")
+    _lib.check(getattr(lib, entry)(_p(x), k, h, w, n0, n, _p(table.dev), a, u, t, code, fill, float(wc), float(ww), int(hu),
+                                   _p(values), _p(level), _stream()), entry)
 
 
 # ---------------------------------------------------------------------------- sliding thin slabs (csrc/project_slabs.hip)

@@ -438,6 +438,29 @@ int ctg_project_finish(const int* acc, int planes, long plane_items, int mode, i
 int ctg_project_rotate(const short* pix, int K, int H, int W, int n0, int N, const int* coef, int A, int U, int T, int mode,
                        int fill, float wc, float ww, int hu, short* values, unsigned char* level, void* stream);
 
+/* ---- series inference, rotating projections with bilinear sampling (added under ABI 15: purely additive, no existing signature
+ * or meaning moves, so the version stays 15): cta_gan_amd/infer.py: SeriesRotator(sampling="bilinear"), rotate_volume,
+ * SeriesTranslator(rotate_sampling="bilinear"); ops.project_rotate(sampling="bilinear").
+ * ctg_project_rotate_bilinear: the arguments, the checks, the table, the detector, the modes, `fill`, the level and the rows
+ *   written are those of ctg_project_rotate, and so is what counts: with X = c0 + c1 u + c2 t and Y = c3 + c4 u + c5 t (they
+ *   carry the + 0.5 of the nearest rule) sample (u, t) counts exactly when pixel (X >> 16, Y >> 16) lies in the slice, so a ray's
+ *   count and the place of `fill` do not depend on the sampling.  The value of a counted sample, all shifts arithmetic:
+ *       Xc = X - 32768            Yc = Y - 32768                    (the centre-based position, 16.16)
+ *       x0 = Xc >> 16             fx = (Xc >> 8) & 255              (x0 may be -1; a fraction of 8 bits)
+ *       y0 = Yc >> 16             fy = (Yc >> 8) & 255
+ *       xa = clamp(x0, 0, W-1)    xb = clamp(x0 + 1, 0, W-1)        (the edge pixel replicated)
+ *       ya = clamp(y0, 0, H-1)    yb = clamp(y0 + 1, 0, H-1)
+ *       top = p[ya][xa] (256 - fx) + p[ya][xb] fx        bot = p[yb][xa] (256 - fx) + p[yb][xb] fx
+ *       v   = (top (256 - fy) + bot fy + 32768) >> 16
+ *   The weights sum to 65536, so v is an int16 value; the sum before the shift lies in [-2^31 + 32768, 2^31 - 32768].  max and min
+ *   run over v, the mean is the int32 sum of v (at most 4096 samples) / the ray's count, truncating toward zero.  Memory-safe
+ *   whatever the table holds: the clamps keep the four addresses inside the slice, a sample that is not counted reads pixel 0.
+ * Oversampled rays, for either entry, are a matter of the table: t voxels in T = t s steps of 1 / s voxel have ct = (T - 1) / (2 s),
+ *   c2 = r(-sin / s), c5 = r(cos / s) and the other four as above (infer.py: rotation_coefficients(..., oversample=s)); T <= 4096.
+ *   Exact integer arithmetic up to the level: the same bits as numpy (tests/rotate_lerp_np.py). ---- */
+int ctg_project_rotate_bilinear(const short* pix, int K, int H, int W, int n0, int N, const int* coef, int A, int U, int T, int mode,
+                                int fill, float wc, float ww, int hu, short* values, unsigned char* level, void* stream);
+
 /* ---- series inference, the subtraction volume (added under ABI 15: purely additive, no existing signature or meaning moves, so
  * the version stays 15): synthesized CTA minus the CT it was made from, chunk by chunk behind ctg_export_slices
  * (cta_gan_amd/infer.py: SeriesTranslator(subtract=True), subtract_volume).  The generator writes on its input's pixel grid, so the

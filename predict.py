@@ -4,7 +4,8 @@
     python predict.py --config Yaml/HdGan.yaml --weights netG_A2B.pth --input series.npy --output out.npy
                       [--level-dir DIR] [--hu] [--wc 50 --ww 400] [--batch 16] [--dtype bf16x3]
                       [--mip-dir DIR [--mip-mode max|min|mean] [--slab K] [--aspect R]]
-                      [--rot-dir DIR [--rot-angles 36] [--rot-span 360] [--mip-mode max|min|mean] [--aspect R]]
+                      [--rot-dir DIR [--rot-angles 36] [--rot-span 360] [--rot-sampling nearest|bilinear] [--rot-oversample S]
+                       [--mip-mode max|min|mean] [--aspect R]]
                       [--sts-dir DIR --sts-thick T[,Tc,Ts] [--sts-step S[,Sc,Ss]] [--sts-axes axial,coronal,sagittal]
                        [--mip-mode max|min|mean] [--aspect R]]
                       [--sub-output sub.npy [--sub-level-dir DIR] [--sub-floor 0] [--sub-no-median] [--sub-ct-min HU]
@@ -22,7 +23,9 @@ spacing / pixel spacing draws the coronal and sagittal PNGs with round(N R) rows
 --rot-dir: the rotating projection of the synthesized volume, --rot-angles views over --rot-span degrees about the cranio-caudal
 axis (0 = coronal, 90 = sagittal; --mip-mode, --wc / --ww, --hu and --aspect as above), made on the device while the volume is
 made: rot_%03d.png, one 8-bit frame [round(N R), D] per angle with D = ceil(hypot(H, W)), and rotation.npz with values (int16
-[A, N, D]), level (uint8) and angles (degrees).
+[A, N, D]), level (uint8) and angles (degrees).  --rot-sampling bilinear interpolates the four pixels around every sample of a
+ray instead of taking the nearest one, and --rot-oversample S takes S steps per voxel (with either sampling): a one-pixel vessel
+that nearest sampling at unit steps steps over at some angles is seen at every angle by bilinear, at nearly every one by S = 2.
 --sts-dir: the sliding thin-slab projections of the synthesized volume, the mode a CTA is read in: slabs of --sts-thick voxels
 moved on by --sts-step voxels (default: the thickness, slabs that do not overlap; 1 <= step <= thick) along the --sts-axes.  One
 number serves every axis, three (axial, coronal, sagittal) give each axis its own: slice spacing and pixel spacing differ.
@@ -61,6 +64,8 @@ def build_parser():
     parser.add_argument("--rot-dir", type=str, default=None, help="also write the rotating projection of the synthesized volume here")
     parser.add_argument("--rot-angles", type=int, default=36, help="view angles of the rotating projection (with --rot-dir)")
     parser.add_argument("--rot-span", type=float, default=360.0, help="degrees the view angles are spread over (with --rot-dir)")
+    parser.add_argument("--rot-sampling", choices=["nearest", "bilinear"], default="nearest", help="how a ray samples the slice (with --rot-dir)")
+    parser.add_argument("--rot-oversample", type=int, default=1, help="steps per voxel along a ray (with --rot-dir)")
     parser.add_argument("--sts-dir", type=str, default=None, help="also write the sliding thin-slab projections here")
     parser.add_argument("--sts-thick", type=str, default=None, help="voxels per slab: T, or T,Tc,Ts for axial,coronal,sagittal")
     parser.add_argument("--sts-step", type=str, default=None, help="voxels a slab moves on: S or S,Sc,Ss (default: the thickness)")
@@ -131,6 +136,8 @@ def main(argv=None):
         raise SystemExit("--aspect: a positive ratio expected")
     if opts.rot_dir is not None and opts.rot_angles < 1:
         raise SystemExit("--rot-angles: at least one view angle expected")
+    if opts.rot_oversample < 1:
+        raise SystemExit("--rot-oversample: at least one step per voxel expected")
     import numpy as np
     import torch
     import yaml
@@ -157,7 +164,8 @@ def main(argv=None):
                                  project_source=opts.mip_source,
                                  project=opts.mip_mode if opts.mip_dir is not None else None, slab=opts.slab,
                                  rotate=view_angles(opts.rot_angles, opts.rot_span) if opts.rot_dir is not None else None,
-                                 rotate_mode=opts.mip_mode, slabs=opts.sts)
+                                 rotate_mode=opts.mip_mode, rotate_sampling=opts.rot_sampling, rotate_oversample=opts.rot_oversample,
+                                 slabs=opts.sts)
     out = translate(volume)
     np.save(opts.output, out["pix"])
     if opts.level_dir is not None:

@@ -2,12 +2,15 @@
 
     python scripts/rotate_bench.py kernel      # one ctg_project_rotate launch vs the stock-torch composition, same tensors
     python scripts/rotate_bench.py series      # SeriesTranslator on a 256-slice 512 x 512 volume, rotate=36 against rotate=None
+    ... [--sampling nearest|bilinear] [--oversample S] [--reps N]      # the rays of either leg (default: nearest, unit steps)
 
 `kernel`: a chunk of 16 x 512 x 512 int16, A = 36 view angles, D = 725, max, values and level.  The composition gathers
 `vol[:, yi, xi]` by the same integer tables (precomputed on the device, outside the timed window, as one linear index and one
 mask per angle), masks, takes `amax` over the ray and fills the empty rays: the values only, bit-equal (checked first); it
-materialises a [K, U, T] tensor per angle.  Device events around back-to-back calls, alternating the two.  `series`: batch 16,
+materialises a [K, U, T] tensor per angle.  Device events around back-to-back calls, alternating the two.  With --sampling
+bilinear there is no composition to compare with: the launch is timed alone.  `series`: batch 16,
 bf16, host volume in pageable memory, the two translators alternating inside every round.  Both print the build digest."""
+import argparse
 import os
 import sys
 import time
@@ -21,20 +24,21 @@ def _digest():
     return build._digest()[:16]
 
 
-def kernel(reps=50, torch_reps=3, rounds=5, k=16, s=512, count=36):
+def kernel(reps=50, torch_reps=3, rounds=5, k=16, s=512, count=36, sampling="nearest", oversample=1):
     from cta_gan_amd import ops
     from cta_gan_amd.infer import default_detector, rotation_coefficients, view_angles
     d = default_detector(s, s)
+    steps = d * oversample
     angles = view_angles(count)
-    coef = [rotation_coefficients(a, s, s) for a in angles]
+    coef = [rotation_coefficients(a, s, s, oversample=oversample) for a in angles]
     table = ops.RotateTable(coef)
     vol = torch.randint(0, 4096, (k, s, s), generator=torch.Generator().manual_seed(0), dtype=torch.int16).cuda()
     values = torch.empty((count, k, d), dtype=torch.int16, device="cuda")
     level = torch.empty((count, k, d), dtype=torch.uint8, device="cuda")
     u = torch.arange(d, dtype=torch.int64, device="cuda")[:, None]
-    t = torch.arange(d, dtype=torch.int64, device="cuda")[None, :]
+    t = torch.arange(steps, dtype=torch.int64, device="cuda")[None, :]
     index = []
-    for c in coef:
+    for c in coef if sampling == "nearest" else ():
         xi, yi = (c[0] + c[1] * u + c[2] * t) >> 16, (c[3] + c[4] * u + c[5] * t) >> 16
         ok = (xi >= 0) & (xi < s) & (yi >= 0) & (yi < s)
         index.append((torch.where(ok, yi * s + xi, 0).reshape(-1), ok[None], ok.any(dim=1)[None]))
@@ -43,18 +47,21 @@ def kernel(reps=50, torch_reps=3, rounds=5, k=16, s=512, count=36):
     air = torch.tensor(0, dtype=torch.int16, device="cuda")
 
     def fused():
-        ops.project_rotate(vol, 0, table, d, "max", values=values, level=level)
+        ops.project_rotate(vol, 0, table, steps, "max", values=values, level=level, sampling=sampling)
         return values
 
     def composed():
         out = []
         for lin, ok, seen in index:
-            g = flat.index_select(1, lin).view(k, d, d)
+            g = flat.index_select(1, lin).view(k, d, steps)
             out.append(torch.where(seen, torch.where(ok, g, lowest).amax(dim=2), air))
         return torch.stack(out)
 
-    print("same values: %s" % torch.equal(fused(), composed()), flush=True)
-    fns = (("project_rotate (1 launch)", fused, reps), ("torch composition", composed, torch_reps))
+    print("sampling %s, %d step(s) per voxel: %d steps per ray" % (sampling, oversample, steps), flush=True)
+    fns = (("project_rotate (1 launch)", fused, reps),)
+    if sampling == "nearest":
+        print("same values: %s" % torch.equal(fused(), composed()), flush=True)
+        fns += (("torch composition", composed, torch_reps),)
     for _, fn, _ in fns:
         for _ in range(3):
             fn()
@@ -71,13 +78,15 @@ def kernel(reps=50, torch_reps=3, rounds=5, k=16, s=512, count=36):
             times[name].append(e0.elapsed_time(e1) * 1e3 / n)
     for name, v in times.items():
         print("%-28s us per call, %d windows: %s" % (name, rounds, " ".join("%.1f" % x for x in v)), flush=True)
-    best, other = min(times["project_rotate (1 launch)"]), min(times["torch composition"])
-    samples = count * k * d * d
-    print("project_rotate: %.1f us best window, %.1f G samples/s over %d samples; torch composition %.1f us: %.1f x"
-          % (best, samples / best / 1e3, samples, other, other / best), flush=True)
+    best = min(times["project_rotate (1 launch)"])
+    samples = count * k * d * steps
+    print("project_rotate: %.1f us best window, %.1f G samples/s over %d samples" % (best, samples / best / 1e3, samples), flush=True)
+    if sampling == "nearest":
+        other = min(times["torch composition"])
+        print("torch composition %.1f us: %.1f x" % (other, other / best), flush=True)
 
 
-def series(n=256, s=512, batch=16, rounds=4, count=36):
+def series(n=256, s=512, batch=16, rounds=4, count=36, sampling="nearest", oversample=1):
     import numpy as np
     from cta_gan_amd import nets, synth
     from cta_gan_amd.Model.HdGan import Generator
@@ -85,7 +94,9 @@ def series(n=256, s=512, batch=16, rounds=4, count=36):
     vol = np.random.RandomState(0).randint(-1100, 3000, size=(n, s, s)).astype(np.int16)
     nets.set_default_compute_dtype(torch.bfloat16)
     g = synth.fill_module(Generator(1, 1), seed=0).cuda()
-    legs = (("rotate=None", SeriesTranslator(g, batch=batch)), ("rotate=%d" % count, SeriesTranslator(g, batch=batch, rotate=count)))
+    print("sampling %s, %d step(s) per voxel" % (sampling, oversample), flush=True)
+    legs = (("rotate=None", SeriesTranslator(g, batch=batch)),
+            ("rotate=%d" % count, SeriesTranslator(g, batch=batch, rotate=count, rotate_sampling=sampling, rotate_oversample=oversample)))
     for _, tr in legs:
         tr(vol[:2 * batch])
     torch.cuda.synchronize()
@@ -106,5 +117,14 @@ def series(n=256, s=512, batch=16, rounds=4, count=36):
 
 
 if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("leg", choices=["kernel", "series"])
+    ap.add_argument("--sampling", choices=["nearest", "bilinear"], default="nearest")
+    ap.add_argument("--oversample", type=int, default=1)
+    ap.add_argument("--reps", type=int, default=None, help="kernel: calls per timed window (default 50)")
+    o = ap.parse_args()
     print("build digest", _digest(), flush=True)
-    {"kernel": kernel, "series": series}[sys.argv[1]]()
+    if o.leg == "kernel":
+        kernel(sampling=o.sampling, oversample=o.oversample, **({} if o.reps is None else {"reps": o.reps}))
+    else:
+        series(sampling=o.sampling, oversample=o.oversample)

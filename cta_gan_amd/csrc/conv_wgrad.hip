@@ -339,6 +339,119 @@ typedef const __attribute__((address_space(1))) void* wg_gptr_t;
 typedef __attribute__((address_space(3))) void* wg_lptr_t;
 __device__ __attribute__((aligned(16))) unsigned g_wg_zero_chunk[4];
 
+// ---- tile loads of the halo-resident kernels ---------------------------------------------------------------------------
+// A thread's LDS-DMA slots never change over a launch: slot `it` of thread `tid` is 16-byte chunk tid + 256 it of the tile,
+// i.e. always the same (tile row, tile column, swizzled channel chunk); only the tile origin moves.  Both loaders therefore
+//   * derive slot 0's (row, column, chunk) from the thread id with constant divisors and every further slot from the slot
+//     before it (256 chunks = a compile-time (rows, columns) step with one wrap compare): no run-time division, trip counts
+//     and the "does this wave own the slot" test are compile-time for every slot but the last;
+//   * take a workgroup-uniform test per tile: a tile that lies wholly inside the image (84 of the 128 tiles of a 128^2 sample)
+//     needs no reflection, no bounds compare, no zero chunk -- its sources are a scalar tile base plus a 32-bit lane offset
+//     (the host guarantees 32-bit offsets inside a sample); border and ragged tiles keep the per-slot reflection / zero padding
+//     and fetch the same bytes as ever;
+//   * rebuild that geometry per tile from the thread id (a handful of straight-line VALU) instead of holding per-slot offsets
+//     across the MFMA phase: the empty asm statement makes the id opaque, so the compiler cannot hoist the offsets into
+//     registers that live across the tile loop (that form spilled at 64 x 64 channels and cost occupancy at 32 x 32).
+// `wave` must be wave-uniform to the compiler (readfirstlane): the LDS destination then stays scalar and goes to m0 directly.
+__device__ __forceinline__ void wg_dma16(const void* src, char* dst) {
+    __builtin_amdgcn_global_load_lds((wg_gptr_t)src, (wg_lptr_t)dst, 16, 0, 0);
+}
+
+// G tile: WGH_TH x WGH_TW pixels x CPM chunks at tile origin (y0, x0); G = the sample's plane at channel m0
+template <int CPM>
+__device__ __forceinline__ void wg_issue_g(const bf16_t* __restrict__ G, char* bG, int tid, int wave, int y0, int x0,
+                                           int Hs, int Ws, int g_ld) {
+    constexpr int G_IT = WGH_TH * WGH_TW * CPM / 256;
+    constexpr int RSTEP = 256 / CPM / WGH_TW;          // slot it is the same pixel RSTEP * it tile rows further down
+    static_assert(G_IT >= 1 && RSTEP * G_IT == WGH_TH && (256 / CPM) % 8 == 0, "the swizzle key repeats from slot to slot");
+    unsigned t = (unsigned)tid;
+    asm volatile("" : "+v"(t));
+    const int p = (int)(t / CPM), c = (int)(t % CPM);
+    const int kc = wg_swz<CPM>(p, c);
+    const int py = p / WGH_TW, px = p % WGH_TW;
+    if (y0 + WGH_TH <= Hs && x0 + WGH_TW <= Ws) {
+        const char* base = (const char*)(G + (size_t)(y0 * Ws + x0) * g_ld);
+        const unsigned off = (unsigned)((py * Ws + px) * g_ld + kc * 8) * 2u;
+        const size_t step = (size_t)(RSTEP * Ws) * g_ld * 2;
+#pragma unroll
+        for (int it = 0; it < G_IT; ++it) wg_dma16(base + it * step + off, bG + (256 * it + 64 * wave) * 16);
+    } else {
+        const int ox = x0 + px;
+#pragma unroll
+        for (int it = 0; it < G_IT; ++it) {
+            const int oy = y0 + py + RSTEP * it;
+            const bool ok = oy < Hs && ox < Ws;
+            const bf16_t* src = ok ? G + ((size_t)(oy * Ws + ox) * g_ld + kc * 8) : (const bf16_t*)g_wg_zero_chunk;
+            wg_dma16(src, bG + (256 * it + 64 * wave) * 16);
+        }
+    }
+}
+
+// X halo tile: (WGH_TH + KH - 1) x (WGH_TW + KW - 1) halo pixels x CPN chunks (swizzled by the halo COLUMN: see the fragment
+// reads); halo pixel (hy, hx) is image pixel (iy0 + IS hy, ix0 + IS hx) of X = the sample's plane at channel n0.  The slots
+// behind the last halo pixel (the tile is rounded up to whole waves) are read by no fragment: any in-bounds source serves.
+template <int CPN, int KH, int KW>
+__device__ __forceinline__ void wg_issue_x(const bf16_t* __restrict__ X, char* bX, int tid, int wave, int iy0, int ix0, int IS,
+                                           int Hi, int Wi, int x_ld, int pad_mode) {
+    constexpr int HPW = WGH_TW + KW - 1, HPH = WGH_TH + KH - 1, NPX = HPH * HPW;
+    constexpr int X_CH = NPX * CPN, X_CH64 = (X_CH + 63) & ~63, X_IT = (X_CH64 + 255) / 256;
+    constexpr int D = 256 / CPN, DR = D / HPW, DC = D % HPW;      // halo pixels / rows / columns from one slot to the next
+    unsigned t = (unsigned)tid;
+    asm volatile("" : "+v"(t));
+    const int hrow0 = (int)(t / CPN), c = (int)(t % CPN);
+    int hy = hrow0 / HPW, hx = hrow0 - hy * HPW;
+    if (iy0 >= 0 && ix0 >= 0 && iy0 + (HPH - 1) * IS < Hi && ix0 + (HPW - 1) * IS < Wi) {
+        const char* base = (const char*)(X + ((size_t)iy0 * Wi + ix0) * x_ld);
+        const unsigned colB = (unsigned)(IS * x_ld) * 2u, rowB = colB * (unsigned)Wi;
+        const unsigned stepA = DR * rowB + DC * colB, stepW = stepA + rowB - HPW * colB;
+        unsigned voff = (unsigned)hy * rowB + (unsigned)hx * colB;
+        static_for<X_IT>([&](auto ic) __attribute__((always_inline)) {
+            constexpr int it = decltype(ic)::value;
+            if constexpr (it > 0) {
+                if constexpr (DC != 0) {
+                    hx += DC;
+                    const bool w = hx >= HPW;
+                    hx = w ? hx - HPW : hx;
+                    voff += w ? stepW : stepA;
+                } else {
+                    voff += stepA;
+                }
+            }
+            if (256 * (it + 1) <= X_CH64 || 256 * it + 64 * wave < X_CH64) {
+                unsigned off = voff + (unsigned)wg_swz<CPN>(hx, c) * 16u;
+                if constexpr (256 * (it + 1) > X_CH)
+                    if (hrow0 + it * D >= NPX) off = (unsigned)c * 16u;
+                wg_dma16(base + off, bX + (256 * it + 64 * wave) * 16);
+            }
+        });
+    } else {
+        static_for<X_IT>([&](auto ic) __attribute__((always_inline)) {
+            constexpr int it = decltype(ic)::value;
+            if constexpr (it > 0) {
+                hy += DR;
+                if constexpr (DC != 0) {
+                    hx += DC;
+                    const bool w = hx >= HPW;
+                    hx = w ? hx - HPW : hx;
+                    hy = w ? hy + 1 : hy;
+                }
+            }
+            if (256 * (it + 1) <= X_CH64 || 256 * it + 64 * wave < X_CH64) {
+                const int kc = wg_swz<CPN>(hx, c);
+                int iy = iy0 + hy * IS, ix = ix0 + hx * IS;
+                if (pad_mode == PAD_REFLECT) {
+                    iy = reflect_idx(iy, Hi);
+                    ix = reflect_idx(ix, Wi);
+                }
+                bool ok = ((unsigned)iy < (unsigned)Hi) && ((unsigned)ix < (unsigned)Wi);
+                if constexpr (256 * (it + 1) > X_CH) ok = ok && hrow0 + it * D < NPX;
+                const bf16_t* src = ok ? X + ((size_t)(iy * Wi + ix) * x_ld + kc * 8) : (const bf16_t*)g_wg_zero_chunk;
+                wg_dma16(src, bX + (256 * it + 64 * wave) * 16);
+            }
+        });
+    }
+}
+
 // WN4 = 1: the four waves split the ci-tile 1 x 4 (each wave: all BM co x BN/4 ci), so every X fragment a wave
 // reads feeds BM/16 MFMAs instead of BM/32: fewer LDS bytes per MFMA at the same accumulator budget.
 template <int BM, int BN, int NT, int WN4, int KW>
@@ -367,20 +480,20 @@ __global__ __launch_bounds__(256, (NT > 16 ? 1 : 2)) void conv_wgrad_halo_kernel
     int ph0 = 0;
     if (a.phase_split) { ph0 = z % 3; z /= 3; }
     const int n = z / a.sps, part_i = z - n * a.sps;
-    const int HPW = WGH_TW + a.kw - 1, HPH = WGH_TH + a.khb - 1;
-    const int X_CH = HPH * HPW * CPN;
-    const int X_CH64 = (X_CH + 63) & ~63;
+    // the halo geometry is compile-time: the launcher refuses an a.khb / a.kw other than NT / KW, KW
+    constexpr int HPW = WGH_TW + KW - 1, HPH = WGH_TH + NT / KW - 1;
+    constexpr int X_CH = HPH * HPW * CPN;
+    constexpr int X_CH64 = (X_CH + 63) & ~63;
+    const int wave_s = __builtin_amdgcn_readfirstlane(wave);   // scalar copy for the LDS-DMA destinations
     const int tx_n = (a.Ws + WGH_TW - 1) / WGH_TW, ty_n = (a.Hs + WGH_TH - 1) / WGH_TH;
     const int ntile = tx_n * ty_n;
     const int per = (ntile + a.sps - 1) / a.sps;
     const int t_beg = part_i * per, t_end = min(t_beg + per, ntile);
     const T* __restrict__ G0 = (const T*)a.g + (size_t)n * a.Hs * a.Ws * a.g_ld + m0;
     const T* __restrict__ X0 = (const T*)a.x + (size_t)n * a.Hi * a.Wi * a.x_ld + n0;
-    const unsigned hpw_magic = (unsigned)((0x100000000ULL + HPW - 1) / HPW);
     const int Hs = a.Hs, Ws = a.Ws, Hi = a.Hi, Wi = a.Wi, g_ld = a.g_ld, x_ld = a.x_ld, pad_mode = a.pad_mode;
-    const int dy_g = a.dy0 + tg * a.khb, dx_g = a.dx0;
+    const int dy_g = a.dy0 + tg * (NT / KW), dx_g = a.dx0;
     const int IS = a.is;
-    const int x_it = (X_CH64 + 255) / 256;
 
     f32x4 acc[NT][TM][TN];
 #pragma unroll
@@ -415,74 +528,53 @@ __global__ __launch_bounds__(256, (NT > 16 ? 1 : 2)) void conv_wgrad_halo_kernel
 
     // LDS holds TWO (G tile, X halo) pairs: the loads of tile t+1 are issued before the MFMAs of tile t and are
     // drained by the single __syncthreads() that ends the tile (one barrier per tile, loads fully overlapped).
-    const int pair_bytes = (G_CH + X_CH64) * 16;
+    constexpr int pair_bytes = (G_CH + X_CH64) * 16;
     const int NPH = a.phase_split ? 1 : a.phases;
-    auto issue_G = [&](int tile, char* bG, bool lo) __attribute__((always_inline)) {
-        const int y0 = (tile / tx_n) * WGH_TH, x0 = (tile % tx_n) * WGH_TW;
-        const T* __restrict__ G = G0 + (lo ? a.g_lo : 0);
-        // ---- G tile: slot s -> (pixel p, chunk)
-#pragma unroll
-        for (int it = 0; it < G_CH / 256; ++it) {
-            const int sl = tid + 256 * it;
-            const int p = sl / CPM;
-            const int kc = wg_swz<CPM>(p, sl % CPM);
-            const int oy = y0 + p / WGH_TW, ox = x0 + p % WGH_TW;
-            const bool ok = oy < Hs && ox < Ws;
-            const T* src = ok ? G + ((size_t)(oy * Ws + ox) * g_ld + kc * 8) : (const T*)g_wg_zero_chunk;
-            __builtin_amdgcn_global_load_lds((wg_gptr_t)src, (wg_lptr_t)(bG + (256 * it + 64 * wave) * 16), 16, 0, 0);
-        }
+    // the tile loads take the tile ORIGIN (y0, x0): the run carries it along (no division by tx_n per tile)
+    auto issue_G = [&](int y0, int x0, char* bG, bool lo) __attribute__((always_inline)) {
+        wg_issue_g<CPM>(G0 + (lo ? a.g_lo : 0), bG, tid, wave_s, y0, x0, Hs, Ws, g_ld);
     };
-    auto issue_X = [&](int tile, char* bX, bool lo) __attribute__((always_inline)) {
-        const int y0 = (tile / tx_n) * WGH_TH, x0 = (tile % tx_n) * WGH_TW;
-        const T* __restrict__ X = X0 + (lo ? a.x_lo : 0);
-        // ---- X halo tile
-        for (int it = 0; it < x_it; ++it) {
-            if (256 * it + 64 * wave < X_CH64) {
-                const int sl = tid + 256 * it;
-                const int hrow = sl / CPN;
-                const int hy = (int)__umulhi((unsigned)hrow, hpw_magic), hx = hrow - hy * HPW;
-                const int kc = wg_swz<CPN>(hx, sl % CPN);   // swizzled by the halo COLUMN: see the fragment reads
-                int iy = (y0 + dy_g + hy) * IS + a.py, ix = (x0 + dx_g + hx) * IS + a.px;
-                if (pad_mode == PAD_REFLECT) {
-                    iy = reflect_idx(iy, Hi);
-                    ix = reflect_idx(ix, Wi);
-                }
-                const bool ok = sl < X_CH && ((unsigned)iy < (unsigned)Hi) && ((unsigned)ix < (unsigned)Wi);
-                const T* src = ok ? X + ((size_t)(iy * Wi + ix) * x_ld + kc * 8) : (const T*)g_wg_zero_chunk;
-                __builtin_amdgcn_global_load_lds((wg_gptr_t)src, (wg_lptr_t)(bX + (256 * it + 64 * wave) * 16), 16, 0, 0);
-            }
-        }
+    auto issue_X = [&](int y0, int x0, char* bX, bool lo) __attribute__((always_inline)) {
+        wg_issue_x<CPN, NT / KW, KW>(X0 + (lo ? a.x_lo : 0), bX, tid, wave_s, (y0 + dy_g) * IS + a.py, (x0 + dx_g) * IS + a.px, IS,
+                                     Hi, Wi, x_ld, pad_mode);
     };
-    auto issue_tile = [&](int tile, int buf, int ph) __attribute__((always_inline)) {
+    auto issue_tile = [&](int y0, int x0, int buf, int ph) __attribute__((always_inline)) {
         char* bG = smem + buf * pair_bytes;
-        issue_G(tile, bG, ph + ph0 == 2);
-        issue_X(tile, bG + G_CH * 16, ph + ph0 == 1);
+        issue_G(y0, x0, bG, ph + ph0 == 2);
+        issue_X(y0, x0, bG + G_CH * 16, ph + ph0 == 1);
     };
     // Three sweeps in one workgroup (split pair, prefetching): each of the four planes has ITS buffer -- G0 <- g_lo, X0 <- x_hi,
     // G1 <- g_hi, X1 <- x_lo -- and the sweeps run (g_lo, x_hi), (g_hi, x_hi), (g_hi, x_lo): x_hi and g_hi are fetched ONCE per
     // pixel tile instead of twice (four tile loads instead of six; the loads of a step land in a buffer no sweep is reading).
     const bool reuse = NPH == 3 && a.prefetch && !a.no_reuse;
     char* const G0b = smem, * const X0b = smem + G_CH * 16, * const G1b = smem + pair_bytes, * const X1b = G1b + G_CH * 16;
+    int cy = (t_beg / tx_n) * WGH_TH, cx = (t_beg % tx_n) * WGH_TW;   // origin of the current tile, carried along the run
+    const int x_end = tx_n * WGH_TW;
     if (t_beg < t_end) {
-        if (reuse) { issue_G(t_beg, G0b, true); issue_X(t_beg, X0b, false); }
-        else issue_tile(t_beg, 0, 0);
+        if (reuse) { issue_G(cy, cx, G0b, true); issue_X(cy, cx, X0b, false); }
+        else issue_tile(cy, cx, 0, 0);
     }
     __syncthreads();
     int tile = t_beg, ph = 0;
     for (int u = 0; tile < t_end; ++u) {
         int tile_n = tile, ph_n = ph + 1;          // the step after this one
-        if (ph_n == NPH) { ph_n = 0; ++tile_n; }
+        int ny = cy, nx = cx;                      // ... and its tile origin
+        if (ph_n == NPH) {
+            ph_n = 0; ++tile_n;
+            nx += WGH_TW;
+            if (nx >= x_end) { nx = 0; ny += WGH_TH; }
+        }
         const int cur = a.prefetch ? u & 1 : 0;
         const char* sG = smem + cur * pair_bytes;
         const char* sX = sG + G_CH * 16;
         if (reuse) {
-            if (ph == 0) issue_G(tile, G1b, false);
-            else if (ph == 1) issue_X(tile, X1b, true);
-            else if (tile_n < t_end) { issue_G(tile_n, G0b, true); issue_X(tile_n, X0b, false); }
+            if (ph == 0) issue_G(cy, cx, G1b, false);
+            else if (ph == 1) issue_X(cy, cx, X1b, true);
+            else if (tile_n < t_end) { issue_G(ny, nx, G0b, true); issue_X(ny, nx, X0b, false); }
             sG = ph == 0 ? G0b : G1b;
             sX = ph == 2 ? X1b : X0b;
         } else if (a.prefetch && tile_n < t_end) {
-            issue_tile(tile_n, cur ^ 1, ph_n);
+            issue_tile(ny, nx, cur ^ 1, ph_n);
         }
         // ---- 4 k-steps of 32 pixels (= two 16-pixel tile rows); the K order inside a step is the same for A and B.
         // Fully unrolled: every fragment address is a per-tile base register (G: one per co-tile; X: one per tap COLUMN
@@ -566,27 +658,29 @@ __global__ __launch_bounds__(256, (NT > 16 ? 1 : 2)) void conv_wgrad_halo_kernel
         });
         __syncthreads();   // next tile landed (vmcnt(0)) and every wave is done with this one
         if (!a.prefetch && tile_n < t_end) {
-            issue_tile(tile_n, 0, ph_n);
+            issue_tile(ny, nx, 0, ph_n);
             __syncthreads();
         }
         tile = tile_n;
         ph = ph_n;
+        cy = ny;
+        cx = nx;
     }
 
+    // partial store: one base per thread (its first accumulator row and column); tap slot, co-tile, row and ci-tile are
+    // wave-uniform steps from it
+    const size_t tap_sz = (size_t)a.Mc * a.Nc;
+    float* __restrict__ const out0 = a.part + (size_t)z_out * a.gtaps * tap_sz +
+                                     (size_t)(m0 + wm * TM * 16 + (lane >> 4) * 4) * a.Nc + (n0 + wn * TN * 16 + (lane & 15));
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
-        float* __restrict__ out = a.part + ((size_t)z_out * a.gtaps + a.tmap[tg * NT + t]) * a.Mc * a.Nc;
+        float* __restrict__ out = out0 + a.tmap[tg * NT + t] * tap_sz;
 #pragma unroll
         for (int mt = 0; mt < TM; ++mt)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int m = m0 + (wm * TM + mt) * 16 + (lane >> 4) * 4 + r;
+            for (int r = 0; r < 4; ++r)
 #pragma unroll
-                for (int nt = 0; nt < TN; ++nt) {
-                    const int c = n0 + (wn * TN + nt) * 16 + (lane & 15);
-                    out[(size_t)m * a.Nc + c] = acc[t][mt][nt][r];
-                }
-            }
+                for (int nt = 0; nt < TN; ++nt) out[(size_t)((mt * 16 + r) * a.Nc) + nt * 16] = acc[t][mt][nt][r];
     }
 }
 
@@ -595,6 +689,7 @@ static int launch_wgh(const WgHaloArgs& a, hipStream_t st) {
     const int hp = (WGH_TH + a.khb - 1) * (WGH_TW + a.kw - 1);
     const int pair = (WGH_TH * WGH_TW * (BM / 8) + ((hp * (BN / 8) + 63) & ~63)) * 16;
     if (pair > 80 * 1024 || hp >= 65536) return -1;
+    if (a.kw != KW || a.khb * KW != NT) return -1;   // the kernel's halo geometry is compile-time: (NT / KW) x KW taps per workgroup
     WgHaloArgs b = a;
     if (2 * pair > 80 * 1024) b.prefetch = 0;       // one (G, X-halo) pair fits, two do not: no prefetch
     const int smem = 2 * pair > 80 * 1024 ? pair + 16 : 2 * pair;
@@ -729,7 +824,6 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_s2m_kernel(const WgHaloArgs
     constexpr int G_CH = WGH_TH * WGH_TW * CPM;
     constexpr int HPW = WGH_TW + 1, HPH = WGH_TH + 1;
     constexpr int X_CH = HPH * HPW * CPN, X_CH64 = (X_CH + 63) & ~63;
-    constexpr int X_IT = (X_CH64 + 255) / 256;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wn = wave;
@@ -749,8 +843,8 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_s2m_kernel(const WgHaloArgs
     const int t_beg = part_i * per, t_end = min(t_beg + per, ntile);
     const T* __restrict__ G0p = (const T*)a.g + (size_t)n * a.Hs * a.Ws * a.g_ld + m0;
     const T* __restrict__ X0p = (const T*)a.x + (size_t)n * a.Hi * a.Wi * a.x_ld + n0;
-    constexpr unsigned hpw_magic = (unsigned)((0x100000000ULL + HPW - 1) / HPW);
     const int Hs = a.Hs, Ws = a.Ws, Hi = a.Hi, Wi = a.Wi, g_ld = a.g_ld, x_ld = a.x_ld;
+    const int wave_s = __builtin_amdgcn_readfirstlane(wave);   // scalar copy for the LDS-DMA destinations
 
     f32x4 acc[9][TM][TN];
 #pragma unroll
@@ -777,37 +871,21 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_s2m_kernel(const WgHaloArgs
             xoffc[tx][nt] = (hx * CPN + wg_swz<CPN>(hx, cidx)) * 16 + 8 * (psel & 1);
         }
 
-    auto issue_G = [&](int tile, char* bG, bool lo) __attribute__((always_inline)) {
-        const int y0 = (tile / tx_n) * WGH_TH, x0 = (tile % tx_n) * WGH_TW;
-        const T* __restrict__ G = G0p + (lo ? a.g_lo : 0);
-#pragma unroll 1
-        for (int it = 0; it < G_CH / 256; ++it) {
-            const int sl = tid + 256 * it;
-            const int p = sl / CPM;
-            const int kc = wg_swz<CPM>(p, sl % CPM);
-            const int oy = y0 + p / WGH_TW, ox = x0 + p % WGH_TW;
-            const bool ok = oy < Hs && ox < Ws;
-            const T* src = ok ? G + ((size_t)(oy * Ws + ox) * g_ld + kc * 8) : (const T*)g_wg_zero_chunk;
-            __builtin_amdgcn_global_load_lds((wg_gptr_t)src, (wg_lptr_t)(bG + (256 * it + 64 * wave) * 16), 16, 0, 0);
-        }
+    // the loaders of conv_wgrad_halo_kernel with its stride-2 geometry: halo pixel (hy, hx) of polyphase component (py, px) behind
+    // window origin (-1, -1) of the tile at (y0, x0) is image pixel (2 (y0 - 1 + hy) + py, 2 (x0 - 1 + hx) + px); zero padding
+    auto issue_G = [&](int y0, int x0, char* bG, bool lo) __attribute__((always_inline)) {
+        wg_issue_g<CPM>(G0p + (lo ? a.g_lo : 0), bG, tid, wave_s, y0, x0, Hs, Ws, g_ld);
     };
-    // the (8 + 1) x (16 + 1) pixels of polyphase component (py, px) of X behind window origin (-1, -1)
-    auto issue_X = [&](int tile, char* bX, bool lo, int py, int px) __attribute__((always_inline)) {
-        const int y0 = (tile / tx_n) * WGH_TH, x0 = (tile % tx_n) * WGH_TW;
-        const T* __restrict__ X = X0p + (lo ? a.x_lo : 0);
-#pragma unroll 1
-        for (int it = 0; it < X_IT; ++it) {
-            if (256 * it + 64 * wave < X_CH64) {
-                const int sl = tid + 256 * it;
-                const int hrow = sl / CPN;
-                const int hy = (int)__umulhi((unsigned)hrow, hpw_magic), hx = hrow - hy * HPW;
-                const int kc = wg_swz<CPN>(hx, sl % CPN);
-                const int iy = (y0 - 1 + hy) * 2 + py, ix = (x0 - 1 + hx) * 2 + px;
-                const bool ok = sl < X_CH && ((unsigned)iy < (unsigned)Hi) && ((unsigned)ix < (unsigned)Wi);
-                const T* src = ok ? X + ((size_t)(iy * Wi + ix) * x_ld + kc * 8) : (const T*)g_wg_zero_chunk;
-                __builtin_amdgcn_global_load_lds((wg_gptr_t)src, (wg_lptr_t)(bX + (256 * it + 64 * wave) * 16), 16, 0, 0);
-            }
-        }
+    auto issue_X = [&](int y0, int x0, char* bX, bool lo, int py, int px) __attribute__((always_inline)) {
+        wg_issue_x<CPN, 2, 2>(X0p + (lo ? a.x_lo : 0), bX, tid, wave_s, (y0 - 1) * 2 + py, (x0 - 1) * 2 + px, 2, Hi, Wi, x_ld, PAD_ZERO);
+    };
+    // tile origin carried along the run: (cy, cx) this tile, (ny, nx) the next
+    int cy = (t_beg / tx_n) * WGH_TH, cx = (t_beg % tx_n) * WGH_TW, ny = 0, nx = 0;
+    const int x_end = tx_n * WGH_TW;
+    auto next_origin = [&]() __attribute__((always_inline)) {
+        ny = cy;
+        nx = cx + WGH_TW;
+        if (nx >= x_end) { nx = 0; ny += WGH_TH; }
     };
     char* const GA = smem, * const GB = smem + G_CH * 16, * const XA = smem + 2 * G_CH * 16, * const XB = XA + X_CH64 * 16;
     // phase p = 2 py + px, its sub-window inside the uniform halo
@@ -820,39 +898,41 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_s2m_kernel(const WgHaloArgs
     }
     if constexpr (!PAIR) {
         // ---- bf16: GA / GB alternate per tile, XA / XB per phase
-        if (t_beg < t_end) { issue_G(t_beg, GA, false); issue_X(t_beg, XA, false, 0, 0); }
+        if (t_beg < t_end) { issue_G(cy, cx, GA, false); issue_X(cy, cx, XA, false, 0, 0); }
         __syncthreads();
-        for (int tile = t_beg, u = 0; tile < t_end; ++tile, ++u) {
+        for (int tile = t_beg, u = 0; tile < t_end; ++tile, ++u, cy = ny, cx = nx) {
             const char* sG = (u & 1) ? GB : GA;
             char* nG = (u & 1) ? GA : GB;
+            next_origin();
             static_for<4>([&](auto pc) __attribute__((always_inline)) {
                 constexpr int P = decltype(pc)::value;
-                if constexpr (P < 3) issue_X(tile, (P & 1) ? XA : XB, false, (P + 1) >> 1, (P + 1) & 1);
-                else if (tile + 1 < t_end) { issue_G(tile + 1, nG, false); issue_X(tile + 1, XA, false, 0, 0); }
+                if constexpr (P < 3) issue_X(cy, cx, (P & 1) ? XA : XB, false, (P + 1) >> 1, (P + 1) & 1);
+                else if (tile + 1 < t_end) { issue_G(ny, nx, nG, false); issue_X(ny, nx, XA, false, 0, 0); }
                 S2M_PHASE(P, sG, (P & 1) ? XB : XA)
                 __syncthreads();   // the step's loads landed (vmcnt(0)) and every wave is done with the buffers it read
             });
         }
     } else {
         // ---- split pair: GA = g_lo, GB = g_hi, XA = x_hi(p), XB = x_lo(p); sweeps (g_lo, x_hi), (g_hi, x_hi), (g_hi, x_lo)
-        if (t_beg < t_end) { issue_G(t_beg, GA, true); issue_X(t_beg, XA, false, 0, 0); }
+        if (t_beg < t_end) { issue_G(cy, cx, GA, true); issue_X(cy, cx, XA, false, 0, 0); }
         __syncthreads();
-        for (int tile = t_beg; tile < t_end; ++tile) {
+        for (int tile = t_beg; tile < t_end; ++tile, cy = ny, cx = nx) {
+            next_origin();
             static_for<4>([&](auto pc) __attribute__((always_inline)) {
                 constexpr int P = decltype(pc)::value;
                 constexpr int py = P >> 1, px = P & 1;
                 // sweep 0: (g_lo, x_hi); fetch x_lo(p) -- and, in the tile's first step, g_hi (GB is free since the tile before)
-                issue_X(tile, XB, true, py, px);
-                if constexpr (P == 0) issue_G(tile, GB, false);
+                issue_X(cy, cx, XB, true, py, px);
+                if constexpr (P == 0) issue_G(cy, cx, GB, false);
                 S2M_PHASE(P, GA, XA)
                 __syncthreads();
                 // sweep 1: (g_hi, x_hi); behind the last use of g_lo (phase 3, sweep 0) the next tile's g_lo
-                if constexpr (P == 3) { if (tile + 1 < t_end) issue_G(tile + 1, GA, true); }
+                if constexpr (P == 3) { if (tile + 1 < t_end) issue_G(ny, nx, GA, true); }
                 S2M_PHASE(P, GB, XA)
                 __syncthreads();
                 // sweep 2: (g_hi, x_lo); fetch x_hi of the next phase (of the next tile's phase 0)
-                if constexpr (P < 3) issue_X(tile, XA, false, (P + 1) >> 1, (P + 1) & 1);
-                else if (tile + 1 < t_end) issue_X(tile + 1, XA, false, 0, 0);
+                if constexpr (P < 3) issue_X(cy, cx, XA, false, (P + 1) >> 1, (P + 1) & 1);
+                else if (tile + 1 < t_end) issue_X(ny, nx, XA, false, 0, 0);
                 S2M_PHASE(P, GB, XB)
                 __syncthreads();
             });
@@ -860,20 +940,17 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_s2m_kernel(const WgHaloArgs
     }
 #undef S2M_PHASE
 
+    const size_t tap_sz = (size_t)a.Mc * a.Nc;   // (one base per thread, wave-uniform steps: as in conv_wgrad_halo_kernel)
+    float* __restrict__ const out0 = a.part + (size_t)z * 9 * tap_sz + (size_t)(m0 + (lane >> 4) * 4) * a.Nc + (n0 + wn * TN * 16 + (lane & 15));
 #pragma unroll
     for (int t = 0; t < 9; ++t) {
-        float* __restrict__ out = a.part + ((size_t)z * 9 + t) * a.Mc * a.Nc;
+        float* __restrict__ out = out0 + t * tap_sz;
 #pragma unroll
         for (int mt = 0; mt < TM; ++mt)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int m = m0 + mt * 16 + (lane >> 4) * 4 + r;
+            for (int r = 0; r < 4; ++r)
 #pragma unroll
-                for (int nt = 0; nt < TN; ++nt) {
-                    const int c = n0 + (wn * TN + nt) * 16 + (lane & 15);
-                    out[(size_t)m * a.Nc + c] = acc[t][mt][nt][r];
-                }
-            }
+                for (int nt = 0; nt < TN; ++nt) out[(size_t)((mt * 16 + r) * a.Nc) + nt * 16] = acc[t][mt][nt][r];
     }
 }
 

@@ -87,6 +87,9 @@ SIGNATURES = {
     "ctg_subtract_slices": "ppiiiiiiiiffppp",
     "ctg_project_slabs_inplane": "piiiiiiiiiffippp",
     "ctg_project_accumulate_sliding": "piiiiiiiipp",
+    "ctg_project_rotate_depth": "piiiiipiiiiiiiffippppp",
+    "ctg_project_accumulate_depth": "piiiiiipppp",
+    "ctg_project_finish_depth": "piliiiiffippppp",
     "ctg_window_pairs": "ppppilipp",
     "ctg_maxpool3s2_fwd": "pipiiiiip",
     "ctg_lpips_layer": "pipiliippp",

@@ -20,6 +20,15 @@ voxels at 45 degrees (a ray of slope 1 skips pixels between its samples), so a o
 `oversample=s` takes s steps per voxel, with either sampling: bilinear sees a one-pixel maximum at every angle, nearest at two
 steps per voxel at nearly every one.
 
+Depth of the maximum (`depth=True` on `SeriesRotator`, `SeriesProjector`, `rotate_volume`, `project_volume`,
+`SeriesTranslator`): a MIP throws the depth away, so front and back look the same in a rotating view and a pixel cannot be sent
+back to its voxel.  With `depth=True` (mode "max" / "min") every projection also returns "depth", int16: how far along the ray
+the value was found (the first sample from the viewer's end; -1 on a rotated ray that misses the slice), and "cued", the 8-bit
+level attenuated by that depth (`cue` in 0 .. 256; 0 leaves the level as it is).  The (value, depth) pair is one 32-bit key, so
+the kernels stay single-pass, order-free integer reductions (`ops.project_rotate_depth`, `ops.project_accumulate_depth`,
+`ops.project_finish_depth`); `ray_voxel` maps a rotated pixel and its depth back to the voxel.  Sliding thin slabs have no
+depth planes: a thin slab has little depth to show.
+
 Subtraction (`subtract_volume`, `SeriesTranslator(subtract=True)`): the synthesized CTA minus the CT it was made from.  The
 generator writes on its input's pixel grid, so the pair is registered by construction: the difference of the stored values is the
 contrast-enhancement map and bone cancels without a segmentation.  One launch per chunk (`ops.subtract_slices`: 3 x 3 in-plane
@@ -95,6 +104,17 @@ def aspect_rows(n, aspect):
     return np.minimum(np.floor(np.arange(rows, dtype=np.float32) * scale).astype(np.int64), int(n) - 1)
 
 
+def _check_depth(who, depth, cue, mode):
+    """-> (depth, cue) of the depth planes: cue an integer in 0 .. 256; a depth exists for "max" and "min" only."""
+    if isinstance(cue, bool) or not isinstance(cue, (int, np.integer)) or not 0 <= cue <= 256:
+        raise ValueError("%s: cue: an integer in 0 .. 256 expected, got %r" % (who, cue))
+    if depth and mode not in ("max", "min"):
+        raise ValueError("%s: depth=True needs mode 'max' or 'min' (a mean has no depth), got %r" % (who, mode))
+    if cue and not depth:
+        raise ValueError("%s: cue=%d needs depth=True" % (who, cue))
+    return bool(depth), int(cue)
+
+
 class SeriesProjector:
     """Running projections of an int16 volume [n, h, w] that arrives in chunks on the device.
 
@@ -102,11 +122,16 @@ class SeriesProjector:
     whole volume, one plane; slabs do not overlap, the last may be shorter); axes: which of "axial" [S, h, w], "coronal" [n, w]
     (the reduction over h) and "sagittal" [n, h] (over w) to keep.  `update(pix_chunk, n0)` in any order, every slice once;
     `result(wc, ww)` -> {axis: {"values": int16, "level": uint8 or None}} on the device; `reset()` for the next volume of the
-    same shape.  Exact integer arithmetic on the current stream: equal to numpy bit for bit."""
+    same shape.  Exact integer arithmetic on the current stream: equal to numpy bit for bit.
+    depth=True (mode "max" / "min"; no axis above 32767 voxels): the accumulators hold (value, depth) keys and every axis of the
+    result gains "depth" int16 -- the slice n (axial; global, also with slabs), the row y (coronal) or the column x (sagittal)
+    of the first voxel along the axis that attains the value, np.argmax / np.argmin -- and, when the level is wanted, "cued" uint8:
+    the level attenuated by the depth inside the ray, (level w + 128) >> 8 with w = 256 - (cue d) / E, `cue` in 0 .. 256."""
 
-    def __init__(self, n, h, w, mode="max", slab=None, axes=AXES, device=None):
+    def __init__(self, n, h, w, mode="max", slab=None, axes=AXES, device=None, depth=False, cue=0):
         if mode not in PROJECTIONS:
             raise ValueError("SeriesProjector: mode %r is not one of %s" % (mode, PROJECTIONS))
+        self.depth, self.cue = _check_depth("SeriesProjector", depth, cue, mode)
         axes = tuple(axes)
         if not axes or any(a not in AXES for a in axes):
             raise ValueError("SeriesProjector: axes %r, a non-empty choice of %s expected" % (axes, AXES))
@@ -118,6 +143,9 @@ class SeriesProjector:
         self.thick = self.n if slab is None else int(slab)
         self.slabs, self.div_last = slab_plan(self.n, self.thick)
         self.thick = min(self.thick, self.n)
+        if self.depth and max(self.n, self.h, self.w) > 32767:
+            raise ValueError("SeriesProjector: depth=True: no axis above %d voxels (a depth is an int16), got (%d, %d, %d)"
+                             % (32767, self.n, self.h, self.w))
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("SeriesProjector: a GPU device is required (no CPU fallback)")
@@ -126,17 +154,31 @@ class SeriesProjector:
         self.reset()
 
     def reset(self):
+        identity = ops.PROJECT_DEPTH_IDENTITY[self.code] if self.depth else ops.PROJECT_IDENTITY[self.code]
         for t in self.acc.values():
-            t.fill_(ops.PROJECT_IDENTITY[self.code])
+            t.fill_(identity)
 
     def update(self, pix_chunk, n0):
         k = pix_chunk.shape[0]
         if tuple(pix_chunk.shape[1:]) != (self.h, self.w) or int(n0) < 0 or int(n0) + k > self.n:
             raise RuntimeError("SeriesProjector: chunk %s at slice %d does not lie in the volume (%d, %d, %d)"
                                % (tuple(pix_chunk.shape), int(n0), self.n, self.h, self.w))
-        ops.project_accumulate(pix_chunk, int(n0), self.thick, self.code, **self.acc)
+        if self.depth:
+            ops.project_accumulate_depth(pix_chunk, int(n0), self.thick, self.code, **self.acc)
+        else:
+            ops.project_accumulate(pix_chunk, int(n0), self.thick, self.code, **self.acc)
 
     def result(self, wc=50.0, ww=400.0, hu=False, level=True):
+        if self.depth:
+            extent = {"axial": (self.thick, self.n), "coronal": (self.h, self.h), "sagittal": (self.w, self.w)}
+            out = {}
+            for a, acc in self.acc.items():
+                values, lvl, depth, cued = ops.project_finish_depth(acc, self.code, extent[a][0], extent[a][1], cue=self.cue, wc=wc,
+                                                                    ww=ww, hu=hu, want_level=level, want_cued=level)
+                out[a] = {"values": values, "level": lvl, "depth": depth}
+                if level:
+                    out[a]["cued"] = cued
+            return out
         div = {"axial": (self.thick, self.div_last), "coronal": (self.h, self.h), "sagittal": (self.w, self.w)}
         out = {}
         for a, acc in self.acc.items():
@@ -145,10 +187,12 @@ class SeriesProjector:
         return out
 
 
-def project_volume(volume, mode="max", slab=None, wc=50.0, ww=400.0, hu=False, batch=64, axes=AXES, level=True, device=None):
+def project_volume(volume, mode="max", slab=None, wc=50.0, ww=400.0, hu=False, batch=64, axes=AXES, level=True, device=None,
+                   depth=False, cue=0):
     """The projections of a volume that already exists (the input CT, the real CTA for a side-by-side view): int16 [N, H, W],
-    a host array / CPU tensor (chunks of `batch` slices cross PCIe one after another) or a device tensor.  Returns what
-    `SeriesProjector.result` returns, of the input's kind (numpy arrays, CPU tensors or device tensors)."""
+    a host array / CPU tensor (chunks of `batch` slices cross PCIe one after another) or a device tensor; depth and cue as
+    `SeriesProjector`.  Returns what `SeriesProjector.result` returns, of the input's kind (numpy arrays, CPU tensors or device
+    tensors)."""
     is_np = isinstance(volume, np.ndarray)
     vol = torch.from_numpy(np.ascontiguousarray(volume)) if is_np else volume
     if not torch.is_tensor(vol) or vol.dtype != torch.int16 or vol.dim() != 3:
@@ -157,7 +201,7 @@ def project_volume(volume, mode="max", slab=None, wc=50.0, ww=400.0, hu=False, b
         raise ValueError("project_volume: batch >= 1 expected")
     on_host = not vol.is_cuda
     n, h, w = vol.shape
-    proj = SeriesProjector(n, h, w, mode=mode, slab=slab, axes=axes, device=device if on_host else vol.device)
+    proj = SeriesProjector(n, h, w, mode=mode, slab=slab, axes=axes, device=device if on_host else vol.device, depth=depth, cue=cue)
     with torch.cuda.device(proj.device):
         for s, e, _ in plan_chunks(n, batch):
             proj.update(vol[s:e].to(proj.device) if on_host else vol[s:e], s)
@@ -320,6 +364,20 @@ def rotation_coefficients(angle, h, w, u=None, t=None, oversample=1):
     return (r(cx - cu * cos + ct * sin + 0.5), r(cos), r(-sin / s), r(cy - cu * sin - ct * cos + 0.5), r(sin), r(cos / s))
 
 
+def ray_voxel(coef_row, u, t):
+    """(x, y): the pixel of the slice that sample (u, t) of a rotated view falls in, by the kernel's nearest rule
+    x = (c0 + c1 u + c2 t) >> 16, y = (c3 + c4 u + c5 t) >> 16 (arithmetic shift) for the view's coefficient row (c0 .. c5)
+    (`rotation_coefficients`, a row of `SeriesRotator.table.host`).  With t = the "depth" of detector column u in row n of the
+    view, (n, y, x) is the voxel the projected value came from (nearest sampling; with bilinear sampling, the pixel the sample
+    counts by).  A pure host function; u and t may be integers or integer arrays, a missed ray (depth -1) has no voxel."""
+    c = [int(v) for v in coef_row]
+    if len(c) != 6:
+        raise ValueError("ray_voxel: a coefficient row of six integers expected, got %d" % len(c))
+    u, t = np.asarray(u, dtype=np.int64), np.asarray(t, dtype=np.int64)
+    x, y = (c[0] + c[1] * u + c[2] * t) >> 16, (c[3] + c[4] * u + c[5] * t) >> 16
+    return (int(x), int(y)) if x.ndim == 0 else (x, y)
+
+
 def _check_sampling(who, sampling, oversample):
     if sampling not in ops.ROTATE_SAMPLINGS:
         raise ValueError("%s: sampling %r is not one of %s" % (who, sampling, tuple(ops.ROTATE_SAMPLINGS)))
@@ -334,12 +392,17 @@ class SeriesRotator:
     takes `.steps` = T s steps of 1 / s voxel (`.t` stays T).  A ray that misses the slice gets `fill` (default: air, 0 or
     -1024 with `hu`); level=False skips the 8-bit planes of the window (wc, ww).  `update(pix_chunk, n0)` in any order, every
     slice once: a chunk finishes its own rows of every angle; `result()` -> {"values": int16 [A, n, U], "level": uint8 or None,
-    "angles": float64 [A]} on the device.  Exact integer arithmetic on the current stream: equal to numpy bit for bit."""
+    "angles": float64 [A]} on the device.  Exact integer arithmetic on the current stream: equal to numpy bit for bit.
+    depth=True (mode "max" / "min"): the result gains "depth" int16 [A, n, U] -- the step 0 .. `.steps`-1, counted from the
+    viewer's end of the ray, of the first counted sample that attains the value; -1 where the ray misses the slice (`ray_voxel`
+    maps it back to the pixel) -- and, with level, "cued" uint8: the level attenuated by the depth, (level w + 128) >> 8 with
+    w = 256 - (cue depth) / steps, `cue` in 0 .. 256.  One launch per chunk either way: the depth entry replaces the plain one."""
 
     def __init__(self, n, h, w, angles, mode="max", detector=None, fill=None, wc=50.0, ww=400.0, hu=False, level=True, device=None,
-                 sampling="nearest", oversample=1):
+                 sampling="nearest", oversample=1, depth=False, cue=0):
         if mode not in PROJECTIONS:
             raise ValueError("SeriesRotator: mode %r is not one of %s" % (mode, PROJECTIONS))
+        self.depth, self.cue = _check_depth("SeriesRotator", depth, cue, mode)
         _check_sampling("SeriesRotator", sampling, oversample)
         self.sampling, self.oversample = sampling, int(oversample)
         self.n, self.h, self.w = int(n), int(h), int(w)
@@ -362,6 +425,8 @@ class SeriesRotator:
         shape = (len(self.angles), self.n, self.u)
         self.values = torch.empty(shape, dtype=torch.int16, device=self.device)
         self.level = torch.empty(shape, dtype=torch.uint8, device=self.device) if level else None
+        self.depth_plane = torch.empty(shape, dtype=torch.int16, device=self.device) if self.depth else None
+        self.cued = torch.empty(shape, dtype=torch.uint8, device=self.device) if self.depth and level else None
         self._angles = torch.tensor(self.angles, dtype=torch.float64, device=self.device)
 
     def reset(self):
@@ -374,18 +439,28 @@ class SeriesRotator:
                                % (tuple(pix_chunk.shape), int(n0), self.n, self.h, self.w))
         if k < 1:
             return
+        if self.depth:
+            ops.project_rotate_depth(pix_chunk, int(n0), self.table, self.steps, self.code, values=self.values, level=self.level,
+                                     depth=self.depth_plane, cued=self.cued, cue=self.cue, fill=self.fill, wc=self.window[0],
+                                     ww=self.window[1], hu=self.hu, sampling=self.sampling)
+            return
         ops.project_rotate(pix_chunk, int(n0), self.table, self.steps, self.code, values=self.values, level=self.level,
                            fill=self.fill, wc=self.window[0], ww=self.window[1], hu=self.hu, sampling=self.sampling)
 
     def result(self):
-        return {"values": self.values, "level": self.level, "angles": self._angles}
+        out = {"values": self.values, "level": self.level, "angles": self._angles}
+        if self.depth:
+            out["depth"] = self.depth_plane
+            if self.cued is not None:
+                out["cued"] = self.cued
+        return out
 
 
 def rotate_volume(volume, angles, mode="max", detector=None, fill=None, wc=50.0, ww=400.0, hu=False, level=True, batch=64,
-                  device=None, sampling="nearest", oversample=1):
+                  device=None, sampling="nearest", oversample=1, depth=False, cue=0):
     """The rotating projections of a volume that already exists, the counterpart of `project_volume`: int16 [N, H, W], a host
     array / CPU tensor (chunks of `batch` slices cross PCIe one after another) or a device tensor; angles: degrees, or an int
-    count of views around the full circle (`view_angles`); sampling and oversample as `SeriesRotator`.  Returns what
+    count of views around the full circle (`view_angles`); sampling, oversample, depth and cue as `SeriesRotator`.  Returns what
     `SeriesRotator.result` returns, of the input's kind."""
     is_np = isinstance(volume, np.ndarray)
     vol = torch.from_numpy(np.ascontiguousarray(volume)) if is_np else volume
@@ -396,7 +471,7 @@ def rotate_volume(volume, angles, mode="max", detector=None, fill=None, wc=50.0,
     on_host = not vol.is_cuda
     n, h, w = vol.shape
     rot = SeriesRotator(n, h, w, _angle_list(angles), mode=mode, detector=detector, fill=fill, wc=wc, ww=ww, hu=hu, level=level,
-                        device=device if on_host else vol.device, sampling=sampling, oversample=oversample)
+                        device=device if on_host else vol.device, sampling=sampling, oversample=oversample, depth=depth, cue=cue)
     with torch.cuda.device(rot.device):
         for s, e, _ in plan_chunks(n, batch):
             rot.update(vol[s:e].to(rot.device) if on_host else vol[s:e], s)
@@ -471,6 +546,9 @@ class SeriesTranslator:
     slabs = a dict of `SeriesSlabs` keyword arguments (thick, and any of step, mode, axes) adds "slabs": {axis: {"values":
     int16 [J, ...], "level": uint8}}, the sliding thin-slab projections of the same source in the same window, copied back once
     after the last chunk; with slabs=None nothing of it is allocated or launched.
+    depth=True (depth_cue: 0 .. 256) applies to whichever of `project` / `rotate` is on, with mode "max" / "min": their dicts gain
+    "depth" (int16) and "cued" (uint8, the depth-cued level), as `SeriesProjector` / `SeriesRotator` give them, staged back with
+    the other planes; the slabs have no depth planes.  With depth=False nothing of it is allocated or launched.
 
     size: the side(s) the generator runs at (None: the volume's own); a volume of another size is resized (nearest) on the way
     in and comes back at its own size.  wc / ww: the window of the 8-bit level; hu: pixels minus 1024 (SimpleITK) instead of
@@ -479,7 +557,8 @@ class SeriesTranslator:
 
     def __init__(self, generator, batch=16, size=None, wc=50.0, ww=400.0, hu=False, level=True, device=None, project=None,
                  slab=None, rotate=None, rotate_mode=None, subtract=False, sub_median=True, sub_floor=0, sub_ct_range=(None, None),
-                 sub_window=(150.0, 300.0), project_source="cta", slabs=None, rotate_sampling="nearest", rotate_oversample=1):
+                 sub_window=(150.0, 300.0), project_source="cta", slabs=None, rotate_sampling="nearest", rotate_oversample=1,
+                 depth=False, depth_cue=0):
         if int(batch) < 1:
             raise ValueError("SeriesTranslator: batch >= 1 expected")
         if project_source not in PROJECT_SOURCES or (project_source == "sub" and not subtract):
@@ -498,6 +577,11 @@ class SeriesTranslator:
             raise ValueError("SeriesTranslator: rotate needs at least one angle and a rotate_mode of %s, got %r"
                              % (PROJECTIONS, self.rotate_mode))
         _check_sampling("SeriesTranslator", rotate_sampling, rotate_oversample)
+        self.depth, self.depth_cue = _check_depth("SeriesTranslator", depth, depth_cue, "max")
+        if self.depth and project is None and self.rotate is None:
+            raise ValueError("SeriesTranslator: depth=True needs project or rotate")
+        for mode in ([project] if project is not None else []) + ([self.rotate_mode] if self.rotate is not None else []):
+            _check_depth("SeriesTranslator", self.depth, self.depth_cue, mode)
         self.rotate_sampling, self.rotate_oversample = rotate_sampling, int(rotate_oversample)
         self._rotator = self._rot_host = None
         self.slabs = None if slabs is None else dict(slabs)
@@ -696,8 +780,8 @@ class SeriesTranslator:
 
     def _stage_rotation(self, dev):
         """Start the copies of the rotating projections into page-locked buffers (kept between calls on volumes of one shape)."""
-        dev = {k: dev[k] for k in ("values", "level")}
-        if self._rot_host is None or self._rot_host["values"].shape != dev["values"].shape:
+        dev = {k: dev[k] for k in ("values", "level", "depth", "cued") if k in dev}
+        if self._rot_host is None or self._rot_host["values"].shape != dev["values"].shape or set(self._rot_host) != set(dev):
             self._rot_host = {k: torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for k, t in dev.items()}
         for k, t in dev.items():
             self._rot_host[k].copy_(t, non_blocking=True)
@@ -734,7 +818,8 @@ class SeriesTranslator:
         if r is None or (r.n, r.h, r.w) != (n, h, w):
             wc, ww = self._view_window()
             r = self._rotator = SeriesRotator(n, h, w, self.rotate, mode=self.rotate_mode, wc=wc, ww=ww, hu=self._view_hu(),
-                                              device=self.device, sampling=self.rotate_sampling, oversample=self.rotate_oversample)
+                                              device=self.device, sampling=self.rotate_sampling, oversample=self.rotate_oversample,
+                                              depth=self.depth, cue=self.depth_cue)
         return r
 
     def _projector_for(self, n, h, w):
@@ -743,7 +828,8 @@ class SeriesTranslator:
             return None
         p = self._projector
         if p is None or (p.n, p.h, p.w) != (n, h, w):
-            p = self._projector = SeriesProjector(n, h, w, mode=self.project, slab=self.slab, device=self.device)
+            p = self._projector = SeriesProjector(n, h, w, mode=self.project, slab=self.slab, device=self.device, depth=self.depth,
+                                                  cue=self.depth_cue)
         else:
             p.reset()
         return p

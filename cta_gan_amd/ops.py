@@ -1835,6 +1835,143 @@ def project_rotate(pix, n0, coef, t, mode, values=None, level=None, fill=None, w
                                    _p(values), _p(level), _stream()), entry)
 
 
+# ---------------------------------------------------------------------------- depth of the maximum (project_rotate.hip, project.hip)
+PROJECT_DEPTH_IDENTITY = (0, -1)      # what a keyed accumulator holds before the first chunk, by mode code (max, min)
+_ROTATE_SAMPLING_CODES = {"nearest": 0, "bilinear": 1}      # `sampling` of ctg_project_rotate_depth
+
+
+def _depth_mode(mode, what):
+    code = _project_mode(mode, what)
+    if code == 2:
+        raise RuntimeError("%s: a depth exists for mode 0 / 'max' and 1 / 'min' only, got %r" % (what, mode))
+    return code
+
+
+def _depth_cue(cue, what):
+    if isinstance(cue, bool) or not isinstance(cue, int) or not 0 <= cue <= 256:
+        raise RuntimeError("%s: cue: an integer in 0 .. 256 expected, got %r" % (what, cue))
+    return cue
+
+
+def project_rotate_depth(pix, n0, coef, t, mode, values=None, level=None, depth=None, cued=None, cue=0, fill=None, wc=50.0, ww=400.0,
+                         hu=False, sampling="nearest"):
+    """`project_rotate` with the depth of the maximum, one launch of ctg_project_rotate_depth (the plain entry is not run): mode 0 /
+    "max" or 1 / "min" only.  depth int16 (A, N, U): the step t in 0 .. T-1 of the first counted sample, from the viewer's end,
+    that attains the value (np.argmax / np.argmin over the ray's counted samples), -1 where the ray misses the slice.  cued uint8:
+    the level attenuated by that depth, (level w + 128) >> 8 with w = 256 - (cue depth) / T, cue an integer in 0 .. 256 (0: the
+    level itself).  values and level are what `project_rotate` writes.  Any of the four may be None, not all."""
+    lib = _lib.load()
+    who = "project_rotate_depth"
+    if not torch.is_tensor(pix) or not pix.is_cuda:
+        raise RuntimeError("%s: CPU tensors are not supported (no CPU fallback)" % who)
+    if pix.dtype != torch.int16 or pix.dim() != 3:
+        raise RuntimeError("%s: pix must be int16 (K, H, W), got %s %s" % (who, pix.dtype, tuple(pix.shape)))
+    code = _depth_mode(mode, who)
+    cue = _depth_cue(cue, who)
+    if sampling not in _ROTATE_SAMPLING_CODES:
+        raise RuntimeError("%s: sampling %r is not one of %s" % (who, sampling, tuple(_ROTATE_SAMPLING_CODES)))
+    outs = (("values", values, torch.int16), ("level", level, torch.uint8), ("depth", depth, torch.int16), ("cued", cued, torch.uint8))
+    given = [o for _, o, _ in outs if o is not None]
+    if not given:
+        raise RuntimeError("%s: at least one of values, level, depth, cued expected" % who)
+    for name, o, dtype in outs:
+        _rotate_out(o, dtype, name)
+    if any(o.shape != given[0].shape for o in given):
+        raise RuntimeError("%s: the outputs differ in shape: %s" % (who, [tuple(o.shape) for o in given]))
+    if torch.is_tensor(coef) and coef.is_cuda:
+        raise RuntimeError("%s: the coefficients are checked on the host: pass a host table or an ops.RotateTable" % who)
+    table = coef if isinstance(coef, RotateTable) else RotateTable(coef, pix.device)
+    if any(o.device != pix.device for o in given + [table.dev]):
+        raise RuntimeError("%s: pix, the coefficient table and the outputs must live on one device" % who)
+    a, n, u = given[0].shape
+    x = pix.contiguous()
+    k, h, w = x.shape
+    n0, t, hu = int(n0), int(t), bool(hu)
+    fill = (-1024 if hu else 0) if fill is None else int(fill)
+    if a != table.count:
+        raise RuntimeError("%s: %d planes for a table of %d angles" % (who, a, table.count))
+    if k < 1 or n0 < 0 or n0 + k > n:
+        raise RuntimeError("%s: chunk of %d slices at slice %d does not lie in the volume of %d" % (who, k, n0, n))
+    if not (1 <= min(h, w, u, t) and max(h, w, u, t) <= ROTATE_MAX_DIM):
+        raise RuntimeError("%s: H, W, U, T in 1 .. %d expected, got %d %d %d %d" % (who, ROTATE_MAX_DIM, h, w, u, t))
+    if not -32768 <= fill <= 32767:
+        raise RuntimeError("%s: fill %d is not an int16 value" % (who, fill))
+    _lib.check(lib.ctg_project_rotate_depth(_p(x), k, h, w, n0, n, _p(table.dev), a, u, t, code, _ROTATE_SAMPLING_CODES[sampling], fill,
+                                            cue, float(wc), float(ww), int(hu), _p(values), _p(level), _p(depth), _p(cued), _stream()),
+               "ctg_project_rotate_depth")
+
+
+def project_accumulate_depth(pix, n0, thick, mode, axial=None, coronal=None, sagittal=None):
+    """`project_accumulate` on keyed accumulators (value and depth of the maximum in one 32-bit word, include/ctagan_hip.h): the
+    same arguments and shapes, int32 tensors that the caller fills with PROJECT_DEPTH_IDENTITY[mode] before the first chunk; mode
+    0 / "max" or 1 / "min" only.  The depth is the slice n (axial; global, also with slabs), the row y (coronal) or the column x
+    (sagittal) of the first voxel along the axis that attains the value; no axis may exceed 32767 voxels.  `project_finish_depth`
+    unpacks an accumulator."""
+    lib = _lib.load()
+    who = "project_accumulate_depth"
+    if not torch.is_tensor(pix) or not pix.is_cuda:
+        raise RuntimeError("%s: CPU tensors are not supported (no CPU fallback)" % who)
+    if pix.dtype != torch.int16 or pix.dim() != 3:
+        raise RuntimeError("%s: pix must be int16 (K, H, W), got %s %s" % (who, pix.dtype, tuple(pix.shape)))
+    code = _depth_mode(mode, who)
+    n0, thick = int(n0), int(thick)
+    if n0 < 0 or thick < 1:
+        raise RuntimeError("%s: n0 >= 0 and thick >= 1 expected, got n0=%d thick=%d" % (who, n0, thick))
+    if axial is None and coronal is None and sagittal is None:
+        raise RuntimeError("%s: at least one accumulator expected" % who)
+    x = pix.contiguous()
+    k, h, w = x.shape
+    if k < 1:
+        return
+    if max(n0 + k, h, w) > 32767:
+        raise RuntimeError("%s: a depth is an int16: no axis above %d voxels, got n0 + K = %d, H = %d, W = %d"
+                           % (who, 32767, n0 + k, h, w))
+    _project_acc(axial, ((n0 + k - 1) // thick + 1, h, w), "axial")
+    _project_acc(coronal, (n0 + k, w), "coronal")
+    _project_acc(sagittal, (n0 + k, h), "sagittal")
+    if any(t is not None and t.device != x.device for t in (axial, coronal, sagittal)):
+        raise RuntimeError("%s: pix and the accumulators must live on one device" % who)
+    _lib.check(lib.ctg_project_accumulate_depth(_p(x), k, h, w, n0, thick, code, _p(axial), _p(coronal), _p(sagittal), _stream()),
+               "ctg_project_accumulate_depth")
+
+
+def project_finish_depth(acc, mode, thick, extent, cue=0, wc=50.0, ww=400.0, hu=False, want_values=True, want_level=True,
+                         want_depth=True, want_cued=True):
+    """A keyed accumulator of `project_accumulate_depth` -> (values int16, level uint8, depth int16, cued uint8) of its shape, one
+    launch; each is None when not wanted.  Plane s of a 3-d accumulator holds rays that start at coordinate s * thick of an axis
+    of `extent` voxels and are min(thick, extent - s thick) long (axial: thick, extent = N; a 2-d coronal / sagittal accumulator:
+    thick = extent = H / W).  depth is the voxel coordinate along the axis (global), cued = (level w + 128) >> 8 with
+    w = 256 - (cue (depth - s thick)) / that length, cue an integer in 0 .. 256.  thick and extent must be those the accumulator
+    was filled under (the keys carry global coordinates; another plan cannot be detected and makes `cued` meaningless).  values and
+    level are what `project_finish` gives the plain accumulator."""
+    lib = _lib.load()
+    who = "project_finish_depth"
+    if not torch.is_tensor(acc) or not acc.is_cuda:
+        raise RuntimeError("%s: CPU tensors are not supported (no CPU fallback)" % who)
+    if acc.dtype != torch.int32 or acc.dim() not in (2, 3) or not acc.is_contiguous():
+        raise RuntimeError("%s: a contiguous int32 accumulator of 2 or 3 dimensions expected, got %s %s"
+                           % (who, acc.dtype, tuple(acc.shape)))
+    if not (want_values or want_level or want_depth or want_cued):
+        raise RuntimeError("%s: at least one of values, level, depth, cued expected" % who)
+    code = _depth_mode(mode, who)
+    cue = _depth_cue(cue, who)
+    thick, extent = int(thick), int(extent)
+    planes = acc.shape[0] if acc.dim() == 3 else 1
+    if thick < 1 or not 1 <= extent <= 32767 or (planes - 1) * thick >= extent:
+        raise RuntimeError("%s: thick >= 1, 1 <= extent <= %d and (planes - 1) thick < extent expected, got thick=%d extent=%d "
+                           "planes=%d" % (who, 32767, thick, extent, planes))
+    values = torch.empty(acc.shape, dtype=torch.int16, device=acc.device) if want_values else None
+    level = torch.empty(acc.shape, dtype=torch.uint8, device=acc.device) if want_level else None
+    depth = torch.empty(acc.shape, dtype=torch.int16, device=acc.device) if want_depth else None
+    cued = torch.empty(acc.shape, dtype=torch.uint8, device=acc.device) if want_cued else None
+    if acc.numel() == 0:
+        return values, level, depth, cued
+    _lib.check(lib.ctg_project_finish_depth(_p(acc), planes, acc.numel() // planes, code, thick, extent, cue, float(wc), float(ww),
+                                            int(bool(hu)), _p(values), _p(level), _p(depth), _p(cued), _stream()),
+               "ctg_project_finish_depth")
+    return values, level, depth, cued
+
+
 # ---------------------------------------------------------------------------- sliding thin slabs (csrc/project_slabs.hip)
 SLAB_AXES = {"coronal": 0, "sagittal": 1}      # the in-plane axes of `project_slabs_inplane`
 SLAB_MAX_DIM = 65535

@@ -509,6 +509,49 @@ int ctg_project_slabs_inplane(const short* pix, int K, int H, int W, int n0, int
 int ctg_project_accumulate_sliding(const short* pix, int K, int H, int W, int n0, int N, int thick, int step, int mode, int* axial,
                                    void* stream);
 
+/* ---- series inference, the depth of the maximum (added under ABI 15: purely additive, no existing signature or meaning moves, so
+ * the version stays 15): a maximum-intensity projection throws the depth away -- front and back look the same in a rotating MIP,
+ * and a pixel cannot be sent back to the voxel it came from.  These entries give, beside the value and its level, the depth plane
+ * (how far along the ray the value was found) and the depth-cued level (the level attenuated by that depth): cta_gan_amd/infer.py:
+ * SeriesRotator(depth=True), SeriesProjector(depth=True), rotate_volume, project_volume, SeriesTranslator(depth=True), ray_voxel.
+ * Definitions, for all three entries:
+ *   Modes: 0 max and 1 min.  A mean has no depth: mode 2 is CTG_EINVAL.
+ *   Depth of a ray: the index along the ray of the first sample, from the viewer's end, that attains the projected value: the
+ *     smallest index wins a tie, np.argmax / np.argmin over the axis.  Rotating projection: the step t in 0 .. T-1 (steps of 1 / s
+ *     voxel when oversampled; step 0 is the end nearest the viewer), over counted samples only; a ray that misses the slice
+ *     (count 0) has depth -1.  Axis projections: the voxel coordinate along the projected axis -- the slice n (global, also with
+ *     axial slabs), the row y (coronal), the column x (sagittal).  Depth planes are int16: an axis extent above 32767 is CTG_EINVAL.
+ *   Packed key: with b = value + 32768 in 0 .. 65535 and depth d,
+ *       max: key = b << 16 | (65535 - d), combined by the unsigned maximum, identity 0
+ *       min: key = b << 16 | d,           combined by the unsigned minimum, identity 0xffffffff
+ *     so "better value first, then nearer depth" is the order of one 32-bit word, and every reduction stays order-free.  Keyed
+ *     accumulators are int32 arrays filled with 0 / -1 (the identities' bits); the kernels read and combine them as unsigned.
+ *   Depth cue: an integer cue in 0 .. 256.  With E the length of the ray and d the depth measured from the ray's own start,
+ *       w = 256 - (cue d) / E  (C division: 1 <= w <= 256 because d < E; a missed ray keeps w = 256),  cued = (level w + 128) >> 8
+ *     E = T steps (rotation), H (coronal), W (sagittal), the slab's own length min(thick, N - slab thick) (axial; only the last
+ *     slab can be short), and d = n - slab thick for axial.  cue = 0 reproduces level bit for bit; cued <= level always.
+ * ctg_project_rotate_depth: the arguments, the checks, the table, the detector, the interval, the "counted" rule, `fill` and the
+ *   rows written are those of ctg_project_rotate; sampling 0 = nearest, 1 = bilinear (the value of ctg_project_rotate_bilinear).
+ *   Outputs [A][N][U]: values int16, level uint8, depth int16, cued uint8; any may be NULL, not all four.  values and level equal
+ *   what ctg_project_rotate / _bilinear write for the same arguments.  One launch, no accumulator.
+ * ctg_project_accumulate_depth: the arguments, the checks and the chunk handling of ctg_project_accumulate on keyed accumulators of
+ *   the same shapes: axial [S][H][W] keys carry n0 + k, coronal [N][W] keys the row y, sagittal [N][H] keys the column x.  Chunks in
+ *   any order, every slice once.  K, thick 1 .. 65535; n0 + K, H, W <= 32767.
+ * ctg_project_finish_depth: acc = one keyed accumulator of `planes` planes of `plane_items` items -> values int16, level uint8,
+ *   depth int16, cued uint8 of the same shape; any may be NULL, not all four.  Plane s holds rays that start at coordinate s thick
+ *   of an axis of `extent` voxels (axial: planes = S, thick, extent = N; coronal: planes = 1, thick = extent = H; sagittal:
+ *   planes = 1, thick = extent = W); (planes - 1) thick < extent <= 32767.  thick and extent must be those the accumulator was
+ *   filled under (the thick of the ctg_project_accumulate_depth calls, the axis' full extent): the keys carry global coordinates
+ *   and nothing can check them against another plan -- with another plan `cued` is meaningless (w is kept in 1 .. 256, nothing
+ *   else).  An item no chunk reached has the mode's identity value and depth -1.  level as ctg_project_finish. ---- */
+int ctg_project_rotate_depth(const short* pix, int K, int H, int W, int n0, int N, const int* coef, int A, int U, int T, int mode,
+                             int sampling, int fill, int cue, float wc, float ww, int hu, short* values, unsigned char* level,
+                             short* depth, unsigned char* cued, void* stream);
+int ctg_project_accumulate_depth(const short* pix, int K, int H, int W, int n0, int thick, int mode, int* axial, int* coronal,
+                                 int* sagittal, void* stream);
+int ctg_project_finish_depth(const int* acc, int planes, long plane_items, int mode, int thick, int extent, int cue, float wc,
+                             float ww, int hu, short* values, unsigned char* level, short* depth, unsigned char* cued, void* stream);
+
 /* ---- LPIPS (AlexNet, lpips 0.1) of the test() loops (ABI 14): `loss_fn_alex = lpips.LPIPS(net='alex')` (trainer/HdTrainer.py:26-28)
  * and its calls `loss_fn_alex.forward(torch.tensor(c), torch.tensor(b))` on the windowed and on the raw masked pair of every slice
  * (HdTrainer.py:504-513, 531-536, 1029-1031, 1054-1056; the twins in CycTrainer.py, p2pTrainer.py, RegTrainer.py).  The five

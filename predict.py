@@ -10,6 +10,7 @@
                        [--mip-mode max|min|mean] [--aspect R]]
                       [--sub-output sub.npy [--sub-level-dir DIR] [--sub-floor 0] [--sub-no-median] [--sub-ct-min HU]
                        [--sub-ct-max HU] [--sub-wc 150 --sub-ww 300] [--mip-source cta|sub]]
+                      [--depth [--depth-cue C]]
 
 --input: int16 [N, H, W] .npy in SimpleITK's convention (what the reference's loaders read from the DICOMs); --weights: the
 reference-format `state_dict` of Model.HdGan.Generator (what train() saves as netG_A2B*.pth).  --output receives the int16
@@ -37,6 +38,12 @@ device while the volume is made: the pair is registered by construction, so bone
 open), become 0.  --sub-level-dir: one 8-bit PNG per slice in the window --sub-wc / --sub-ww of a HU difference.  --mip-source
 sub makes --mip-dir, --rot-dir and --sts-dir show the subtraction volume (levels in the --sub window) instead of the synthesized one: the
 bone-free MIP.
+--depth (with --mip-dir and / or --rot-dir, --mip-mode max or min): the depth of the maximum.  rotation.npz gains depth (int16
+[A, N, D]: the step along the ray, counted from the viewer's end, at which the value was found; -1 where the ray misses the
+slice) and projections.npz gains axial_depth, coronal_depth and sagittal_depth (the slice, row or column of the value).
+--depth-cue C (0 .. 256, default 0) also adds the depth-cued levels (cued; axial_cued, coronal_cued, sagittal_cued): the level
+attenuated by up to C / 256 toward the far end of the ray, which tells front from back in the rotating view; with C > 0 the PNGs
+are written from them.  Without --depth every output is what it was.
 DICOM reading and writing are not part of this build.
 """
 import argparse
@@ -66,6 +73,8 @@ def build_parser():
     parser.add_argument("--rot-span", type=float, default=360.0, help="degrees the view angles are spread over (with --rot-dir)")
     parser.add_argument("--rot-sampling", choices=["nearest", "bilinear"], default="nearest", help="how a ray samples the slice (with --rot-dir)")
     parser.add_argument("--rot-oversample", type=int, default=1, help="steps per voxel along a ray (with --rot-dir)")
+    parser.add_argument("--depth", action="store_true", help="also record the depth of the maximum (with --mip-dir / --rot-dir)")
+    parser.add_argument("--depth-cue", type=int, default=0, help="0 .. 256: attenuate the levels by depth (with --depth)")
     parser.add_argument("--sts-dir", type=str, default=None, help="also write the sliding thin-slab projections here")
     parser.add_argument("--sts-thick", type=str, default=None, help="voxels per slab: T, or T,Tc,Ts for axial,coronal,sagittal")
     parser.add_argument("--sts-step", type=str, default=None, help="voxels a slab moves on: S or S,Sc,Ss (default: the thickness)")
@@ -125,6 +134,12 @@ def parse_args(argv=None):
         parser.error("--mip-source sub and --sub-level-dir need --sub-output")
     if opts.sub_ct_min is not None and opts.sub_ct_max is not None and opts.sub_ct_min > opts.sub_ct_max:
         parser.error("--sub-ct-min above --sub-ct-max")
+    if not 0 <= opts.depth_cue <= 256:
+        parser.error("--depth-cue: 0 .. 256 expected")
+    if opts.depth_cue and not opts.depth:
+        parser.error("--depth-cue needs --depth")
+    if opts.depth and (opts.mip_mode == "mean" or (opts.mip_dir is None and opts.rot_dir is None)):
+        parser.error("--depth needs --mip-dir or --rot-dir and --mip-mode max or min (a mean has no depth)")
     return opts
 
 
@@ -165,7 +180,8 @@ def main(argv=None):
                                  project=opts.mip_mode if opts.mip_dir is not None else None, slab=opts.slab,
                                  rotate=view_angles(opts.rot_angles, opts.rot_span) if opts.rot_dir is not None else None,
                                  rotate_mode=opts.mip_mode, rotate_sampling=opts.rot_sampling, rotate_oversample=opts.rot_oversample,
-                                 slabs=opts.sts)
+                                 slabs=opts.sts, depth=opts.depth, depth_cue=opts.depth_cue)
+    shown = "cued" if opts.depth_cue > 0 else "level"      # the plane the PNGs of the projections are written from
     out = translate(volume)
     np.save(opts.output, out["pix"])
     if opts.level_dir is not None:
@@ -186,12 +202,17 @@ def main(argv=None):
         from cta_gan_amd.infer import aspect_rows
         os.makedirs(opts.mip_dir, exist_ok=True)
         proj = out["projections"]
-        for i, plane in enumerate(proj["axial"]["level"]):
+        for i, plane in enumerate(proj["axial"][shown]):
             Image.fromarray(plane).save(os.path.join(opts.mip_dir, "axial_%03d.png" % i))
         rows = aspect_rows(volume.shape[0], opts.aspect)
         for axis in ("coronal", "sagittal"):
-            Image.fromarray(np.ascontiguousarray(proj[axis]["level"][rows])).save(os.path.join(opts.mip_dir, axis + ".png"))
-        np.savez(os.path.join(opts.mip_dir, "projections.npz"), **{axis: proj[axis]["values"] for axis in proj})
+            Image.fromarray(np.ascontiguousarray(proj[axis][shown][rows])).save(os.path.join(opts.mip_dir, axis + ".png"))
+        arrays = {axis: proj[axis]["values"] for axis in proj}
+        if opts.depth:
+            arrays.update({axis + "_depth": proj[axis]["depth"] for axis in proj})
+        if opts.depth_cue > 0:
+            arrays.update({axis + "_cued": proj[axis]["cued"] for axis in proj})
+        np.savez(os.path.join(opts.mip_dir, "projections.npz"), **arrays)
         print("wrote the %s projections to %s" % (opts.mip_mode, opts.mip_dir), flush=True)
     if opts.rot_dir is not None:
         from PIL import Image
@@ -199,9 +220,14 @@ def main(argv=None):
         os.makedirs(opts.rot_dir, exist_ok=True)
         rot = out["rotation"]
         rows = aspect_rows(volume.shape[0], opts.aspect)
-        for i, plane in enumerate(rot["level"]):
+        for i, plane in enumerate(rot[shown]):
             Image.fromarray(np.ascontiguousarray(plane[rows])).save(os.path.join(opts.rot_dir, "rot_%03d.png" % i))
-        np.savez(os.path.join(opts.rot_dir, "rotation.npz"), values=rot["values"], level=rot["level"], angles=rot["angles"])
+        arrays = {"values": rot["values"], "level": rot["level"], "angles": rot["angles"]}
+        if opts.depth:
+            arrays["depth"] = rot["depth"]
+        if opts.depth_cue > 0:
+            arrays["cued"] = rot["cued"]
+        np.savez(os.path.join(opts.rot_dir, "rotation.npz"), **arrays)
         print("wrote %d views of the %s projection to %s" % (len(rot["angles"]), opts.mip_mode, opts.rot_dir), flush=True)
     if opts.sts_dir is not None:
         from PIL import Image

@@ -2,6 +2,7 @@
 
     python scripts/project_bench.py kernels     # one ctg_project_accumulate call (all three axes) vs the stock-torch composition
     python scripts/project_bench.py series      # SeriesTranslator on a 256-slice 512 x 512 volume, project="max" vs project=None
+    python scripts/project_bench.py kernels --depth      # + ctg_project_accumulate_depth / ctg_project_finish_depth beside the plain calls
 
 `kernels`: a (16, 512, 512) int16 chunk, mode max, whole-volume axial slab; the composition is `torch.amax` over each of the
 three dims plus `torch.maximum` into the running axial plane (and the row stores into the coronal / sagittal arrays).  Device
@@ -21,7 +22,7 @@ def _digest():
     return build._digest()[:16]
 
 
-def kernels(reps=200, rounds=5):
+def kernels(reps=200, rounds=5, depth=False):
     from cta_gan_amd import ops
     k, s = 16, 512
     pix = torch.randint(-1024, 3072, (k, s, s), generator=torch.Generator().manual_seed(0), dtype=torch.int16).cuda()
@@ -51,6 +52,11 @@ def kernels(reps=200, rounds=5):
     def coronal_only():
         ops.project_accumulate(pix, 0, k, 0, coronal=acc["coronal"])
 
+    keyed = {a: torch.empty_like(t) for a, t in acc.items()}
+
+    def with_depth():
+        ops.project_accumulate_depth(pix, 0, k, 0, **keyed)
+
     clear()
     fused()
     composed()
@@ -58,6 +64,15 @@ def kernels(reps=200, rounds=5):
     fns = (("project_accumulate (3 axes)", fused), ("torch composition", composed),
            ("project_accumulate (axial + sagittal)", rows_only),
            ("project_accumulate (coronal)", coronal_only))
+    if depth:
+        for t in keyed.values():
+            t.fill_(ops.PROJECT_DEPTH_IDENTITY[0])
+        with_depth()
+        extent = {"axial": (k, k), "coronal": (s, s), "sagittal": (s, s)}
+        print("depth: same values %s" % " ".join("%s %s" % (a, torch.equal(
+            ops.project_finish_depth(keyed[a], 0, *extent[a], want_level=False, want_depth=False, want_cued=False)[0],
+            ops.project_finish(acc[a], 0, want_level=False)[0])) for a in acc), flush=True)
+        fns += (("project_accumulate_depth (3 axes)", with_depth),)
     for _, fn in fns:
         for _ in range(20):
             fn()
@@ -94,6 +109,22 @@ def kernels(reps=200, rounds=5):
     torch.cuda.synchronize()
     print("project_finish: %.1f us for the three projections of a 256-slice volume (3 launches, 6 allocations)"
           % (e0.elapsed_time(e1) * 1e3 / reps))
+    if depth:
+        other = min(times["project_accumulate_depth (3 axes)"])
+        print("project_accumulate_depth %.1f us best window: %.3f x the plain call" % (other, other / best))
+        extent = {"axial": (256, 256), "coronal": (s, s), "sagittal": (s, s)}
+        for _ in range(5):
+            for a, t in big.items():
+                ops.project_finish_depth(t, 0, *extent[a], cue=128)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            for a, t in big.items():
+                ops.project_finish_depth(t, 0, *extent[a], cue=128)
+        e1.record()
+        torch.cuda.synchronize()
+        print("project_finish_depth: %.1f us for the same three accumulators, four planes each (3 launches, 12 allocations)"
+              % (e0.elapsed_time(e1) * 1e3 / reps))
 
 
 def series(n=256, s=512, batch=16, rounds=4):
@@ -128,4 +159,7 @@ def series(n=256, s=512, batch=16, rounds=4):
 
 if __name__ == "__main__":
     print("build digest", _digest(), flush=True)
-    {"kernels": kernels, "series": series}[sys.argv[1]]()
+    if sys.argv[1] == "kernels":
+        kernels(depth="--depth" in sys.argv[2:])
+    else:
+        series()

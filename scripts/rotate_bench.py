@@ -3,13 +3,16 @@
     python scripts/rotate_bench.py kernel      # one ctg_project_rotate launch vs the stock-torch composition, same tensors
     python scripts/rotate_bench.py series      # SeriesTranslator on a 256-slice 512 x 512 volume, rotate=36 against rotate=None
     ... [--sampling nearest|bilinear] [--oversample S] [--reps N]      # the rays of either leg (default: nearest, unit steps)
+    python scripts/rotate_bench.py kernel --depth [--cue C]      # + one ctg_project_rotate_depth launch (all four planes) beside it
 
 `kernel`: a chunk of 16 x 512 x 512 int16, A = 36 view angles, D = 725, max, values and level.  The composition gathers
 `vol[:, yi, xi]` by the same integer tables (precomputed on the device, outside the timed window, as one linear index and one
 mask per angle), masks, takes `amax` over the ray and fills the empty rays: the values only, bit-equal (checked first); it
 materialises a [K, U, T] tensor per angle.  Device events around back-to-back calls, alternating the two.  With --sampling
 bilinear there is no composition to compare with: the launch is timed alone.  `series`: batch 16,
-bf16, host volume in pageable memory, the two translators alternating inside every round.  Both print the build digest."""
+bf16, host volume in pageable memory, the two translators alternating inside every round.  Both print the build digest.
+--depth adds the depth launch (values, level, depth, cued) as a third leg of the same alternation, after checking that its values
+and levels are the plain launch's."""
 import argparse
 import os
 import sys
@@ -24,7 +27,7 @@ def _digest():
     return build._digest()[:16]
 
 
-def kernel(reps=50, torch_reps=3, rounds=5, k=16, s=512, count=36, sampling="nearest", oversample=1):
+def kernel(reps=50, torch_reps=3, rounds=5, k=16, s=512, count=36, sampling="nearest", oversample=1, depth=False, cue=128):
     from cta_gan_amd import ops
     from cta_gan_amd.infer import default_detector, rotation_coefficients, view_angles
     d = default_detector(s, s)
@@ -57,8 +60,20 @@ def kernel(reps=50, torch_reps=3, rounds=5, k=16, s=512, count=36, sampling="nea
             out.append(torch.where(seen, torch.where(ok, g, lowest).amax(dim=2), air))
         return torch.stack(out)
 
+    planes = {"values": torch.empty_like(values), "level": torch.empty_like(level), "depth": torch.empty_like(values),
+              "cued": torch.empty_like(level)} if depth else None
+
+    def with_depth():
+        ops.project_rotate_depth(vol, 0, table, steps, "max", cue=cue, sampling=sampling, **planes)
+
     print("sampling %s, %d step(s) per voxel: %d steps per ray" % (sampling, oversample, steps), flush=True)
     fns = (("project_rotate (1 launch)", fused, reps),)
+    if depth:
+        fused()
+        with_depth()
+        print("depth launch: same values %s, same level %s" % (torch.equal(planes["values"], values), torch.equal(planes["level"], level)),
+              flush=True)
+        fns += (("project_rotate_depth (1 launch)", with_depth, reps),)
     if sampling == "nearest":
         print("same values: %s" % torch.equal(fused(), composed()), flush=True)
         fns += (("torch composition", composed, torch_reps),)
@@ -81,6 +96,10 @@ def kernel(reps=50, torch_reps=3, rounds=5, k=16, s=512, count=36, sampling="nea
     best = min(times["project_rotate (1 launch)"])
     samples = count * k * d * steps
     print("project_rotate: %.1f us best window, %.1f G samples/s over %d samples" % (best, samples / best / 1e3, samples), flush=True)
+    if depth:
+        other = min(times["project_rotate_depth (1 launch)"])
+        print("project_rotate_depth (cue %d, four planes) %.1f us best window: %.3f x the plain launch" % (cue, other, other / best),
+              flush=True)
     if sampling == "nearest":
         other = min(times["torch composition"])
         print("torch composition %.1f us: %.1f x" % (other, other / best), flush=True)
@@ -122,9 +141,11 @@ if __name__ == "__main__":
     ap.add_argument("--sampling", choices=["nearest", "bilinear"], default="nearest")
     ap.add_argument("--oversample", type=int, default=1)
     ap.add_argument("--reps", type=int, default=None, help="kernel: calls per timed window (default 50)")
+    ap.add_argument("--depth", action="store_true", help="kernel: also time ctg_project_rotate_depth on the same chunk")
+    ap.add_argument("--cue", type=int, default=128, help="kernel: the depth cue of the --depth leg")
     o = ap.parse_args()
     print("build digest", _digest(), flush=True)
     if o.leg == "kernel":
-        kernel(sampling=o.sampling, oversample=o.oversample, **({} if o.reps is None else {"reps": o.reps}))
+        kernel(sampling=o.sampling, oversample=o.oversample, depth=o.depth, cue=o.cue, **({} if o.reps is None else {"reps": o.reps}))
     else:
         series(sampling=o.sampling, oversample=o.oversample)

@@ -481,6 +481,157 @@ def rotate_volume(volume, angles, mode="max", detector=None, fill=None, wc=50.0,
     return {k: None if t is None else (t.cpu().numpy() if is_np else t.cpu()) for k, t in out.items()}
 
 
+def transfer_function(points, oversample=1):
+    """The transfer table of `SeriesRenderer` / `ops.project_render` from control points: a sequence of (level, r, g, b, opacity)
+    with levels strictly ascending in 0 .. 255, colours in 0 .. 255 and opacity in 0.0 .. 1.0.  Every channel is interpolated
+    linearly over the classes 0 .. 255 in float64 (np.interp: the first and last point extend to the ends); colours round by
+    floor(x + 0.5).  oversample = s: a ray that takes s steps per voxel meets s samples where it met one, so the opacity is
+    corrected per step, a_s = 1 - (1 - a) ** (1 / s) (s = 1 changes nothing), and alpha = floor(a_s * 32768 + 0.5), 32768 = opaque.
+    Returns uint16 [256, 4]: R, G, B, alpha."""
+    if isinstance(oversample, bool) or not isinstance(oversample, (int, np.integer)) or oversample < 1:
+        raise ValueError("transfer_function: oversample: an integer >= 1 expected, got %r" % (oversample,))
+    try:
+        pts = np.array([[float(v) for v in p] for p in points], dtype=np.float64)
+    except (TypeError, ValueError):
+        pts = np.zeros((0, 5))
+    if pts.ndim != 2 or pts.shape[0] < 1 or pts.shape[1] != 5 or not np.isfinite(pts).all():
+        raise ValueError("transfer_function: a sequence of (level, r, g, b, opacity) points expected, got %r" % (points,))
+    lv = pts[:, 0]
+    if (lv != np.floor(lv)).any() or lv.min() < 0 or lv.max() > 255 or (np.diff(lv) <= 0).any():
+        raise ValueError("transfer_function: whole levels in 0 .. 255, strictly ascending, expected, got %s" % lv.tolist())
+    if pts[:, 1:4].min() < 0 or pts[:, 1:4].max() > 255 or pts[:, 4].min() < 0 or pts[:, 4].max() > 1:
+        raise ValueError("transfer_function: colours in 0 .. 255 and opacities in 0.0 .. 1.0 expected")
+    classes = np.arange(256, dtype=np.float64)
+    lut = np.empty((256, 4), dtype=np.uint16)
+    for c in range(3):
+        lut[:, c] = np.floor(np.interp(classes, lv, pts[:, 1 + c]) + 0.5).astype(np.uint16)
+    a = np.interp(classes, lv, pts[:, 4])
+    if int(oversample) > 1:
+        a = 1.0 - (1.0 - a) ** (1.0 / int(oversample))
+    lut[:, 3] = np.floor(a * 32768.0 + 0.5).astype(np.uint16)
+    return lut
+
+
+# Named control points of `transfer_function`, for classes of the default transfer window (wc 300, ww 1500: about 5.9 HU per class,
+# class 0 at -450 HU).  They are data: their look cannot be judged without a display and none was at hand, so they are a first
+# guess by HU range, not tuned (DESIGN.md).
+TRANSFER_PRESETS = {
+    # R = G = B = the class, opacity a ramp
+    "grey": [(0, 0, 0, 0, 0.0), (255, 255, 255, 255, 1.0)],
+    # soft tissue (below about 110 HU) transparent, contrast-filled lumen red and near-opaque, bone pale and opaque
+    "vessels": [(0, 0, 0, 0, 0.0), (95, 150, 60, 50, 0.0), (115, 210, 40, 30, 0.6), (150, 235, 50, 35, 0.9), (185, 240, 230, 200, 1.0),
+                (255, 255, 255, 240, 1.0)],
+    # everything below about 400 HU transparent, bone pale and opaque
+    "bone": [(0, 0, 0, 0, 0.0), (145, 150, 120, 90, 0.0), (185, 230, 215, 180, 0.8), (255, 255, 255, 245, 1.0)],
+}
+
+
+def _transfer_table(who, transfer, oversample):
+    """`transfer` of SeriesRenderer -> uint16 [256, 4]: a preset name, a point list (both through `transfer_function` with the
+    renderer's oversample) or a ready table (taken as it is: whoever made it corrected it)."""
+    if isinstance(transfer, str):
+        if transfer not in TRANSFER_PRESETS:
+            raise ValueError("%s: transfer %r is not one of %s" % (who, transfer, tuple(TRANSFER_PRESETS)))
+        return transfer_function(TRANSFER_PRESETS[transfer], oversample)
+    table = transfer.cpu().numpy() if torch.is_tensor(transfer) else transfer
+    if isinstance(table, np.ndarray) and table.shape == (256, 4):
+        return table
+    return transfer_function(transfer, oversample)
+
+
+class SeriesRenderer:
+    """Volume-rendered rotating views of an int16 volume [n, h, w] that arrives in chunks on the device: the rays, angles,
+    detector, sampling and oversample of `SeriesRotator`, composited front to back instead of reduced to a maximum, so that what
+    lies in front hides what lies behind.  A sample's class is its 8-bit level in the transfer window (wc, ww) (with `hu` as
+    everywhere); `transfer` -- a name of TRANSFER_PRESETS, a point list for `transfer_function` (both corrected for `oversample`)
+    or a ready [256, 4] table -- gives every class its colour and alpha.  A ray ends once its transparency is down to `stop`
+    (of 32768); `surface` (1 .. 32768) is the accumulated opacity whose first step the depth plane records.  `update(pix_chunk,
+    n0)` in any order, every slice once: a chunk finishes its own rows of every angle in one launch (`ops.project_render`);
+    `result()` -> {"rgb": uint8 [A, n, U, 3], "opacity": uint8 [A, n, U], "depth": int16 [A, n, U] (absent with depth=False; -1
+    where the ray never reaches `surface`; `ray_voxel` maps a hit back to the pixel), "angles": float64 [A]} on the device.  Exact
+    integer arithmetic on the current stream: equal to numpy bit for bit."""
+
+    def __init__(self, n, h, w, angles, transfer="vessels", detector=None, wc=300.0, ww=1500.0, hu=False, sampling="nearest",
+                 oversample=1, background=(0, 0, 0), stop=128, surface=16384, depth=True, device=None):
+        _check_sampling("SeriesRenderer", sampling, oversample)
+        self.sampling, self.oversample = sampling, int(oversample)
+        self.n, self.h, self.w = int(n), int(h), int(w)
+        if min(self.n, self.h, self.w) < 1:
+            raise ValueError("SeriesRenderer: a volume of at least one voxel expected")
+        self.angles = [float(a) for a in angles]
+        if not 1 <= len(self.angles) <= ops.ROTATE_MAX_DIM:
+            raise ValueError("SeriesRenderer: 1 .. %d view angles expected, got %d" % (ops.ROTATE_MAX_DIM, len(self.angles)))
+        self.background = tuple(background)
+        if len(self.background) != 3 or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v <= 255
+                                            for v in self.background):
+            raise ValueError("SeriesRenderer: background: three integers in 0 .. 255 expected, got %r" % (background,))
+        self.background = tuple(int(v) for v in self.background)
+        for name, v, lo in (("stop", stop, 0), ("surface", surface, 1)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= lo + ops.RENDER_OPAQUE - 1:
+                raise ValueError("SeriesRenderer: %s: an integer in %d .. %d expected, got %r" % (name, lo, lo + ops.RENDER_OPAQUE - 1, v))
+        self.stop, self.surface = int(stop), int(surface)
+        d = default_detector(self.h, self.w)
+        self.u, self.t = (d, d) if detector is None else _pair(detector)
+        self.steps = self.t * self.oversample
+        self.hu, self.window = bool(hu), (float(wc), float(ww))
+        lut = _transfer_table("SeriesRenderer", transfer, self.oversample)
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("SeriesRenderer: a GPU device is required (no CPU fallback)")
+        self.table = ops.RotateTable([rotation_coefficients(a, self.h, self.w, self.u, self.t, self.oversample)
+                                      for a in self.angles], self.device)
+        self.lut = ops.TransferTable(lut, self.device)
+        shape = (len(self.angles), self.n, self.u)
+        self.rgb = torch.empty(shape + (3,), dtype=torch.uint8, device=self.device)
+        self.opacity = torch.empty(shape, dtype=torch.uint8, device=self.device)
+        self.depth_plane = torch.empty(shape, dtype=torch.int16, device=self.device) if depth else None
+        self._angles = torch.tensor(self.angles, dtype=torch.float64, device=self.device)
+
+    def reset(self):
+        """Nothing to refill (every update writes whole rows); kept for symmetry with `SeriesProjector`."""
+
+    def update(self, pix_chunk, n0):
+        k = pix_chunk.shape[0]
+        if tuple(pix_chunk.shape[1:]) != (self.h, self.w) or int(n0) < 0 or int(n0) + k > self.n:
+            raise RuntimeError("SeriesRenderer: chunk %s at slice %d does not lie in the volume (%d, %d, %d)"
+                               % (tuple(pix_chunk.shape), int(n0), self.n, self.h, self.w))
+        if k < 1:
+            return
+        ops.project_render(pix_chunk, int(n0), self.table, self.steps, self.lut, rgb=self.rgb, opacity=self.opacity,
+                           depth=self.depth_plane, background=self.background, stop=self.stop, surface=self.surface,
+                           wc=self.window[0], ww=self.window[1], hu=self.hu, sampling=self.sampling)
+
+    def result(self):
+        out = {"rgb": self.rgb, "opacity": self.opacity, "angles": self._angles}
+        if self.depth_plane is not None:
+            out["depth"] = self.depth_plane
+        return out
+
+
+def render_volume(volume, angles, batch=64, device=None, **options):
+    """The volume-rendered views of a volume that already exists, the counterpart of `rotate_volume`: int16 [N, H, W], a host
+    array / CPU tensor (chunks of `batch` slices cross PCIe one after another) or a device tensor; angles: degrees, or an int
+    count of views around the full circle (`view_angles`); options: the keyword arguments of `SeriesRenderer` (transfer,
+    detector, wc, ww, hu, sampling, oversample, background, stop, surface, depth).  Returns what `SeriesRenderer.result`
+    returns, of the input's kind."""
+    is_np = isinstance(volume, np.ndarray)
+    vol = torch.from_numpy(np.ascontiguousarray(volume)) if is_np else volume
+    if not torch.is_tensor(vol) or vol.dtype != torch.int16 or vol.dim() != 3:
+        raise RuntimeError("render_volume: an int16 volume [N, H, W] expected")
+    if int(batch) < 1:
+        raise ValueError("render_volume: batch >= 1 expected")
+    on_host = not vol.is_cuda
+    n, h, w = vol.shape
+    ren = SeriesRenderer(n, h, w, _angle_list(angles), device=device if on_host else vol.device, **options)
+    with torch.cuda.device(ren.device):
+        for s, e, _ in plan_chunks(n, batch):
+            ren.update(vol[s:e].to(ren.device) if on_host else vol[s:e], s)
+        out = ren.result()
+    if not on_host:
+        return out
+    return {k: t.cpu().numpy() if is_np else t.cpu() for k, t in out.items()}
+
+
 def subtract_volume(cta, ct_hu, cta_is_hu=False, median=True, floor=0, ct_range=(None, None), wc=150.0, ww=300.0, level=True,
                     batch=64, device=None):
     """The subtraction of two volumes that already exist (a real CTA and its registered CT for a side-by-side view, or a
@@ -522,6 +673,7 @@ def subtract_volume(cta, ct_hu, cta_is_hu=False, median=True, floor=0, ct_range=
 
 
 PROJECT_SOURCES = ("cta", "sub")
+RENDER_OPTIONS = ("transfer", "detector", "wc", "ww", "hu", "sampling", "oversample", "background", "stop", "surface", "depth")
 
 
 def _angle_list(rotate):
@@ -549,6 +701,11 @@ class SeriesTranslator:
     depth=True (depth_cue: 0 .. 256) applies to whichever of `project` / `rotate` is on, with mode "max" / "min": their dicts gain
     "depth" (int16) and "cued" (uint8, the depth-cued level), as `SeriesProjector` / `SeriesRotator` give them, staged back with
     the other planes; the slabs have no depth planes.  With depth=False nothing of it is allocated or launched.
+    render = an int count of views around the full circle, or a sequence of degrees (render_options: a dict of `SeriesRenderer`
+    keyword arguments -- transfer, detector, wc, ww, hu (default: that of the source), sampling, oversample, background, stop,
+    surface, depth) adds "render": {"rgb": uint8 [A, N, D, 3], "opacity": uint8, "depth": int16 (unless depth=False), "angles":
+    float64 [A]}, the volume-rendered views of the same source (`project_source`), copied back once after the last chunk.  With
+    render=None nothing of it is allocated or launched.
 
     size: the side(s) the generator runs at (None: the volume's own); a volume of another size is resized (nearest) on the way
     in and comes back at its own size.  wc / ww: the window of the 8-bit level; hu: pixels minus 1024 (SimpleITK) instead of
@@ -558,9 +715,17 @@ class SeriesTranslator:
     def __init__(self, generator, batch=16, size=None, wc=50.0, ww=400.0, hu=False, level=True, device=None, project=None,
                  slab=None, rotate=None, rotate_mode=None, subtract=False, sub_median=True, sub_floor=0, sub_ct_range=(None, None),
                  sub_window=(150.0, 300.0), project_source="cta", slabs=None, rotate_sampling="nearest", rotate_oversample=1,
-                 depth=False, depth_cue=0):
+                 depth=False, depth_cue=0, render=None, render_options=None):
         if int(batch) < 1:
             raise ValueError("SeriesTranslator: batch >= 1 expected")
+        self.render = None if render is None else _angle_list(render)
+        self.render_options = dict(render_options or {})
+        if self.render is None and self.render_options:
+            raise ValueError("SeriesTranslator: render_options need render")
+        if self.render is not None and (not self.render or set(self.render_options) - set(RENDER_OPTIONS)):
+            raise ValueError("SeriesTranslator: render needs at least one angle, and render_options %r a dict with any of %s"
+                             % (render_options, RENDER_OPTIONS))
+        self._renderer = self._ren_host = None
         if project_source not in PROJECT_SOURCES or (project_source == "sub" and not subtract):
             raise ValueError("SeriesTranslator: project_source %r: one of %s expected, and 'sub' needs subtract=True"
                              % (project_source, PROJECT_SOURCES))
@@ -647,6 +812,7 @@ class SeriesTranslator:
             proj = self._projector_for(n, h, w)
             rot = self._rotator_for(n, h, w)
             slb = self._slabber_for(n, h, w)
+            ren = self._renderer_for(n, h, w)
             in_free = [None] * SLOTS       # event: the slot's H2D copy has drained, the host may rewrite it
             pending = [None] * SLOTS       # (event, start, stop): the slot's D2H copy, not yet moved into the result
 
@@ -700,6 +866,8 @@ class SeriesTranslator:
                         rot.update(src, s)
                     if slb is not None:
                         slb.update(src, s)
+                    if ren is not None:
+                        ren.update(src, s)
                 computed = torch.cuda.Event()
                 computed.record(cur)
                 drain(slot)                          # the chunk that used this slot last: its D2H started two chunks ago
@@ -734,6 +902,11 @@ class SeriesTranslator:
                 slab_staged = self._stage_slabs(slb.result())
                 slab_done = torch.cuda.Event()
                 slab_done.record(cur)
+            ren_done = None
+            if ren is not None:       # the finished rendered views of every angle, staged the same way
+                ren_staged = self._stage_render(ren.result())
+                ren_done = torch.cuda.Event()
+                ren_done.record(cur)
             for slot in sorted(range(SLOTS), key=lambda q: pending[q][1] if pending[q] else -1):
                 drain(slot)
             projections = None
@@ -755,6 +928,13 @@ class SeriesTranslator:
                 slab_done.synchronize()
                 stats["wait"] += clock() - t0
                 slab_out = {a: {k: t.clone().numpy() if is_np else t.clone() for k, t in d.items()} for a, d in slab_staged.items()}
+            rendered = None
+            if ren_done is not None:
+                t0 = clock()
+                ren_done.synchronize()
+                stats["wait"] += clock() - t0
+                rendered = {k: t.clone().numpy() if is_np else t.clone() for k, t in ren_staged.items()}
+                rendered["angles"] = np.array(ren.angles, dtype=np.float64) if is_np else torch.tensor(ren.angles, dtype=torch.float64)
         # the forwards above ran fused conv + InstanceNorm launches: none may have given up (raises)
         ops.nie_check("series inference")
         stats["total"] = clock() - t_call
@@ -765,6 +945,8 @@ class SeriesTranslator:
             out["rotation"] = rotation
         if slab_out is not None:
             out["slabs"] = slab_out
+        if rendered is not None:
+            out["render"] = rendered
         return out
 
     def _stage_projections(self, dev):
@@ -786,6 +968,15 @@ class SeriesTranslator:
         for k, t in dev.items():
             self._rot_host[k].copy_(t, non_blocking=True)
         return self._rot_host
+
+    def _stage_render(self, dev):
+        """Start the copies of the rendered views into page-locked buffers (kept between calls on volumes of one shape)."""
+        dev = {k: dev[k] for k in ("rgb", "opacity", "depth") if k in dev}
+        if self._ren_host is None or self._ren_host["rgb"].shape != dev["rgb"].shape or set(self._ren_host) != set(dev):
+            self._ren_host = {k: torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for k, t in dev.items()}
+        for k, t in dev.items():
+            self._ren_host[k].copy_(t, non_blocking=True)
+        return self._ren_host
 
     def _stage_slabs(self, dev):
         """Start the copies of the finished slab planes into page-locked buffers (kept between calls on volumes of one shape)."""
@@ -809,6 +1000,17 @@ class SeriesTranslator:
         else:
             s.reset()
         return s
+
+    def _renderer_for(self, n, h, w):
+        """The renderer of an (n, h, w) volume, kept between calls on volumes of one shape; None without `render`."""
+        if self.render is None:
+            return None
+        r = self._renderer
+        if r is None or (r.n, r.h, r.w) != (n, h, w):
+            options = dict(self.render_options)
+            options.setdefault("hu", self._view_hu())
+            r = self._renderer = SeriesRenderer(n, h, w, self.render, device=self.device, **options)
+        return r
 
     def _rotator_for(self, n, h, w):
         """The rotator of an (n, h, w) volume, kept between calls on volumes of one shape; None without `rotate`."""

@@ -1901,6 +1901,99 @@ def project_rotate_depth(pix, n0, coef, t, mode, values=None, level=None, depth=
                "ctg_project_rotate_depth")
 
 
+# ---------------------------------------------------------------------------- volume-rendered views (csrc/project_render.hip)
+RENDER_OPAQUE = 32768      # the alpha of an opaque class, and the transparency a ray starts from
+
+
+class TransferTable:
+    """The transfer table of `project_render`: (256, 4) integers in 0 .. 65535 -- R, G, B, alpha of every 8-bit class -- checked
+    on the host and uploaded once as uint16.  The kernel reads min(R, 255), min(G, 255), min(B, 255) and min(alpha, 32768), with
+    32768 = opaque (`infer.transfer_function` makes such tables).  `.host`: the numpy table, `.dev`: its device copy."""
+
+    def __init__(self, lut, device=None):
+        import numpy as np
+        host = np.asarray(lut.cpu() if torch.is_tensor(lut) else lut)
+        if host.shape != (256, 4) or host.dtype.kind not in "iu":
+            raise RuntimeError("project_render: a transfer table of 256 x 4 integers expected, got %s %s" % (host.dtype, tuple(host.shape)))
+        if host.min() < 0 or host.max() > 65535:
+            raise RuntimeError("project_render: transfer table values in 0 .. 65535 expected")
+        self.host = np.ascontiguousarray(host.astype(np.uint16))
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("project_render: a GPU device is required (no CPU fallback)")
+        self.dev = torch.from_numpy(self.host.view(np.int16)).to(self.device).view(torch.uint16)
+
+
+def _render_out(t, dtype, dims, name):
+    if t is None:
+        return
+    if not torch.is_tensor(t) or not t.is_cuda or t.dtype != dtype or not t.is_contiguous() or t.dim() != dims \
+            or (dims == 4 and t.shape[3] != 3):
+        raise RuntimeError("project_render: %s must be a contiguous %s tensor (A, N, U%s) on the GPU" % (name, dtype, ", 3" if dims == 4 else ""))
+
+
+def _render_int(who, name, v, lo, hi):
+    if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+        raise RuntimeError("%s: %s: an integer in %d .. %d expected, got %r" % (who, name, lo, hi, v))
+    return v
+
+
+def project_render(pix, n0, coef, t, lut, rgb=None, opacity=None, depth=None, background=(0, 0, 0), stop=128, surface=16384,
+                   wc=50.0, ww=400.0, hu=False, sampling="nearest"):
+    """One chunk of an int16 volume into its volume-rendered views, in place, one launch of ctg_project_render: pix, n0, coef, t,
+    hu and sampling as `project_rotate`; lut: an `ops.TransferTable`, or a host table (256, 4) that is checked and uploaded by
+    this call; (wc, ww): the window that sorts a sample into its class 0 .. 255 (the transfer function's, not a display window).
+    Every ray is composited front to back over its counted samples -- wgt = (Tr A) >> 15, C += wgt colour, Tr -= wgt from
+    Tr = 32768 -- and ends once Tr <= stop (0 .. 32767).  rgb uint8 (A, N, U, 3): (C + background Tr + 16384) >> 15; opacity
+    uint8 (A, N, U): ((32768 - Tr) 255 + 16384) >> 15; depth int16 (A, N, U): the first step at which the accumulated opacity
+    reaches `surface` (1 .. 32768), -1 if never.  Any of the three may be None, not all; the call writes rows n0 .. n0+K-1 and
+    nothing else.  Exact integer arithmetic: equal to numpy bit for bit."""
+    lib = _lib.load()
+    who = "project_render"
+    if not torch.is_tensor(pix) or not pix.is_cuda:
+        raise RuntimeError("%s: CPU tensors are not supported (no CPU fallback)" % who)
+    if pix.dtype != torch.int16 or pix.dim() != 3:
+        raise RuntimeError("%s: pix must be int16 (K, H, W), got %s %s" % (who, pix.dtype, tuple(pix.shape)))
+    if sampling not in _ROTATE_SAMPLING_CODES:
+        raise RuntimeError("%s: sampling %r is not one of %s" % (who, sampling, tuple(_ROTATE_SAMPLING_CODES)))
+    stop = _render_int(who, "stop", stop, 0, RENDER_OPAQUE - 1)
+    surface = _render_int(who, "surface", surface, 1, RENDER_OPAQUE)
+    try:
+        bg = tuple(background)
+    except TypeError:
+        bg = ()
+    if len(bg) != 3:
+        raise RuntimeError("%s: background: three integers in 0 .. 255 expected, got %r" % (who, background))
+    bg = tuple(_render_int(who, "background", v, 0, 255) for v in bg)
+    _render_out(rgb, torch.uint8, 4, "rgb")
+    _render_out(opacity, torch.uint8, 3, "opacity")
+    _render_out(depth, torch.int16, 3, "depth")
+    given = [o for o in (rgb, opacity, depth) if o is not None]
+    if not given:
+        raise RuntimeError("%s: at least one of rgb, opacity, depth expected" % who)
+    if any(o.shape[:3] != given[0].shape[:3] for o in given):
+        raise RuntimeError("%s: the outputs differ in shape: %s" % (who, [tuple(o.shape) for o in given]))
+    if (torch.is_tensor(coef) and coef.is_cuda) or (torch.is_tensor(lut) and lut.is_cuda):
+        raise RuntimeError("%s: the tables are checked on the host: pass host tables or an ops.RotateTable / ops.TransferTable" % who)
+    table = coef if isinstance(coef, RotateTable) else RotateTable(coef, pix.device)
+    transfer = lut if isinstance(lut, TransferTable) else TransferTable(lut, pix.device)
+    if any(o.device != pix.device for o in given + [table.dev, transfer.dev]):
+        raise RuntimeError("%s: pix, the two tables and the outputs must live on one device" % who)
+    a, n, u = given[0].shape[:3]
+    x = pix.contiguous()
+    k, h, w = x.shape
+    n0, t = int(n0), int(t)
+    if a != table.count:
+        raise RuntimeError("%s: %d planes for a table of %d angles" % (who, a, table.count))
+    if k < 1 or n0 < 0 or n0 + k > n:
+        raise RuntimeError("%s: chunk of %d slices at slice %d does not lie in the volume of %d" % (who, k, n0, n))
+    if not (1 <= min(h, w, u, t) and max(h, w, u, t) <= ROTATE_MAX_DIM):
+        raise RuntimeError("%s: H, W, U, T in 1 .. %d expected, got %d %d %d %d" % (who, ROTATE_MAX_DIM, h, w, u, t))
+    _lib.check(lib.ctg_project_render(_p(x), k, h, w, n0, n, _p(table.dev), a, u, t, _p(transfer.dev), _ROTATE_SAMPLING_CODES[sampling],
+                                      stop, surface, bg[0], bg[1], bg[2], float(wc), float(ww), int(bool(hu)), _p(rgb), _p(opacity),
+                                      _p(depth), _stream()), "ctg_project_render")
+
+
 def project_accumulate_depth(pix, n0, thick, mode, axial=None, coronal=None, sagittal=None):
     """`project_accumulate` on keyed accumulators (value and depth of the maximum in one 32-bit word, include/ctagan_hip.h): the
     same arguments and shapes, int32 tensors that the caller fills with PROJECT_DEPTH_IDENTITY[mode] before the first chunk; mode

@@ -552,6 +552,36 @@ int ctg_project_accumulate_depth(const short* pix, int K, int H, int W, int n0, 
 int ctg_project_finish_depth(const int* acc, int planes, long plane_items, int mode, int thick, int extent, int cue, float wc,
                              float ww, int hu, short* values, unsigned char* level, short* depth, unsigned char* cued, void* stream);
 
+/* ---- series inference, the volume-rendered rotating view (added under ABI 15: purely additive, no existing signature or meaning
+ * moves, so the version stays 15): front-to-back compositing along the rays of the rotating projections, the display that keeps
+ * the depth a MIP throws away.  cta_gan_amd/infer.py: SeriesRenderer, render_volume, SeriesTranslator(render=...),
+ * transfer_function; ops.project_render, ops.TransferTable.  The reference has no counterpart.
+ * ctg_project_render: pix, K, H, W, n0, N, coef, A, U, T, wc, ww, hu and stream, the table, the detector, the interval, the
+ *   "counted" rule and the rows written are those of ctg_project_rotate_depth; sampling 0 = nearest (the pixel), 1 = bilinear (the
+ *   value of ctg_project_rotate_bilinear).  An uncounted sample takes no part.
+ *   Classification: a counted sample of value v has the class l = the 8-bit window level of v in the window (wc, ww) -- the
+ *     transfer function's own window, independent of any display window -- with `hu` as everywhere (v + 1024 is the stored value):
+ *     a whole number 0 .. 255.  lut = uint16 [256][4] on the device, 2-byte aligned: R, G, B, alpha of every class.  The kernel
+ *     uses min(R, 255), min(G, 255), min(B, 255) and A = min(alpha, 32768); A = 32768 is opaque, so any table is defined.
+ *   Compositing: over the ray's counted samples in ascending step t, from Tr = 32768 and C[3] = 0, all uint32:
+ *       wgt = (Tr A) >> 15;   C[c] += wgt col[c]  (c = R, G, B);   Tr -= wgt;
+ *       if depth < 0 and 32768 - Tr >= surface: depth = t;     if Tr <= stop: the ray ends (later samples take no part)
+ *     wgt <= Tr; the weights sum to 32768 - Tr, hence C[c] <= 32768 * 255: nothing overflows and every output fits 8 bits.
+ *     stop in 0 .. 32767 is part of the definition (0: only an opaque sample ends a ray); surface in 1 .. 32768.
+ *   Outputs, any subset, at least one, each [A][N][U] (rows n0 .. n0+K-1 are written, nothing else):
+ *     rgb uint8 [A][N][U][3]: (C[c] + bg_c Tr + 16384) >> 15, the background bg_r, bg_g, bg_b in 0 .. 255;
+ *     opacity uint8: ((32768 - Tr) 255 + 16384) >> 15;
+ *     depth int16 (2-byte aligned): the step of the first counted sample at which the accumulated opacity 32768 - Tr reaches
+ *     `surface`, -1 if it never does.  A ray that misses the slice gives bg, opacity 0 and depth -1.
+ *   Oversampled rays are a matter of the tables: T = t s steps, and the host corrects the alphas per step when it builds lut.
+ *   Exact integer arithmetic: the same bits as numpy (tests/render_np.py).  One launch, no accumulator, no atomics.
+ *   CTG_EINVAL, nothing launched: a null pix, coef or lut; no output; K < 1, n0 < 0, n0 + K > N; H, W, U, T or A outside
+ *   1 .. 4096; sampling outside 0 .. 1; stop outside 0 .. 32767; surface outside 1 .. 32768; a bg outside 0 .. 255; pix, lut or
+ *   depth not 2-byte aligned, coef not 4-byte aligned; a grid beyond 2^31 - 1 workgroups. ---- */
+int ctg_project_render(const short* pix, int K, int H, int W, int n0, int N, const int* coef, int A, int U, int T,
+                       const unsigned short* lut, int sampling, int stop, int surface, int bg_r, int bg_g, int bg_b, float wc,
+                       float ww, int hu, unsigned char* rgb, unsigned char* opacity, short* depth, void* stream);
+
 /* ---- LPIPS (AlexNet, lpips 0.1) of the test() loops (ABI 14): `loss_fn_alex = lpips.LPIPS(net='alex')` (trainer/HdTrainer.py:26-28)
  * and its calls `loss_fn_alex.forward(torch.tensor(c), torch.tensor(b))` on the windowed and on the raw masked pair of every slice
  * (HdTrainer.py:504-513, 531-536, 1029-1031, 1054-1056; the twins in CycTrainer.py, p2pTrainer.py, RegTrainer.py).  The five

@@ -11,6 +11,8 @@
                       [--sub-output sub.npy [--sub-level-dir DIR] [--sub-floor 0] [--sub-no-median] [--sub-ct-min HU]
                        [--sub-ct-max HU] [--sub-wc 150 --sub-ww 300] [--mip-source cta|sub]]
                       [--depth [--depth-cue C]]
+                      [--vr-dir DIR [--vr-angles 36] [--vr-span 360] [--vr-preset grey|vessels|bone] [--vr-wc 300 --vr-ww 1500]
+                       [--vr-sampling nearest|bilinear] [--vr-oversample S] [--vr-background R,G,B] [--aspect R]]
 
 --input: int16 [N, H, W] .npy in SimpleITK's convention (what the reference's loaders read from the DICOMs); --weights: the
 reference-format `state_dict` of Model.HdGan.Generator (what train() saves as netG_A2B*.pth).  --output receives the int16
@@ -36,7 +38,7 @@ axial_%03d.png [H, W], coronal_%03d.png [round(N R), W] and sagittal_%03d.png [r
 device while the volume is made: the pair is registered by construction, so bone cancels.  A 3 x 3 in-plane median unless
 --sub-no-median; differences below --sub-floor, and pixels whose input HU lies outside --sub-ct-min .. --sub-ct-max (default:
 open), become 0.  --sub-level-dir: one 8-bit PNG per slice in the window --sub-wc / --sub-ww of a HU difference.  --mip-source
-sub makes --mip-dir, --rot-dir and --sts-dir show the subtraction volume (levels in the --sub window) instead of the synthesized one: the
+sub makes --mip-dir, --rot-dir, --sts-dir and --vr-dir show the subtraction volume (levels in the --sub window) instead of the synthesized one: the
 bone-free MIP.
 --depth (with --mip-dir and / or --rot-dir, --mip-mode max or min): the depth of the maximum.  rotation.npz gains depth (int16
 [A, N, D]: the step along the ray, counted from the viewer's end, at which the value was found; -1 where the ray misses the
@@ -44,6 +46,14 @@ slice) and projections.npz gains axial_depth, coronal_depth and sagittal_depth (
 --depth-cue C (0 .. 256, default 0) also adds the depth-cued levels (cued; axial_cued, coronal_cued, sagittal_cued): the level
 attenuated by up to C / 256 toward the far end of the ray, which tells front from back in the rotating view; with C > 0 the PNGs
 are written from them.  Without --depth every output is what it was.
+--vr-dir: the volume-rendered rotating view of the same source (--mip-source), --vr-angles views over --vr-span degrees, made on
+the device while the volume is made: every ray is composited front to back, so what lies in front hides what lies behind.  A
+sample's class is its 8-bit level in the transfer window --vr-wc / --vr-ww (independent of --wc / --ww); --vr-preset names the
+transfer function that gives every class its colour and opacity (cta_gan_amd/infer.py: TRANSFER_PRESETS).  --vr-sampling and
+--vr-oversample as --rot-sampling and --rot-oversample (the opacities are corrected per step); --vr-background R,G,B (0 .. 255)
+shows through where a ray stays transparent.  vr_%03d.png, one RGB frame [round(N R), D] per angle, and render.npz with rgb
+(uint8 [A, N, D, 3]), opacity (uint8), depth (int16: the step at which a ray becomes half opaque, -1 if never), angles and lut
+(the uint16 [256, 4] transfer table that was used).
 DICOM reading and writing are not part of this build.
 """
 import argparse
@@ -51,6 +61,7 @@ import os
 
 DTYPES = ["fp32", "bf16", "bf16x3", "bf16x3f"]
 DEFAULT_DTYPE = "bf16x3"      # train.py's default
+VR_PRESETS = ["grey", "vessels", "bone"]      # the names of cta_gan_amd.infer.TRANSFER_PRESETS (not imported here: --help needs no torch)
 
 
 def build_parser():
@@ -75,6 +86,15 @@ def build_parser():
     parser.add_argument("--rot-oversample", type=int, default=1, help="steps per voxel along a ray (with --rot-dir)")
     parser.add_argument("--depth", action="store_true", help="also record the depth of the maximum (with --mip-dir / --rot-dir)")
     parser.add_argument("--depth-cue", type=int, default=0, help="0 .. 256: attenuate the levels by depth (with --depth)")
+    parser.add_argument("--vr-dir", type=str, default=None, help="also write the volume-rendered rotating view here")
+    parser.add_argument("--vr-angles", type=int, default=36, help="view angles of the rendered view (with --vr-dir)")
+    parser.add_argument("--vr-span", type=float, default=360.0, help="degrees the view angles are spread over (with --vr-dir)")
+    parser.add_argument("--vr-preset", choices=VR_PRESETS, default="vessels", help="transfer function (with --vr-dir)")
+    parser.add_argument("--vr-wc", type=float, default=300.0, help="centre of the transfer function's window (with --vr-dir)")
+    parser.add_argument("--vr-ww", type=float, default=1500.0, help="width of the transfer function's window (with --vr-dir)")
+    parser.add_argument("--vr-sampling", choices=["nearest", "bilinear"], default="nearest", help="how a ray samples the slice (with --vr-dir)")
+    parser.add_argument("--vr-oversample", type=int, default=1, help="steps per voxel along a ray (with --vr-dir)")
+    parser.add_argument("--vr-background", type=str, default="0,0,0", help="R,G,B in 0 .. 255 behind the rendered view (with --vr-dir)")
     parser.add_argument("--sts-dir", type=str, default=None, help="also write the sliding thin-slab projections here")
     parser.add_argument("--sts-thick", type=str, default=None, help="voxels per slab: T, or T,Tc,Ts for axial,coronal,sagittal")
     parser.add_argument("--sts-step", type=str, default=None, help="voxels a slab moves on: S or S,Sc,Ss (default: the thickness)")
@@ -140,6 +160,14 @@ def parse_args(argv=None):
         parser.error("--depth-cue needs --depth")
     if opts.depth and (opts.mip_mode == "mean" or (opts.mip_dir is None and opts.rot_dir is None)):
         parser.error("--depth needs --mip-dir or --rot-dir and --mip-mode max or min (a mean has no depth)")
+    try:
+        opts.vr_background = tuple(int(v) for v in opts.vr_background.split(","))
+    except ValueError:
+        parser.error("--vr-background: whole numbers R,G,B expected, got %r" % opts.vr_background)
+    if len(opts.vr_background) != 3 or not all(0 <= v <= 255 for v in opts.vr_background):
+        parser.error("--vr-background: three values R,G,B in 0 .. 255 expected")
+    if opts.vr_angles < 1 or opts.vr_oversample < 1:
+        parser.error("--vr-angles and --vr-oversample: at least 1 expected")
     return opts
 
 
@@ -172,7 +200,13 @@ def main(argv=None):
     device = torch.device("cuda", torch.cuda.current_device())
     generator = Generator(config["input_nc"], config["output_nc"]).to(device)
     generator.load_state_dict(torch.load(opts.weights, map_location=device))
-    translate = SeriesTranslator(generator, batch=opts.batch, size=config.get("size"), wc=opts.wc, ww=opts.ww, hu=opts.hu,
+    vr_lut = vr_options = None
+    if opts.vr_dir is not None:      # the table is made here, corrected for the oversampling, so that render.npz can record it
+        from cta_gan_amd.infer import TRANSFER_PRESETS, transfer_function
+        vr_lut = transfer_function(TRANSFER_PRESETS[opts.vr_preset], opts.vr_oversample)
+        vr_options = {"transfer": vr_lut, "wc": opts.vr_wc, "ww": opts.vr_ww, "sampling": opts.vr_sampling,
+                      "oversample": opts.vr_oversample, "background": opts.vr_background}
+    translate =SeriesTranslator(generator, batch=opts.batch, size=config.get("size"), wc=opts.wc, ww=opts.ww, hu=opts.hu,
                                  level=opts.level_dir is not None or opts.sub_level_dir is not None, device=device,
                                  subtract=opts.sub_output is not None, sub_median=not opts.sub_no_median, sub_floor=opts.sub_floor,
                                  sub_ct_range=(opts.sub_ct_min, opts.sub_ct_max), sub_window=(opts.sub_wc, opts.sub_ww),
@@ -180,7 +214,9 @@ def main(argv=None):
                                  project=opts.mip_mode if opts.mip_dir is not None else None, slab=opts.slab,
                                  rotate=view_angles(opts.rot_angles, opts.rot_span) if opts.rot_dir is not None else None,
                                  rotate_mode=opts.mip_mode, rotate_sampling=opts.rot_sampling, rotate_oversample=opts.rot_oversample,
-                                 slabs=opts.sts, depth=opts.depth, depth_cue=opts.depth_cue)
+                                 slabs=opts.sts, depth=opts.depth, depth_cue=opts.depth_cue,
+                                 render=view_angles(opts.vr_angles, opts.vr_span) if opts.vr_dir is not None else None,
+                                 render_options=vr_options)
     shown = "cued" if opts.depth_cue > 0 else "level"      # the plane the PNGs of the projections are written from
     out = translate(volume)
     np.save(opts.output, out["pix"])
@@ -229,6 +265,18 @@ def main(argv=None):
             arrays["cued"] = rot["cued"]
         np.savez(os.path.join(opts.rot_dir, "rotation.npz"), **arrays)
         print("wrote %d views of the %s projection to %s" % (len(rot["angles"]), opts.mip_mode, opts.rot_dir), flush=True)
+    if opts.vr_dir is not None:
+        from PIL import Image
+        from cta_gan_amd.infer import aspect_rows
+        os.makedirs(opts.vr_dir, exist_ok=True)
+        ren = out["render"]
+        rows = aspect_rows(volume.shape[0], opts.aspect)
+        for i, frame in enumerate(ren["rgb"]):
+            Image.fromarray(np.ascontiguousarray(frame[rows])).save(      # uint8 [rows, D, 3]: mode "RGB"
+os.path.join(opts.vr_dir, "vr_%03d.png" % i))
+        np.savez(os.path.join(opts.vr_dir, "render.npz"), rgb=ren["rgb"], opacity=ren["opacity"], depth=ren["depth"],
+                 angles=ren["angles"], lut=vr_lut)
+        print("wrote %d volume-rendered views (%s) to %s" % (len(ren["angles"]), opts.vr_preset, opts.vr_dir), flush=True)
     if opts.sts_dir is not None:
         from PIL import Image
         from cta_gan_amd.infer import aspect_rows

@@ -4,6 +4,7 @@
     python scripts/rotate_bench.py series      # SeriesTranslator on a 256-slice 512 x 512 volume, rotate=36 against rotate=None
     ... [--sampling nearest|bilinear] [--oversample S] [--reps N]      # the rays of either leg (default: nearest, unit steps)
     python scripts/rotate_bench.py kernel --depth [--cue C]      # + one ctg_project_rotate_depth launch (all four planes) beside it
+    python scripts/rotate_bench.py kernel --render               # + two ctg_project_render launches (rgb, opacity, depth) beside it
 
 `kernel`: a chunk of 16 x 512 x 512 int16, A = 36 view angles, D = 725, max, values and level.  The composition gathers
 `vol[:, yi, xi]` by the same integer tables (precomputed on the device, outside the timed window, as one linear index and one
@@ -12,7 +13,10 @@ materialises a [K, U, T] tensor per angle.  Device events around back-to-back ca
 bilinear there is no composition to compare with: the launch is timed alone.  `series`: batch 16,
 bf16, host volume in pageable memory, the two translators alternating inside every round.  Both print the build digest.
 --depth adds the depth launch (values, level, depth, cued) as a third leg of the same alternation, after checking that its values
-and levels are the plain launch's."""
+and levels are the plain launch's.
+--render adds two ctg_project_render launches (rgb, opacity, depth) on the same chunk, angles and sampling to the alternation: the
+"vessels" preset in its default window with stop 128 -- on this random chunk most rays meet an opaque class within a few steps and
+end -- and a thin fog (every alpha 64 of 32768, stop 0) that no ray ever leaves early: the full-length cost of the ordered fold."""
 import argparse
 import os
 import sys
@@ -27,9 +31,10 @@ def _digest():
     return build._digest()[:16]
 
 
-def kernel(reps=50, torch_reps=3, rounds=5, k=16, s=512, count=36, sampling="nearest", oversample=1, depth=False, cue=128):
+def kernel(reps=50, torch_reps=3, rounds=5, k=16, s=512, count=36, sampling="nearest", oversample=1, depth=False, cue=128,
+           render=False):
     from cta_gan_amd import ops
-    from cta_gan_amd.infer import default_detector, rotation_coefficients, view_angles
+    from cta_gan_amd.infer import TRANSFER_PRESETS, default_detector, rotation_coefficients, transfer_function, view_angles
     d = default_detector(s, s)
     steps = d * oversample
     angles = view_angles(count)
@@ -66,8 +71,25 @@ def kernel(reps=50, torch_reps=3, rounds=5, k=16, s=512, count=36, sampling="nea
     def with_depth():
         ops.project_rotate_depth(vol, 0, table, steps, "max", cue=cue, sampling=sampling, **planes)
 
+    frames = {"rgb": torch.empty((count, k, d, 3), dtype=torch.uint8, device="cuda"), "opacity": torch.empty_like(level),
+              "depth": torch.empty_like(values)} if render else None
+    if render:
+        import numpy as np
+        preset = ops.TransferTable(transfer_function(TRANSFER_PRESETS["vessels"], oversample))
+        thin = np.zeros((256, 4), dtype=np.uint16)
+        thin[:, :3], thin[:, 3] = np.arange(256)[:, None], 64
+        thin = ops.TransferTable(thin)
+
+    def render_preset():
+        ops.project_render(vol, 0, table, steps, preset, wc=300.0, ww=1500.0, stop=128, sampling=sampling, **frames)
+
+    def render_fog():
+        ops.project_render(vol, 0, table, steps, thin, wc=300.0, ww=1500.0, stop=0, sampling=sampling, **frames)
+
     print("sampling %s, %d step(s) per voxel: %d steps per ray" % (sampling, oversample, steps), flush=True)
     fns = (("project_rotate (1 launch)", fused, reps),)
+    if render:
+        fns += (("project_render, vessels", render_preset, reps), ("project_render, thin fog", render_fog, reps))
     if depth:
         fused()
         with_depth()
@@ -100,6 +122,10 @@ def kernel(reps=50, torch_reps=3, rounds=5, k=16, s=512, count=36, sampling="nea
         other = min(times["project_rotate_depth (1 launch)"])
         print("project_rotate_depth (cue %d, four planes) %.1f us best window: %.3f x the plain launch" % (cue, other, other / best),
               flush=True)
+    if render:
+        for name in ("project_render, vessels", "project_render, thin fog"):
+            other = min(times[name])
+            print("%s (rgb, opacity, depth) %.1f us best window: %.3f x the plain launch" % (name, other, other / best), flush=True)
     if sampling == "nearest":
         other = min(times["torch composition"])
         print("torch composition %.1f us: %.1f x" % (other, other / best), flush=True)
@@ -143,9 +169,10 @@ if __name__ == "__main__":
     ap.add_argument("--reps", type=int, default=None, help="kernel: calls per timed window (default 50)")
     ap.add_argument("--depth", action="store_true", help="kernel: also time ctg_project_rotate_depth on the same chunk")
     ap.add_argument("--cue", type=int, default=128, help="kernel: the depth cue of the --depth leg")
+    ap.add_argument("--render", action="store_true", help="kernel: also time ctg_project_render on the same chunk")
     o = ap.parse_args()
     print("build digest", _digest(), flush=True)
     if o.leg == "kernel":
-        kernel(sampling=o.sampling, oversample=o.oversample, depth=o.depth, cue=o.cue, **({} if o.reps is None else {"reps": o.reps}))
+        kernel(sampling=o.sampling, oversample=o.oversample, depth=o.depth, cue=o.cue, render=o.render, **({} if o.reps is None else {"reps": o.reps}))
     else:
         series(sampling=o.sampling, oversample=o.oversample)

@@ -91,6 +91,7 @@ SIGNATURES = {
     "ctg_project_accumulate_depth": "piiiiiipppp",
     "ctg_project_finish_depth": "piliiiiffippppp",
     "ctg_project_render": "piiiiipiiipiiiiiiffipppp",
+    "ctg_reformat_lines": "piiipiiiiiiffippp",
     "ctg_window_pairs": "ppppilipp",
     "ctg_maxpool3s2_fwd": "pipiiiiip",
     "ctg_lpips_layer": "pipiliippp",

@@ -51,6 +51,8 @@ struct CtgKnobs {
     // ---- first-layer convs (conv_small.hip), elementwise kernels (norm_act.hip)
     const int small_wgs = ctg_env::num("CTG_SMALL_WGS", 768);         // persistent workgroups over the whole batch
     const bool no_smallb = ctg_env::set("CTG_NO_SMALLB");             // pix_grid: 16 pixels per lane at every batch size
+    // ---- reformats (reformat.hip)
+    const int reformat_t1 = ctg_env::num("CTG_REFORMAT_T1", 0);       // T = 1 layout: 1 an 8 x 8 patch per wave, 2 64 columns of one line; else per sampling
 };
 
 static inline const CtgKnobs& ctg_knobs() {

@@ -41,6 +41,13 @@ runs obliquely stays connected from one slab to the next.  A coronal or sagittal
 chunk finishes its own rows of every slab plane in one launch per axis (`ops.project_slabs_inplane`); the axial slabs are int32
 accumulators (`ops.project_accumulate_sliding`) finished by `ops.project_finish`.  S = 1 makes about one plane per voxel of the
 axis: `SeriesSlabs.nbytes` says what that costs before anything runs.
+
+Reformats (`VolumeReformatter`, `reformat_volume`, `SeriesTranslator(reformat=...)`): every display whose rows cross slices --
+double-oblique planes and thin oblique slabs (`oblique_lines`), rotation about any axis (`orbit_lines`: the tumble), the
+straightened curved reformat along a vessel's centreline (`curved_lines`), any parallel view (`view_lines`).  The source volume
+stays on the device and one kernel samples it along lines given by a table of nine 16.16 integers per output line
+(`ops.reformat_lines`): nearest or trilinear sampling in exact integers, max / min / mean along rays of T steps, anisotropic
+voxels inside the table (`aspect`), one launch per table after the last chunk.
 """
 from __future__ import annotations
 
@@ -632,6 +639,311 @@ def render_volume(volume, angles, batch=64, device=None, **options):
     return {k: t.cpu().numpy() if is_np else t.cpu() for k, t in out.items()}
 
 
+# ------------------------------------------------------------------------------------------------ lines in any direction
+# Coordinates are (x, y, z) = (column, row, slice).  In "pixel units" the in-plane pitch is 1 and the slice pitch is `aspect`
+# (slice spacing / pixel spacing): a point q is voxel (qx, qy, qz / aspect) and the volume's centre is ((w-1)/2, (h-1)/2,
+# (n-1) aspect / 2).  The anisotropy is in the table, so the output is isotropic and no row is repeated on the host.
+REFORMAT_SAMPLINGS = tuple(ops.REFORMAT_SAMPLINGS)
+AXIS_VECTORS = {"x": (1.0, 0.0, 0.0), "y": (0.0, 1.0, 0.0), "z": (0.0, 0.0, 1.0)}
+
+
+class LineSet(tuple):
+    """What the geometry functions return: the pair (table, T) -- an int64 line table [..., rows, 9] for `ops.reformat_lines`
+    and the steps per ray -- that also remembers `.cols`, the samples per line the table was made for."""
+
+    def __new__(cls, table, steps, cols):
+        self = super().__new__(cls, (table, int(steps)))
+        self.cols = int(cols)
+        return self
+
+
+def _r16(v):
+    return np.floor(np.asarray(v, dtype=np.float64) * 65536.0 + 0.5).astype(np.int64)
+
+
+def _vec3(who, name, v):
+    v = AXIS_VECTORS.get(v, v) if isinstance(v, str) else v
+    try:
+        a = np.array([float(c) for c in v], dtype=np.float64)
+    except (TypeError, ValueError):
+        a = np.zeros(0)
+    if a.shape != (3,) or not np.isfinite(a).all():
+        raise ValueError("%s: %s: three finite numbers (x, y, z)%s expected, got %r"
+                         % (who, name, " or one of 'x', 'y', 'z'" if name == "axis" else "", v))
+    return a
+
+
+def _unit(who, name, v):
+    a = _vec3(who, name, v)
+    length = math.sqrt(float(a @ a))
+    if length < 1e-12:
+        raise ValueError("%s: %s has no direction: %r" % (who, name, v))
+    return a / length
+
+
+def _line_geometry(who, n, h, w, rows, cols, depth, oversample, aspect):
+    n, h, w, rows, cols, depth = int(n), int(h), int(w), int(rows), int(cols), int(depth)
+    if isinstance(oversample, bool) or not isinstance(oversample, (int, np.integer)) or oversample < 1:
+        raise ValueError("%s: oversample: an integer >= 1 expected, got %r" % (who, oversample))
+    s, aspect = int(oversample), float(aspect)
+    if min(n, h, w) < 1 or max(n, h, w) > ops.REFORMAT_MAX_DIM:
+        raise ValueError("%s: n, h, w in 1 .. %d expected, got %d %d %d" % (who, ops.REFORMAT_MAX_DIM, n, h, w))
+    if rows < 1 or not 1 <= cols <= ops.REFORMAT_MAX_DIM or depth < 1 or depth * s > ops.REFORMAT_MAX_DIM:
+        raise ValueError("%s: rows >= 1, cols in 1 .. %d and depth * oversample in 1 .. %d steps expected, got rows = %d, cols = %d, "
+                         "depth = %d, oversample = %d" % (who, ops.REFORMAT_MAX_DIM, ops.REFORMAT_MAX_DIM, rows, cols, depth, s))
+    if not (aspect > 0 and math.isfinite(aspect)):
+        raise ValueError("%s: aspect: a positive ratio expected, got %r" % (who, aspect))
+    return n, h, w, rows, cols, depth, s, aspect
+
+
+def volume_centre(n, h, w, aspect=1.0):
+    """The centre of an n x h x w volume in pixel units, (x, y, z)."""
+    return np.array([(int(w) - 1) / 2.0, (int(h) - 1) / 2.0, (int(n) - 1) * float(aspect) / 2.0])
+
+
+def _table(start, right, forward, s, aspect):
+    """int64 [R, 9]: lines that start (sample 0, step 0) at start [R, 3], move by right [R, 3] per sample and by forward [R, 3] / s
+    per step, all in pixel units; every coefficient is rounded on its own, the start with the + 0.5 of the nearest rule."""
+    scale = np.array([1.0, 1.0, aspect])
+    out = np.empty((start.shape[0], 9), dtype=np.int64)
+    out[:, 0::3] = _r16(start / scale + 0.5)
+    out[:, 1::3] = _r16(right / scale)
+    out[:, 2::3] = _r16(forward / s / scale)
+    return out
+
+
+def view_lines(n, h, w, right, down, forward, rows, cols, depth=1, offset=0.0, oversample=1, aspect=1.0, centre=None):
+    """A parallel view of an n x h x w volume as a line table: -> `LineSet` (table int64 [rows, 9], T = depth * oversample).
+    (right, down, forward): an orthonormal basis in pixel units (anything else is refused); sample (r, i, k) lies at
+        q = centre + (i - cu) right + (r - cr) down + (offset + k/s - ct) forward,
+        cu = (cols-1)/2, cr = (rows-1)/2, ct = (depth s - 1)/(2 s), s = oversample
+    (`rotation_coefficients` has the same cu and ct), centre: (x, y, z) in pixel units, default `volume_centre`.  A ray is `depth`
+    voxels long in depth * s steps and centred `offset` in front of the plane through the centre.  float64, every coefficient
+    rounded by floor(v * 65536 + 0.5)."""
+    who = "view_lines"
+    n, h, w, rows, cols, depth, s, aspect = _line_geometry(who, n, h, w, rows, cols, depth, oversample, aspect)
+    basis = np.stack([_vec3(who, "right", right), _vec3(who, "down", down), _vec3(who, "forward", forward)])
+    if np.abs(basis @ basis.T - np.eye(3)).max() > 1e-6:
+        raise ValueError("%s: (right, down, forward) is not an orthonormal basis: %r %r %r" % (who, right, down, forward))
+    c = volume_centre(n, h, w, aspect) if centre is None else _vec3(who, "centre", centre)
+    cu, cr, ct = (cols - 1) / 2.0, (rows - 1) / 2.0, (depth * s - 1) / (2.0 * s)
+    r = np.arange(rows, dtype=np.float64)[:, None]
+    start = c[None, :] + (-cu) * basis[0][None, :] + (r - cr) * basis[1][None, :] + (float(offset) - ct) * basis[2][None, :]
+    ones = np.ones((rows, 1))
+    return LineSet(_table(start, ones * basis[0][None, :], ones * basis[2][None, :], s, aspect), depth * s, cols)
+
+
+def _rotate_about(v, axis, degrees):
+    """v turned by `degrees` about the unit vector `axis` (Rodrigues; exact where the components are 0 and 1)."""
+    rad = math.radians(float(degrees))
+    cos, sin = math.cos(rad), math.sin(rad)
+    return v * cos + np.cross(axis, v) * sin + axis * (float(axis @ v) * (1.0 - cos))
+
+
+def _cover(n, h, w, aspect):
+    """ceil of the volume's diagonal in pixel units: a view of that many rows, columns and voxels of depth sees all of it."""
+    return int(math.ceil(math.sqrt(float(w) ** 2 + float(h) ** 2 + (float(n) * aspect) ** 2)))
+
+
+def orbit_lines(n, h, w, angles, axis="z", rows=None, cols=None, depth=None, offset=0.0, oversample=1, aspect=1.0, centre=None):
+    """The views of an orbit: -> `LineSet` (table int64 [A, rows, 9], T).  The coronal view -- right = +x, down = +z,
+    forward = +y -- turned by each of `angles` (degrees) about `axis` through the centre: "z" is the spin of `SeriesRotator`,
+    "x" the tumble, "y", or any 3-vector (x, y, z).  Defaults that let every angle see the whole volume: about z, rows =
+    ceil(n aspect) and cols = depth = `default_detector`; about any other axis all three are the ceil of the volume's diagonal.
+    With axis "z", aspect 1, rows = n and cols = depth = `default_detector`, the x and y columns of every row are the six integers
+    of `rotation_coefficients` and z0 = (r << 16) + 32768, zu = zk = 0."""
+    who = "orbit_lines"
+    a = _unit(who, "axis", axis)
+    angles = [float(v) for v in angles]
+    if not angles:
+        raise ValueError("%s: at least one angle expected" % who)
+    spin = isinstance(axis, str) and axis == "z"
+    d = default_detector(h, w) if spin else _cover(n, h, w, float(aspect))
+    rows = (max(1, int(math.ceil(int(n) * float(aspect) - 1e-9))) if spin else d) if rows is None else rows
+    cols, depth = d if cols is None else cols, d if depth is None else depth
+    right, down, forward = (np.array(AXIS_VECTORS[k]) for k in "xzy")
+    sets = [view_lines(n, h, w, _rotate_about(right, a, v), _rotate_about(down, a, v), _rotate_about(forward, a, v), rows, cols,
+                       depth, offset, oversample, aspect, centre) for v in angles]
+    return LineSet(np.stack([t for t, _ in sets]), sets[0][1], sets[0].cols)
+
+
+def oblique_lines(n, h, w, normal, up=None, count=1, pitch=1.0, thick=1, rows=None, cols=None, oversample=1, aspect=1.0, centre=None):
+    """Parallel oblique planes: -> `LineSet` (table int64 [count, rows, 9], T = thick * oversample).  `count` planes with the
+    normal `normal` (x, y, z; pixel units), `pitch` apart along it and centred on the centre, each `thick` voxels deep along the
+    normal (mode picks the slab's projection).  In the plane, `down` is the +z axis projected into it (the +y axis where the
+    normal is within 1e-6 of z), or the opposite of `up` projected into it when `up` is given; `right` completes the basis and
+    points toward +x (toward +y where it has no x component).  Defaults: rows and cols cover the volume's extent along down and
+    right.  So, with aspect 1 and pitch 1: normal +z, count n returns the slices as stored; normal +y, count h returns
+    vol[:, y, :]; normal +x, count w returns vol[:, :, x]."""
+    who = "oblique_lines"
+    forward = _unit(who, "normal", normal)
+    count = int(count)
+    if count < 1 or not (float(pitch) > 0 and math.isfinite(float(pitch))):
+        raise ValueError("%s: count >= 1 and pitch > 0 expected, got %r %r" % (who, count, pitch))
+    if up is not None:
+        ref = -_unit(who, "up", up)
+    else:
+        ref = np.array(AXIS_VECTORS["y" if abs(forward[2]) > 1.0 - 1e-6 else "z"])
+    down = ref - float(ref @ forward) * forward
+    if math.sqrt(float(down @ down)) < 1e-6:
+        raise ValueError("%s: up %r runs along the normal %r" % (who, up, normal))
+    down = down / math.sqrt(float(down @ down))
+    right = np.cross(down, forward)
+    lead = right[0] if abs(right[0]) > 1e-9 else (right[1] if abs(right[1]) > 1e-9 else right[2])
+    if lead < 0:
+        right = -right
+    size = np.array([float(w), float(h), float(n) * float(aspect)])
+    rows = max(1, int(math.ceil(float(np.abs(down) @ size) - 1e-9))) if rows is None else rows
+    cols = max(1, int(math.ceil(float(np.abs(right) @ size) - 1e-9))) if cols is None else cols
+    sets = [view_lines(n, h, w, right, down, forward, rows, cols, thick, (p - (count - 1) / 2.0) * float(pitch), oversample, aspect,
+                       centre) for p in range(count)]
+    return LineSet(np.stack([t for t, _ in sets]), sets[0][1], sets[0].cols)
+
+
+def curved_lines(n, h, w, centreline, angles=(0.0,), cols=65, depth=1, pitch=1.0, oversample=1, aspect=1.0):
+    """The straightened curved reformat along a centreline: -> `LineSet` (table int64 [A, R, 9], T = depth * oversample).
+    centreline: float [M >= 2, 3] in (z, y, x) voxel order.  It is resampled linearly at arc-length `pitch` (pixel units): R =
+    floor(length / pitch) + 1 rows p_r; the tangents are central differences of the resampled points (one-sided at the ends);
+    the frame (e1, e2) is carried along by parallel transport -- e1 is re-projected orthogonal to each new tangent and normalised,
+    e2 = tangent x e1 -- and starts from the x axis, or from the y axis where the first tangent is within 1e-6 of x.  Row r at
+    angle phi (degrees) samples p_r + (i - cu) (cos phi e1 + sin phi e2), cu = (cols-1)/2, and its slab of `depth` voxels runs
+    along -sin phi e1 + cos phi e2, centred on the line.  For a straight centreline along z through (y0, x0) with aspect 1, angle
+    0 reads vol[r, y0, x0 + i - cu]."""
+    who = "curved_lines"
+    pts = np.asarray(centreline, dtype=np.float64)
+    if pts.ndim != 2 or pts.shape[1] != 3 or pts.shape[0] < 2 or not np.isfinite(pts).all():
+        raise ValueError("%s: a centreline of M >= 2 finite points (z, y, x) expected, got an array of shape %s" % (who, pts.shape))
+    angles = [float(v) for v in angles]
+    if not angles or not (float(pitch) > 0 and math.isfinite(float(pitch))):
+        raise ValueError("%s: at least one angle and pitch > 0 expected" % who)
+    n, h, w, _, cols, depth, s, aspect = _line_geometry(who, n, h, w, 1, cols, depth, oversample, aspect)
+    p = pts[:, ::-1] * np.array([1.0, 1.0, aspect])      # (x, y, z) in pixel units
+    seg = np.sqrt(((p[1:] - p[:-1]) ** 2).sum(axis=1))
+    arc = np.concatenate([[0.0], np.cumsum(seg)])
+    if arc[-1] <= 0 or (seg <= 0).any():
+        raise ValueError("%s: the centreline repeats a point" % who)
+    at = np.arange(int(math.floor(arc[-1] / float(pitch) + 1e-9)) + 1, dtype=np.float64) * float(pitch)
+    q = np.stack([np.interp(at, arc, p[:, j]) for j in range(3)], axis=1)      # [R, 3]
+    if len(q) > 1:
+        tan = np.empty_like(q)
+        tan[1:-1], tan[0], tan[-1] = q[2:] - q[:-2], q[1] - q[0], q[-1] - q[-2]
+    else:
+        tan = (p[-1] - p[0])[None, :]
+    tan = tan / np.sqrt((tan ** 2).sum(axis=1))[:, None]
+    e1 = np.array(AXIS_VECTORS["y" if abs(tan[0][0]) > 1.0 - 1e-6 else "x"])
+    f1, f2 = np.empty_like(q), np.empty_like(q)
+    for r in range(len(q)):
+        e1 = e1 - float(e1 @ tan[r]) * tan[r]
+        e1 = e1 / math.sqrt(float(e1 @ e1))      # (a turn of 90 degrees between two rows would leave nothing: pitch too coarse)
+        f1[r], f2[r] = e1, np.cross(tan[r], e1)
+    cu, ct = (cols - 1) / 2.0, (depth * s - 1) / (2.0 * s)
+    tables = []
+    for phi in angles:
+        rad = math.radians(phi)
+        cos, sin = math.cos(rad), math.sin(rad)
+        right, forward = cos * f1 + sin * f2, (-sin) * f1 + cos * f2
+        tables.append(_table(q + (-cu) * right + (-ct) * forward, right, forward, s, aspect))
+    return LineSet(np.stack(tables), depth * s, cols)
+
+
+class VolumeReformatter:
+    """Reformats of an int16 volume [n, h, w] that arrives in chunks and stays on the device: oblique planes, tumbling views,
+    curved reformats -- every display whose rows cross slices (`ops.reformat_lines`, csrc/reformat.hip).  tables: {name: a
+    `LineSet`, a pair (table [..., 9], T) with `cols` given here, or a callable (n, h, w) -> either}; mode "max" / "min" / "mean"
+    along the rays of T steps, sampling "trilinear" or "nearest", `fill` where a ray misses the volume (default: air, 0 or -1024
+    with `hu`), level=False skips the 8-bit planes of the window (wc, ww).  `update(pix_chunk, n0)` copies a chunk in, in any
+    order; `result()` raises unless every slice has arrived exactly once since the last `reset()`, then makes one launch per
+    table -> {name: {"values": int16 [..., U], "level": uint8 or None}} on the device.  `.nbytes`: the device memory held (the
+    volume and the tables) plus that of one result, known before the first chunk.  Exact integer arithmetic on the current
+    stream: equal to numpy bit for bit."""
+
+    def __init__(self, n, h, w, tables, mode="max", sampling="trilinear", fill=None, wc=50.0, ww=400.0, hu=False, level=True,
+                 device=None, cols=None):
+        who = "VolumeReformatter"
+        if mode not in PROJECTIONS:
+            raise ValueError("%s: mode %r is not one of %s" % (who, mode, PROJECTIONS))
+        if sampling not in REFORMAT_SAMPLINGS:
+            raise ValueError("%s: sampling %r is not one of %s" % (who, sampling, REFORMAT_SAMPLINGS))
+        self.n, self.h, self.w = int(n), int(h), int(w)
+        if min(self.n, self.h, self.w) < 1 or max(self.n, self.h, self.w) > ops.REFORMAT_MAX_DIM:
+            raise ValueError("%s: n, h, w in 1 .. %d expected, got %d %d %d" % (who, ops.REFORMAT_MAX_DIM, self.n, self.h, self.w))
+        if not isinstance(tables, dict) or not tables:
+            raise ValueError("%s: tables: a dict {name: (table, T)} with at least one entry expected" % who)
+        self.mode, self.sampling = mode, sampling
+        self.hu, self.window, self.want_level = bool(hu), (float(wc), float(ww)), bool(level)
+        self.fill = (-1024 if self.hu else 0) if fill is None else int(fill)
+        self.lines = {}      # name -> (host table, U, T), checked
+        for name, entry in tables.items():
+            entry = entry(self.n, self.h, self.w) if callable(entry) else entry
+            u = getattr(entry, "cols", cols)
+            if not isinstance(entry, tuple) or len(entry) != 2 or u is None:
+                raise ValueError("%s: table %r: a LineSet, or a pair (table, T) together with cols, expected" % (who, name))
+            self.lines[name] = (ops.line_table_host(entry[0], u, entry[1]), int(u), int(entry[1]))
+        self._seen = np.zeros(self.n, dtype=np.int64)
+        per = 2 + (1 if self.want_level else 0)
+        self.nbytes = 2 * self.n * self.h * self.w + sum(t.nbytes + per * (t.size // 9) * u for t, u, _ in self.lines.values())
+        self.device = None if device is None else torch.device(device)      # None: the current device at the first chunk
+        if self.device is not None and self.device.type != "cuda":
+            raise RuntimeError("%s: a GPU device is required (no CPU fallback)" % who)
+        self.tables = self.volume = None      # on the device from the first chunk on
+
+    def reset(self):
+        """Forget which slices have arrived (the volume's memory is kept and overwritten)."""
+        self._seen[:] = 0
+
+    def update(self, pix_chunk, n0):
+        k, n0 = pix_chunk.shape[0], int(n0)
+        if tuple(pix_chunk.shape[1:]) != (self.h, self.w) or n0 < 0 or n0 + k > self.n or pix_chunk.dtype != torch.int16:
+            raise RuntimeError("VolumeReformatter: int16 chunk %s at slice %d does not lie in the volume (%d, %d, %d)"
+                               % (tuple(pix_chunk.shape), n0, self.n, self.h, self.w))
+        if k < 1:
+            return
+        if self.volume is None:
+            if self.device is None:
+                self.device = torch.device("cuda", torch.cuda.current_device())
+            self.tables = {name: ops.LineTable(t, u, steps, self.device) for name, (t, u, steps) in self.lines.items()}
+            self.volume = torch.empty((self.n, self.h, self.w), dtype=torch.int16, device=self.device)
+        self.volume[n0:n0 + k].copy_(pix_chunk, non_blocking=True)
+        self._seen[n0:n0 + k] += 1
+
+    def result(self):
+        if (self._seen != 1).any():
+            missing, twice = int((self._seen == 0).sum()), int((self._seen > 1).sum())
+            raise RuntimeError("VolumeReformatter: every slice must have arrived exactly once: %d of %d missing, %d more than once"
+                               % (missing, self.n, twice))
+        out = {}
+        for name, table in self.tables.items():
+            values, level = ops.reformat_lines(self.volume, table, table.u, table.t, self.mode, fill=self.fill, wc=self.window[0],
+                                               ww=self.window[1], hu=self.hu, sampling=self.sampling, want_level=self.want_level)
+            out[name] = {"values": values, "level": level}
+        return out
+
+
+def reformat_volume(volume, tables, mode="max", sampling="trilinear", fill=None, wc=50.0, ww=400.0, hu=False, level=True, batch=64,
+                    device=None, cols=None):
+    """The reformats of a volume that already exists, the twin of `rotate_volume`: int16 [N, H, W], a host array / CPU tensor
+    (chunks of `batch` slices cross PCIe one after another) or a device tensor; tables and the options as `VolumeReformatter`.
+    Returns what `VolumeReformatter.result` returns, of the input's kind."""
+    is_np = isinstance(volume, np.ndarray)
+    vol = torch.from_numpy(np.ascontiguousarray(volume)) if is_np else volume
+    if not torch.is_tensor(vol) or vol.dtype != torch.int16 or vol.dim() != 3:
+        raise RuntimeError("reformat_volume: an int16 volume [N, H, W] expected")
+    if int(batch) < 1:
+        raise ValueError("reformat_volume: batch >= 1 expected")
+    on_host = not vol.is_cuda
+    n, h, w = vol.shape
+    dev = device if on_host else vol.device
+    ref = VolumeReformatter(n, h, w, tables, mode=mode, sampling=sampling, fill=fill, wc=wc, ww=ww, hu=hu, level=level,
+                            device=torch.device("cuda", torch.cuda.current_device()) if dev is None else dev, cols=cols)
+    with torch.cuda.device(ref.device):
+        for s, e, _ in plan_chunks(n, batch):
+            ref.update(vol[s:e], s)
+        out = ref.result()
+    if not on_host:
+        return out
+    return {name: {k: None if t is None else (t.cpu().numpy() if is_np else t.cpu()) for k, t in d.items()} for name, d in out.items()}
+
+
 def subtract_volume(cta, ct_hu, cta_is_hu=False, median=True, floor=0, ct_range=(None, None), wc=150.0, ww=300.0, level=True,
                     batch=64, device=None):
     """The subtraction of two volumes that already exist (a real CTA and its registered CT for a side-by-side view, or a
@@ -673,6 +985,7 @@ def subtract_volume(cta, ct_hu, cta_is_hu=False, median=True, floor=0, ct_range=
 
 
 PROJECT_SOURCES = ("cta", "sub")
+REFORMAT_OPTIONS = ("mode", "sampling", "fill", "cols")
 RENDER_OPTIONS = ("transfer", "detector", "wc", "ww", "hu", "sampling", "oversample", "background", "stop", "surface", "depth")
 
 
@@ -706,6 +1019,12 @@ class SeriesTranslator:
     surface, depth) adds "render": {"rgb": uint8 [A, N, D, 3], "opacity": uint8, "depth": int16 (unless depth=False), "angles":
     float64 [A]}, the volume-rendered views of the same source (`project_source`), copied back once after the last chunk.  With
     render=None nothing of it is allocated or launched.
+    reformat = {name: a `LineSet`, a pair (table, T), or a callable (n, h, w) -> either} (reformat_options: a dict with any of
+    mode, sampling, fill, cols, as `VolumeReformatter`) adds "reformat": {name: {"values": int16 [..., U], "level": uint8}}:
+    oblique planes, tumbling views and curved reformats of the same source (`project_source`, so "sub" gives bone-free reformats
+    in sub_window).  Their rows cross slices, so the source volume is kept on the device (`VolumeReformatter.nbytes`), every table
+    is one launch after the last chunk, and the planes are copied back once.  With reformat=None nothing of it is allocated or
+    launched.
 
     size: the side(s) the generator runs at (None: the volume's own); a volume of another size is resized (nearest) on the way
     in and comes back at its own size.  wc / ww: the window of the 8-bit level; hu: pixels minus 1024 (SimpleITK) instead of
@@ -715,9 +1034,17 @@ class SeriesTranslator:
     def __init__(self, generator, batch=16, size=None, wc=50.0, ww=400.0, hu=False, level=True, device=None, project=None,
                  slab=None, rotate=None, rotate_mode=None, subtract=False, sub_median=True, sub_floor=0, sub_ct_range=(None, None),
                  sub_window=(150.0, 300.0), project_source="cta", slabs=None, rotate_sampling="nearest", rotate_oversample=1,
-                 depth=False, depth_cue=0, render=None, render_options=None):
+                 depth=False, depth_cue=0, render=None, render_options=None, reformat=None, reformat_options=None):
         if int(batch) < 1:
             raise ValueError("SeriesTranslator: batch >= 1 expected")
+        self.reformat = None if reformat is None else dict(reformat)
+        self.reformat_options = dict(reformat_options or {})
+        if self.reformat is None and self.reformat_options:
+            raise ValueError("SeriesTranslator: reformat_options need reformat")
+        if self.reformat is not None and (not self.reformat or set(self.reformat_options) - set(REFORMAT_OPTIONS)):
+            raise ValueError("SeriesTranslator: reformat needs at least one table, and reformat_options %r a dict with any of %s"
+                             % (reformat_options, REFORMAT_OPTIONS))
+        self._reformatter = self._ref_host = None
         self.render = None if render is None else _angle_list(render)
         self.render_options = dict(render_options or {})
         if self.render is None and self.render_options:
@@ -813,6 +1140,7 @@ class SeriesTranslator:
             rot = self._rotator_for(n, h, w)
             slb = self._slabber_for(n, h, w)
             ren = self._renderer_for(n, h, w)
+            ref = self._reformatter_for(n, h, w)
             in_free = [None] * SLOTS       # event: the slot's H2D copy has drained, the host may rewrite it
             pending = [None] * SLOTS       # (event, start, stop): the slot's D2H copy, not yet moved into the result
 
@@ -868,6 +1196,8 @@ class SeriesTranslator:
                         slb.update(src, s)
                     if ren is not None:
                         ren.update(src, s)
+                    if ref is not None:
+                        ref.update(src, s)
                 computed = torch.cuda.Event()
                 computed.record(cur)
                 drain(slot)                          # the chunk that used this slot last: its D2H started two chunks ago
@@ -907,6 +1237,11 @@ class SeriesTranslator:
                 ren_staged = self._stage_render(ren.result())
                 ren_done = torch.cuda.Event()
                 ren_done.record(cur)
+            ref_done = None
+            if ref is not None:       # the whole volume is on the device now: one launch per table, staged the same way
+                ref_staged = self._stage_reformat(ref.result())
+                ref_done = torch.cuda.Event()
+                ref_done.record(cur)
             for slot in sorted(range(SLOTS), key=lambda q: pending[q][1] if pending[q] else -1):
                 drain(slot)
             projections = None
@@ -935,6 +1270,12 @@ class SeriesTranslator:
                 stats["wait"] += clock() - t0
                 rendered = {k: t.clone().numpy() if is_np else t.clone() for k, t in ren_staged.items()}
                 rendered["angles"] = np.array(ren.angles, dtype=np.float64) if is_np else torch.tensor(ren.angles, dtype=torch.float64)
+            reformats = None
+            if ref_done is not None:
+                t0 = clock()
+                ref_done.synchronize()
+                stats["wait"] += clock() - t0
+                reformats = {a: {k: t.clone().numpy() if is_np else t.clone() for k, t in d.items()} for a, d in ref_staged.items()}
         # the forwards above ran fused conv + InstanceNorm launches: none may have given up (raises)
         ops.nie_check("series inference")
         stats["total"] = clock() - t_call
@@ -947,6 +1288,8 @@ class SeriesTranslator:
             out["slabs"] = slab_out
         if rendered is not None:
             out["render"] = rendered
+        if reformats is not None:
+            out["reformat"] = reformats
         return out
 
     def _stage_projections(self, dev):
@@ -988,6 +1331,30 @@ class SeriesTranslator:
             for k, t in d.items():
                 self._slab_host[a][k].copy_(t, non_blocking=True)
         return self._slab_host
+
+    def _stage_reformat(self, dev):
+        """Start the copies of the finished reformats into page-locked buffers (kept between calls on volumes of one shape)."""
+        shapes = {a: tuple(d["values"].shape) for a, d in dev.items()}
+        if self._ref_host is None or {a: tuple(d["values"].shape) for a, d in self._ref_host.items()} != shapes:
+            self._ref_host = {a: {k: torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for k, t in d.items()}
+                              for a, d in dev.items()}
+        for a, d in dev.items():
+            for k, t in d.items():
+                self._ref_host[a][k].copy_(t, non_blocking=True)
+        return self._ref_host
+
+    def _reformatter_for(self, n, h, w):
+        """The `VolumeReformatter` of an (n, h, w) volume, kept between calls on volumes of one shape; None without `reformat`."""
+        if self.reformat is None:
+            return None
+        r = self._reformatter
+        if r is None or (r.n, r.h, r.w) != (n, h, w):
+            wc, ww = self._view_window()
+            r = self._reformatter = VolumeReformatter(n, h, w, self.reformat, wc=wc, ww=ww, hu=self._view_hu(), device=self.device,
+                                                      **self.reformat_options)
+        else:
+            r.reset()
+        return r
 
     def _slabber_for(self, n, h, w):
         """The `SeriesSlabs` of an (n, h, w) volume, kept between calls on volumes of one shape; None without `slabs`."""

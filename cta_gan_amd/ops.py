@@ -1994,6 +1994,95 @@ def project_render(pix, n0, coef, t, lut, rgb=None, opacity=None, depth=None, ba
                                       _p(depth), _stream()), "ctg_project_render")
 
 
+# ---------------------------------------------------------------------------- lines in any direction (csrc/reformat.hip)
+REFORMAT_MAX_DIM = 4096      # N, H, W, U, T
+REFORMAT_SAMPLINGS = {"nearest": 0, "trilinear": 1}      # `sampling` of ctg_reformat_lines
+
+
+def line_table_host(lines, u, t):
+    """The host half of `LineTable`: lines [..., 9] integers -> the checked int32 copy of the same shape.  For every line and
+    axis |c0| + |cu| (u-1) + |ck| (t-1) < 2^31 is required: exactly the condition under which no fixed-point sum of the kernel
+    wraps (a step may exceed one voxel).  Needs no GPU."""
+    import numpy as np
+    host = np.asarray(lines.cpu() if torch.is_tensor(lines) else lines)
+    if host.ndim < 1 or host.shape[-1] != 9 or host.dtype.kind not in "iu" or host.size < 9:
+        raise RuntimeError("reformat_lines: a line table of [..., 9] integers, at least one line, expected, got %s %s"
+                           % (host.dtype, tuple(host.shape)))
+    u, t = int(u), int(t)
+    if not (1 <= min(u, t) and max(u, t) <= REFORMAT_MAX_DIM):
+        raise RuntimeError("reformat_lines: U, T in 1 .. %d expected, got %d %d" % (REFORMAT_MAX_DIM, u, t))
+    if (np.abs(host.astype(np.float64)) >= 2.0 ** 31).any():      # (uint64 entries: before the int64 view of them)
+        raise RuntimeError("reformat_lines: line table out of range (|c0| + |cu| (U-1) + |ck| (T-1) < 2^31 for every line and axis)")
+    mag = np.abs(host.astype(np.int64)).reshape(-1, 3, 3)
+    if (mag[:, :, 0] + mag[:, :, 1] * (u - 1) + mag[:, :, 2] * (t - 1) >= 1 << 31).any():
+        raise RuntimeError("reformat_lines: line table out of range (|c0| + |cu| (U-1) + |ck| (T-1) < 2^31 for every line and axis)")
+    return np.ascontiguousarray(host.astype(np.int32))
+
+
+class LineTable:
+    """The line table of `reformat_lines`: [..., 9] int32, one row (x0, xu, xk, y0, yu, yk, z0, zu, zk) per output line
+    (`infer.view_lines`, `orbit_lines`, `oblique_lines`, `curved_lines`), range-checked on the host for lines of `u` samples and
+    rays of `t` steps (`line_table_host`) and uploaded once.  `.host`: the numpy table, `.dev`: its device copy [L, 9], `.shape`:
+    the leading shape, `.count`: L, `.u`, `.t`."""
+
+    def __init__(self, lines, u, t, device=None):
+        self.host = line_table_host(lines, u, t)
+        self.u, self.t = int(u), int(t)
+        self.shape = tuple(self.host.shape[:-1])
+        self.count = int(self.host.size // 9)
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("reformat_lines: a GPU device is required (no CPU fallback)")
+        self.dev = torch.from_numpy(self.host.reshape(-1, 9)).to(self.device)
+
+    def __len__(self):
+        return self.count
+
+
+def reformat_lines(vol, lines, u, t, mode, fill=None, wc=50.0, ww=400.0, hu=False, sampling="nearest", want_values=True,
+                   want_level=True):
+    """The whole int16 volume sampled along lines in any direction, one launch of ctg_reformat_lines: vol (N, H, W) int16 on the
+    GPU (a contiguous view is taken as it is: 2-byte alignment is enough); lines: a `LineTable` made for this u and t, or a host
+    table [..., 9] that is checked and uploaded by this call; u: samples per line, t: steps per ray (1: a plain reformat); mode
+    0 / "max", 1 / "min", 2 / "mean" over the counted samples of every ray; sampling "nearest" (the voxel a sample falls in) or
+    "trilinear" (the eight voxels around it, 8-bit fractions, the edge replicated).  Returns (values int16, level uint8), each
+    [..., u] on the GPU, None for the one not wanted: `fill` (default: air, 0 or -1024 with hu) where no sample of a ray lies in
+    the volume, and the 8-bit window level of every value (csrc/reformat.hip has the rule).  Exact integer arithmetic: equal to
+    numpy bit for bit."""
+    lib = _lib.load()
+    who = "reformat_lines"
+    if not torch.is_tensor(vol) or not vol.is_cuda:
+        raise RuntimeError("%s: CPU tensors are not supported (no CPU fallback)" % who)
+    if vol.dtype != torch.int16 or vol.dim() != 3:
+        raise RuntimeError("%s: vol must be int16 (N, H, W), got %s %s" % (who, vol.dtype, tuple(vol.shape)))
+    code = _project_mode(mode, who)
+    if sampling not in REFORMAT_SAMPLINGS:
+        raise RuntimeError("%s: sampling %r is not one of %s" % (who, sampling, tuple(REFORMAT_SAMPLINGS)))
+    if not want_values and not want_level:
+        raise RuntimeError("%s: values, level or both expected" % who)
+    if torch.is_tensor(lines) and lines.is_cuda:
+        raise RuntimeError("%s: the line table is checked on the host: pass a host table or an ops.LineTable" % who)
+    u, t, hu = int(u), int(t), bool(hu)
+    table = lines if isinstance(lines, LineTable) else LineTable(lines, u, t, vol.device)
+    if (table.u, table.t) != (u, t):
+        raise RuntimeError("%s: the line table was checked for U = %d, T = %d, not for %d, %d" % (who, table.u, table.t, u, t))
+    if table.dev.device != vol.device:
+        raise RuntimeError("%s: vol and the line table must live on one device" % who)
+    x = vol.contiguous()
+    n, h, w = x.shape
+    if not (1 <= min(n, h, w) and max(n, h, w) <= REFORMAT_MAX_DIM):
+        raise RuntimeError("%s: N, H, W in 1 .. %d expected, got %d %d %d" % (who, REFORMAT_MAX_DIM, n, h, w))
+    fill = (-1024 if hu else 0) if fill is None else int(fill)
+    if not -32768 <= fill <= 32767:
+        raise RuntimeError("%s: fill %d is not an int16 value" % (who, fill))
+    with torch.cuda.device(vol.device):
+        values = torch.empty(table.shape + (u,), dtype=torch.int16, device=vol.device) if want_values else None
+        level = torch.empty(table.shape + (u,), dtype=torch.uint8, device=vol.device) if want_level else None
+        _lib.check(lib.ctg_reformat_lines(_p(x), n, h, w, _p(table.dev), table.count, u, t, code, REFORMAT_SAMPLINGS[sampling], fill,
+                                          float(wc), float(ww), int(hu), _p(values), _p(level), _stream()), "ctg_reformat_lines")
+    return values, level
+
+
 def project_accumulate_depth(pix, n0, thick, mode, axial=None, coronal=None, sagittal=None):
     """`project_accumulate` on keyed accumulators (value and depth of the maximum in one 32-bit word, include/ctagan_hip.h): the
     same arguments and shapes, int32 tensors that the caller fills with PROJECT_DEPTH_IDENTITY[mode] before the first chunk; mode

@@ -582,6 +582,33 @@ int ctg_project_render(const short* pix, int K, int H, int W, int n0, int N, con
                        const unsigned short* lut, int sampling, int stop, int surface, int bg_r, int bg_g, int bg_b, float wc,
                        float ww, int hu, unsigned char* rgb, unsigned char* opacity, short* depth, void* stream);
 
+/* ---- series inference, lines in any direction (added under ABI 15: purely additive, no existing signature or meaning moves, so
+ * the version stays 15): oblique planes, tumbling views and curved reformats -- every display whose rows cross slices, which the
+ * entries above cannot make.  cta_gan_amd/infer.py: view_lines, orbit_lines, oblique_lines, curved_lines, VolumeReformatter,
+ * reformat_volume, SeriesTranslator(reformat=...); ops.reformat_lines, ops.LineTable.  The reference has no counterpart.
+ * ctg_reformat_lines: vol = the whole int16 volume [N][H][W] on the device, contiguous, 2-byte aligned.  lines = int32 [L][9] on
+ *   the device, 4-byte aligned, one row (x0, xu, xk, y0, yu, yk, z0, zu, zk) per output line: sample (l, i, k), i in 0 .. U-1 and
+ *   k in 0 .. T-1, lies at the 16.16 fixed-point position X = x0 + xu i + xk k, Y = y0 + yu i + yk k, Z = z0 + zu i + zk k (the
+ *   + 0.5 of the nearest rule inside, as in the rotation's table) and is counted exactly when voxel (X >> 16, Y >> 16, Z >> 16),
+ *   arithmetic shifts, lies in the volume.  out[l][i] = the max (mode 0), min (1) or mean (2: the exact sum over the ray's own
+ *   count, C division) over the counted samples of ray (l, i); `fill` where none is counted.  T = 1 is a plain reformat, T > 1 a
+ *   slab or projection along the ray.  values int16 [L][U] and level uint8 [L][U], either may be NULL (not both); level = the
+ *   8-bit window level of v + (hu ? 1024 : 0) in (wc, ww), as ctg_project_rotate writes it, in the same pass.
+ *   sampling 0 = nearest: the voxel above.  sampling 1 = trilinear in exact integers about the centre-based position
+ *   Xc = X - 32768 (Y, Z likewise): x0 = Xc >> 16, fx = (Xc >> 8) & 255 per axis; v0 = the bilinear value of
+ *   ctg_project_rotate_bilinear from fx, fy on slice clamp(z0), v1 the same on slice clamp(z0 + 1) (the in-plane neighbours
+ *   clamped as there), v = (v0 (256 - fz) + v1 fz + 128) >> 8.  Two roundings, each defined; v is an int16 value for every input
+ *   and a constant volume stays constant.  Which samples count does not depend on the sampling.
+ *   Every address is bounds-checked or clamped whatever the table holds; the sums are formed in unsigned arithmetic and read as
+ *   int32, so the caller keeps |c0| + |cu| (U-1) + |ck| (T-1) < 2^31 for every line and axis (ops.LineTable checks it on the host):
+ *   beyond that the result is defined by the wrapped sums, still without an access outside the volume.
+ *   Exact integer arithmetic: the same bits as numpy (tests/reformat_np.py).  One launch, no accumulator, no atomics.
+ *   CTG_EINVAL, nothing launched: a null vol or lines; no output; N, H, W, U or T outside 1 .. 4096; L < 1; mode outside 0 .. 2;
+ *   sampling outside 0 .. 1; fill outside int16; vol or values not 2-byte aligned, lines not 4-byte aligned; a grid beyond
+ *   2^31 - 1 workgroups (L ceil(U / 32)). ---- */
+int ctg_reformat_lines(const short* vol, int N, int H, int W, const int* lines, int L, int U, int T, int mode, int sampling,
+                       int fill, float wc, float ww, int hu, short* values, unsigned char* level, void* stream);
+
 /* ---- LPIPS (AlexNet, lpips 0.1) of the test() loops (ABI 14): `loss_fn_alex = lpips.LPIPS(net='alex')` (trainer/HdTrainer.py:26-28)
  * and its calls `loss_fn_alex.forward(torch.tensor(c), torch.tensor(b))` on the windowed and on the raw masked pair of every slice
  * (HdTrainer.py:504-513, 531-536, 1029-1031, 1054-1056; the twins in CycTrainer.py, p2pTrainer.py, RegTrainer.py).  The five

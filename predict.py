@@ -13,6 +13,10 @@
                       [--depth [--depth-cue C]]
                       [--vr-dir DIR [--vr-angles 36] [--vr-span 360] [--vr-preset grey|vessels|bone] [--vr-wc 300 --vr-ww 1500]
                        [--vr-sampling nearest|bilinear] [--vr-oversample S] [--vr-background R,G,B] [--aspect R]]
+                      [--mpr-dir DIR --mpr-normal X,Y,Z [--mpr-count P] [--mpr-pitch D] [--mpr-thick T]]
+                      [--tumble-dir DIR [--tumble-angles 36] [--tumble-axis x|y|z]]
+                      [--cpr-dir DIR --cpr-centreline pts.npy [--cpr-angles A] [--cpr-width U] [--cpr-thick T]]
+                      [--reformat-sampling nearest|trilinear]
 
 --input: int16 [N, H, W] .npy in SimpleITK's convention (what the reference's loaders read from the DICOMs); --weights: the
 reference-format `state_dict` of Model.HdGan.Generator (what train() saves as netG_A2B*.pth).  --output receives the int16
@@ -54,6 +58,16 @@ transfer function that gives every class its colour and opacity (cta_gan_amd/inf
 shows through where a ray stays transparent.  vr_%03d.png, one RGB frame [round(N R), D] per angle, and render.npz with rgb
 (uint8 [A, N, D, 3]), opacity (uint8), depth (int16: the step at which a ray becomes half opaque, -1 if never), angles and lut
 (the uint16 [256, 4] transfer table that was used).
+--mpr-dir, --tumble-dir, --cpr-dir: reformats whose rows cross slices, made after the last chunk from the volume kept on the
+device (cta_gan_amd/infer.py: VolumeReformatter), of the same source (--mip-source) in the same window, with --mip-mode along
+their rays and --reformat-sampling trilinear (default) or nearest.  --aspect R is inside their geometry: the images are isotropic
+and no row is repeated.  --mpr-dir: --mpr-count parallel oblique planes with the normal --mpr-normal X,Y,Z (x = column, y = row,
+z = slice), --mpr-pitch pixels apart and centred on the volume, each a slab --mpr-thick voxels deep (1: a plain plane):
+mpr_%03d.png.  --tumble-dir: the rotating projection about another axis than --rot-dir's, --tumble-angles views around the full
+circle about --tumble-axis x (default: the tumble), y or z through the centre: tumble_%03d.png.  --cpr-dir: the straightened
+curved reformat along --cpr-centreline (a .npy of M >= 2 points (z, y, x) in voxels), --cpr-width samples across the vessel,
+--cpr-angles views around it, slabs --cpr-thick voxels deep: cpr_%03d.png.  Each directory also receives reformat.npz with values
+(int16), level (uint8) and, for the rotating kinds, angles (degrees).
 DICOM reading and writing are not part of this build.
 """
 import argparse
@@ -95,6 +109,21 @@ def build_parser():
     parser.add_argument("--vr-sampling", choices=["nearest", "bilinear"], default="nearest", help="how a ray samples the slice (with --vr-dir)")
     parser.add_argument("--vr-oversample", type=int, default=1, help="steps per voxel along a ray (with --vr-dir)")
     parser.add_argument("--vr-background", type=str, default="0,0,0", help="R,G,B in 0 .. 255 behind the rendered view (with --vr-dir)")
+    parser.add_argument("--mpr-dir", type=str, default=None, help="also write oblique planes (MPR) here")
+    parser.add_argument("--mpr-normal", type=str, default=None, help="X,Y,Z: the normal of the oblique planes (with --mpr-dir)")
+    parser.add_argument("--mpr-count", type=int, default=1, help="parallel oblique planes (with --mpr-dir)")
+    parser.add_argument("--mpr-pitch", type=float, default=1.0, help="pixels between two oblique planes (with --mpr-dir)")
+    parser.add_argument("--mpr-thick", type=int, default=1, help="voxels an oblique plane is deep: a slab (with --mpr-dir)")
+    parser.add_argument("--tumble-dir", type=str, default=None, help="also write the projection rotating about --tumble-axis here")
+    parser.add_argument("--tumble-angles", type=int, default=36, help="view angles around the full circle (with --tumble-dir)")
+    parser.add_argument("--tumble-axis", choices=["x", "y", "z"], default="x", help="the axis of the orbit (with --tumble-dir)")
+    parser.add_argument("--cpr-dir", type=str, default=None, help="also write the straightened curved reformat here")
+    parser.add_argument("--cpr-centreline", type=str, default=None, help=".npy of M >= 2 points (z, y, x) in voxels (with --cpr-dir)")
+    parser.add_argument("--cpr-angles", type=int, default=1, help="views around the centreline (with --cpr-dir)")
+    parser.add_argument("--cpr-width", type=int, default=65, help="samples across the vessel (with --cpr-dir)")
+    parser.add_argument("--cpr-thick", type=int, default=1, help="voxels the curved reformat is deep: a slab (with --cpr-dir)")
+    parser.add_argument("--reformat-sampling", choices=["nearest", "trilinear"], default="trilinear",
+                        help="how --mpr-dir, --tumble-dir and --cpr-dir sample the volume")
     parser.add_argument("--sts-dir", type=str, default=None, help="also write the sliding thin-slab projections here")
     parser.add_argument("--sts-thick", type=str, default=None, help="voxels per slab: T, or T,Tc,Ts for axial,coronal,sagittal")
     parser.add_argument("--sts-step", type=str, default=None, help="voxels a slab moves on: S or S,Sc,Ss (default: the thickness)")
@@ -168,7 +197,44 @@ def parse_args(argv=None):
         parser.error("--vr-background: three values R,G,B in 0 .. 255 expected")
     if opts.vr_angles < 1 or opts.vr_oversample < 1:
         parser.error("--vr-angles and --vr-oversample: at least 1 expected")
+    if (opts.mpr_dir is None) != (opts.mpr_normal is None):
+        parser.error("--mpr-dir and --mpr-normal need each other")
+    if opts.mpr_normal is not None:
+        try:
+            opts.mpr_normal = tuple(float(v) for v in opts.mpr_normal.split(","))
+        except ValueError:
+            parser.error("--mpr-normal: numbers X,Y,Z expected, got %r" % opts.mpr_normal)
+        if len(opts.mpr_normal) != 3 or not any(opts.mpr_normal):
+            parser.error("--mpr-normal: three numbers X,Y,Z, not all zero, expected")
+    if opts.mpr_count < 1 or opts.mpr_thick < 1 or not opts.mpr_pitch > 0:
+        parser.error("--mpr-count and --mpr-thick: at least 1, --mpr-pitch: above 0 expected")
+    if opts.tumble_angles < 1:
+        parser.error("--tumble-angles: at least one view angle expected")
+    if (opts.cpr_dir is None) != (opts.cpr_centreline is None):
+        parser.error("--cpr-dir and --cpr-centreline need each other")
+    if opts.cpr_angles < 1 or opts.cpr_width < 1 or opts.cpr_thick < 1:
+        parser.error("--cpr-angles, --cpr-width and --cpr-thick: at least 1 expected")
     return opts
+
+
+def reformat_tables(opts):
+    """The `SeriesTranslator(reformat=...)` tables of --mpr-dir / --tumble-dir / --cpr-dir by kind (None without any), and the
+    view angles of the rotating kinds."""
+    import numpy as np
+    from cta_gan_amd.infer import curved_lines, oblique_lines, orbit_lines, view_angles
+    tables, angles = {}, {}
+    if opts.mpr_dir is not None:
+        tables["mpr"] = lambda n, h, w: oblique_lines(n, h, w, opts.mpr_normal, count=opts.mpr_count, pitch=opts.mpr_pitch,
+                                                      thick=opts.mpr_thick, aspect=opts.aspect)
+    if opts.tumble_dir is not None:
+        angles["tumble"] = view_angles(opts.tumble_angles)
+        tables["tumble"] = lambda n, h, w: orbit_lines(n, h, w, angles["tumble"], axis=opts.tumble_axis, aspect=opts.aspect)
+    if opts.cpr_dir is not None:
+        centreline = np.load(opts.cpr_centreline)
+        angles["cpr"] = view_angles(opts.cpr_angles, 180.0)
+        tables["cpr"] = lambda n, h, w: curved_lines(n, h, w, centreline, angles=angles["cpr"], cols=opts.cpr_width,
+                                                     depth=opts.cpr_thick, aspect=opts.aspect)
+    return (tables or None), angles
 
 
 def main(argv=None):
@@ -206,6 +272,7 @@ def main(argv=None):
         vr_lut = transfer_function(TRANSFER_PRESETS[opts.vr_preset], opts.vr_oversample)
         vr_options = {"transfer": vr_lut, "wc": opts.vr_wc, "ww": opts.vr_ww, "sampling": opts.vr_sampling,
                       "oversample": opts.vr_oversample, "background": opts.vr_background}
+    reformat, reformat_angles = reformat_tables(opts)
     translate =SeriesTranslator(generator, batch=opts.batch, size=config.get("size"), wc=opts.wc, ww=opts.ww, hu=opts.hu,
                                  level=opts.level_dir is not None or opts.sub_level_dir is not None, device=device,
                                  subtract=opts.sub_output is not None, sub_median=not opts.sub_no_median, sub_floor=opts.sub_floor,
@@ -216,7 +283,8 @@ def main(argv=None):
                                  rotate_mode=opts.mip_mode, rotate_sampling=opts.rot_sampling, rotate_oversample=opts.rot_oversample,
                                  slabs=opts.sts, depth=opts.depth, depth_cue=opts.depth_cue,
                                  render=view_angles(opts.vr_angles, opts.vr_span) if opts.vr_dir is not None else None,
-                                 render_options=vr_options)
+                                 render_options=vr_options, reformat=reformat,
+                                 reformat_options={"mode": opts.mip_mode, "sampling": opts.reformat_sampling} if reformat else None)
     shown = "cued" if opts.depth_cue > 0 else "level"      # the plane the PNGs of the projections are written from
     out = translate(volume)
     np.save(opts.output, out["pix"])
@@ -277,6 +345,19 @@ os.path.join(opts.vr_dir, "vr_%03d.png" % i))
         np.savez(os.path.join(opts.vr_dir, "render.npz"), rgb=ren["rgb"], opacity=ren["opacity"], depth=ren["depth"],
                  angles=ren["angles"], lut=vr_lut)
         print("wrote %d volume-rendered views (%s) to %s" % (len(ren["angles"]), opts.vr_preset, opts.vr_dir), flush=True)
+    for kind, where in (("mpr", opts.mpr_dir), ("tumble", opts.tumble_dir), ("cpr", opts.cpr_dir)):
+        if where is None:
+            continue
+        from PIL import Image
+        os.makedirs(where, exist_ok=True)
+        planes = out["reformat"][kind]
+        for i, plane in enumerate(planes["level"]):
+            Image.fromarray(np.ascontiguousarray(plane)).save(os.path.join(where, "%s_%03d.png" % (kind, i)))
+        arrays = {"values": planes["values"], "level": planes["level"]}
+        if kind in reformat_angles:
+            arrays["angles"] = np.array(reformat_angles[kind], dtype=np.float64)
+        np.savez(os.path.join(where, "reformat.npz"), **arrays)
+        print("wrote %d %s reformat(s), %s sampling, to %s" % (len(planes["level"]), kind, opts.reformat_sampling, where), flush=True)
     if opts.sts_dir is not None:
         from PIL import Image
         from cta_gan_amd.infer import aspect_rows

@@ -48,6 +48,15 @@ straightened curved reformat along a vessel's centreline (`curved_lines`), any p
 stays on the device and one kernel samples it along lines given by a table of nine 16.16 integers per output line
 (`ops.reformat_lines`): nearest or trilinear sampling in exact integers, max / min / mean along rays of T steps, anisotropic
 voxels inside the table (`aspect`), one launch per table after the last chunk.
+
+The view protocol.  The five display classes above are views (`_SeriesView` holds what they share), and `SeriesTranslator` and
+the `*_volume` functions drive every one of them the same way.  A view is made for one volume shape and has `.n`, `.h`, `.w` and
+`.device`; `update(pix_chunk, n0)` takes a device chunk of slices n0 .. n0+K-1 on the current stream, in any order, every slice
+once; `result()` returns a tree on the device -- a dict of tensors, Nones and nested dicts -- once they have all arrived;
+`reset()` makes the view ready for the next volume of the same shape.  A view whose result has one plane per view angle keeps the
+angles as the host list `.angles`.  Where the classes differ: `SeriesProjector.update` forwards an empty chunk to ops (the others
+return early) and its `result` takes the window (the others take it at construction); `VolumeReformatter` also bounds the sides
+by `ops.REFORMAT_MAX_DIM`, checks the chunk's dtype and resolves device=None at the first chunk only.
 """
 from __future__ import annotations
 
@@ -122,7 +131,71 @@ def _check_depth(who, depth, cue, mode):
     return bool(depth), int(cue)
 
 
-class SeriesProjector:
+def _tree_to(tree, conv):
+    """A result tree -- a dict of tensors, Nones and nested dicts -- with `conv` applied to every tensor."""
+    if isinstance(tree, dict):
+        return {k: _tree_to(v, conv) for k, v in tree.items()}
+    return None if tree is None else conv(tree)
+
+
+def _tree_leaves(tree, path=()):
+    """[(path, tensor), ...]: the tensors of a result tree in its own order, each with the keys that lead to it."""
+    if isinstance(tree, dict):
+        return [leaf for k, v in tree.items() for leaf in _tree_leaves(v, path + (k,))]
+    return [] if tree is None else [(path, tree)]
+
+
+def _view_of_volume(who, volume, batch, device, make, result=lambda view: view.result(), upload=True):
+    """What the `*_volume` functions share: the view `make(n, h, w, device)` fed with a volume that already exists -- int16
+    [N, H, W], a host array / CPU tensor in chunks of `batch` slices (uploaded one after another, or handed over as they are with
+    upload=False) or a device tensor -- and its `result`, converted to the input's kind."""
+    is_np = isinstance(volume, np.ndarray)
+    vol = torch.from_numpy(np.ascontiguousarray(volume)) if is_np else volume
+    if not torch.is_tensor(vol) or vol.dtype != torch.int16 or vol.dim() != 3:
+        raise RuntimeError("%s: an int16 volume [N, H, W] expected" % who)
+    if int(batch) < 1:
+        raise ValueError("%s: batch >= 1 expected" % who)
+    on_host = not vol.is_cuda
+    n, h, w = vol.shape
+    view = make(n, h, w, device if on_host else vol.device)
+    with torch.cuda.device(view.device):
+        for s, e, _ in plan_chunks(n, batch):
+            view.update(vol[s:e].to(view.device) if on_host and upload else vol[s:e], s)
+        out = result(view)
+    if not on_host:
+        return out
+    return _tree_to(out, (lambda t: t.cpu().numpy()) if is_np else (lambda t: t.cpu()))
+
+
+class _SeriesView:
+    """What the five views share: the volume check, the device check, the check that a chunk lies in the volume, and a `reset()`
+    that does nothing.  A view takes `update(pix_chunk, n0)` for every chunk and gives `result()` once they have all arrived."""
+
+    def _volume(self, n, h, w):
+        self.n, self.h, self.w = int(n), int(h), int(w)
+        if min(self.n, self.h, self.w) < 1:
+            raise ValueError("%s: a volume of at least one voxel expected" % type(self).__name__)
+
+    def _gpu(self, device):
+        """-> the torch.device of `device` (None: the current one); anything but a GPU is refused."""
+        device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("%s: a GPU device is required (no CPU fallback)" % type(self).__name__)
+        return device
+
+    def _chunk(self, pix_chunk, n0, dtype=None):
+        """-> K, the slices of a chunk that lies in the volume (and, where the view asks for it, is of `dtype`)."""
+        k, n0 = pix_chunk.shape[0], int(n0)
+        if tuple(pix_chunk.shape[1:]) != (self.h, self.w) or n0 < 0 or n0 + k > self.n or (dtype is not None and pix_chunk.dtype != dtype):
+            raise RuntimeError("%s: %schunk %s at slice %d does not lie in the volume (%d, %d, %d)"
+                               % (type(self).__name__, "" if dtype is None else "int16 ", tuple(pix_chunk.shape), n0, self.n, self.h, self.w))
+        return k
+
+    def reset(self):
+        """For the next volume of the same shape: nothing to refill unless the view keeps accumulators."""
+
+
+class SeriesProjector(_SeriesView):
     """Running projections of an int16 volume [n, h, w] that arrives in chunks on the device.
 
     mode "max" (MIP), "min" (MinIP) or "mean" (ray sum / count, truncated toward zero); slab: slices per axial slab (None: the
@@ -142,9 +215,7 @@ class SeriesProjector:
         axes = tuple(axes)
         if not axes or any(a not in AXES for a in axes):
             raise ValueError("SeriesProjector: axes %r, a non-empty choice of %s expected" % (axes, AXES))
-        self.n, self.h, self.w = int(n), int(h), int(w)
-        if min(self.n, self.h, self.w) < 1:
-            raise ValueError("SeriesProjector: a volume of at least one voxel expected")
+        self._volume(n, h, w)
         self.mode, self.axes = mode, tuple(a for a in AXES if a in axes)
         self.code = ops.PROJECT_MODES[mode]
         self.thick = self.n if slab is None else int(slab)
@@ -153,9 +224,7 @@ class SeriesProjector:
         if self.depth and max(self.n, self.h, self.w) > 32767:
             raise ValueError("SeriesProjector: depth=True: no axis above %d voxels (a depth is an int16), got (%d, %d, %d)"
                              % (32767, self.n, self.h, self.w))
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("SeriesProjector: a GPU device is required (no CPU fallback)")
+        self.device = self._gpu(device)
         shapes = {"axial": (self.slabs, self.h, self.w), "coronal": (self.n, self.w), "sagittal": (self.n, self.h)}
         self.acc = {a: torch.empty(shapes[a], dtype=torch.int32, device=self.device) for a in self.axes}
         self.reset()
@@ -166,10 +235,7 @@ class SeriesProjector:
             t.fill_(identity)
 
     def update(self, pix_chunk, n0):
-        k = pix_chunk.shape[0]
-        if tuple(pix_chunk.shape[1:]) != (self.h, self.w) or int(n0) < 0 or int(n0) + k > self.n:
-            raise RuntimeError("SeriesProjector: chunk %s at slice %d does not lie in the volume (%d, %d, %d)"
-                               % (tuple(pix_chunk.shape), int(n0), self.n, self.h, self.w))
+        self._chunk(pix_chunk, n0)      # (an empty chunk goes on to ops, which returns early)
         if self.depth:
             ops.project_accumulate_depth(pix_chunk, int(n0), self.thick, self.code, **self.acc)
         else:
@@ -200,25 +266,9 @@ def project_volume(volume, mode="max", slab=None, wc=50.0, ww=400.0, hu=False, b
     a host array / CPU tensor (chunks of `batch` slices cross PCIe one after another) or a device tensor; depth and cue as
     `SeriesProjector`.  Returns what `SeriesProjector.result` returns, of the input's kind (numpy arrays, CPU tensors or device
     tensors)."""
-    is_np = isinstance(volume, np.ndarray)
-    vol = torch.from_numpy(np.ascontiguousarray(volume)) if is_np else volume
-    if not torch.is_tensor(vol) or vol.dtype != torch.int16 or vol.dim() != 3:
-        raise RuntimeError("project_volume: an int16 volume [N, H, W] expected")
-    if int(batch) < 1:
-        raise ValueError("project_volume: batch >= 1 expected")
-    on_host = not vol.is_cuda
-    n, h, w = vol.shape
-    proj = SeriesProjector(n, h, w, mode=mode, slab=slab, axes=axes, device=device if on_host else vol.device, depth=depth, cue=cue)
-    with torch.cuda.device(proj.device):
-        for s, e, _ in plan_chunks(n, batch):
-            proj.update(vol[s:e].to(proj.device) if on_host else vol[s:e], s)
-        out = proj.result(wc, ww, hu=hu, level=level)
-    return _projections_to_host(out, is_np) if on_host else out
-
-
-def _projections_to_host(out, is_np):
-    conv = (lambda t: t.cpu().numpy()) if is_np else (lambda t: t.cpu())
-    return {a: {k: None if t is None else conv(t) for k, t in d.items()} for a, d in out.items()}
+    return _view_of_volume("project_volume", volume, batch, device,
+                           lambda n, h, w, dev: SeriesProjector(n, h, w, mode=mode, slab=slab, axes=axes, device=dev, depth=depth, cue=cue),
+                           result=lambda proj: proj.result(wc, ww, hu=hu, level=level))
 
 
 def _per_axis(value, axes, what):
@@ -230,7 +280,7 @@ def _per_axis(value, axes, what):
     return {a: int(value) for a in axes}
 
 
-class SeriesSlabs:
+class SeriesSlabs(_SeriesView):
     """Sliding thin-slab projections (STS-MIP / MinIP / mean) of an int16 volume [n, h, w] that arrives in chunks on the device:
     slabs of `thick` voxels moved on by `step` voxels (`slab_windows`; step=None: thick, slabs that do not overlap) along "axial"
     [J_a, h, w] (over slices), "coronal" [J_c, n, w] (over the rows of the slab) and "sagittal" [J_s, n, h] (over its columns).
@@ -250,9 +300,7 @@ class SeriesSlabs:
         axes = tuple(axes)
         if not axes or any(a not in AXES for a in axes):
             raise ValueError("SeriesSlabs: axes %r, a non-empty choice of %s expected" % (axes, AXES))
-        self.n, self.h, self.w = int(n), int(h), int(w)
-        if min(self.n, self.h, self.w) < 1:
-            raise ValueError("SeriesSlabs: a volume of at least one voxel expected")
+        self._volume(n, h, w)
         self.mode, self.axes = mode, tuple(a for a in AXES if a in axes)
         self.code = ops.PROJECT_MODES[mode]
         self.given = _per_axis(thick, self.axes, "thick")      # what the kernels validate `step` against
@@ -262,9 +310,7 @@ class SeriesSlabs:
         for a in self.axes:
             self.slabs[a], self.thick[a], self.last_len[a] = slab_windows(extent[a], self.given[a], self.step[a])
         self.hu, self.window, self.want_level = bool(hu), (float(wc), float(ww)), bool(level)
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("SeriesSlabs: a GPU device is required (no CPU fallback)")
+        self.device = self._gpu(device)
         shapes = {"coronal": (self.n, self.w), "sagittal": (self.n, self.h)}
         self.values = {a: torch.empty((self.slabs[a],) + shapes[a], dtype=torch.int16, device=self.device)
                        for a in self.axes if a != "axial"}
@@ -286,10 +332,7 @@ class SeriesSlabs:
             self.acc.fill_(ops.PROJECT_IDENTITY[self.code])
 
     def update(self, pix_chunk, n0):
-        k = pix_chunk.shape[0]
-        if tuple(pix_chunk.shape[1:]) != (self.h, self.w) or int(n0) < 0 or int(n0) + k > self.n:
-            raise RuntimeError("SeriesSlabs: chunk %s at slice %d does not lie in the volume (%d, %d, %d)"
-                               % (tuple(pix_chunk.shape), int(n0), self.n, self.h, self.w))
+        k = self._chunk(pix_chunk, n0)
         if k < 1:
             return
         for a in self.values:
@@ -314,21 +357,9 @@ def slab_volume(volume, thick, step=None, mode="max", axes=AXES, wc=50.0, ww=400
     """The sliding thin-slab projections of a volume that already exists, the twin of `project_volume`: int16 [N, H, W], a host
     array / CPU tensor (chunks of `batch` slices cross PCIe one after another) or a device tensor.  Arguments as `SeriesSlabs`.
     Returns what `SeriesSlabs.result` returns, of the input's kind (numpy arrays, CPU tensors or device tensors)."""
-    is_np = isinstance(volume, np.ndarray)
-    vol = torch.from_numpy(np.ascontiguousarray(volume)) if is_np else volume
-    if not torch.is_tensor(vol) or vol.dtype != torch.int16 or vol.dim() != 3:
-        raise RuntimeError("slab_volume: an int16 volume [N, H, W] expected")
-    if int(batch) < 1:
-        raise ValueError("slab_volume: batch >= 1 expected")
-    on_host = not vol.is_cuda
-    n, h, w = vol.shape
-    slabs = SeriesSlabs(n, h, w, thick, step=step, mode=mode, axes=axes, wc=wc, ww=ww, hu=hu, level=level,
-                        device=device if on_host else vol.device)
-    with torch.cuda.device(slabs.device):
-        for s, e, _ in plan_chunks(n, batch):
-            slabs.update(vol[s:e].to(slabs.device) if on_host else vol[s:e], s)
-        out = slabs.result()
-    return _projections_to_host(out, is_np) if on_host else out
+    return _view_of_volume("slab_volume", volume, batch, device,
+                           lambda n, h, w, dev: SeriesSlabs(n, h, w, thick, step=step, mode=mode, axes=axes, wc=wc, ww=ww, hu=hu,
+                                                            level=level, device=dev))
 
 
 def default_detector(h, w):
@@ -392,7 +423,7 @@ def _check_sampling(who, sampling, oversample):
         raise ValueError("%s: oversample: an integer >= 1 expected, got %r" % (who, oversample))
 
 
-class SeriesRotator:
+class SeriesRotator(_SeriesView):
     """Rotating projections of an int16 volume [n, h, w] that arrives in chunks on the device: one plane [n, U] per view angle
     (degrees about the cranio-caudal axis; 0 = coronal, 90 = sagittal), mode "max", "min" or "mean" along rays of T voxels.
     detector: None (U = T = `default_detector`), an int or (U, T).  sampling: "nearest" or "bilinear"; oversample = s >= 1: a ray
@@ -412,9 +443,7 @@ class SeriesRotator:
         self.depth, self.cue = _check_depth("SeriesRotator", depth, cue, mode)
         _check_sampling("SeriesRotator", sampling, oversample)
         self.sampling, self.oversample = sampling, int(oversample)
-        self.n, self.h, self.w = int(n), int(h), int(w)
-        if min(self.n, self.h, self.w) < 1:
-            raise ValueError("SeriesRotator: a volume of at least one voxel expected")
+        self._volume(n, h, w)
         self.angles = [float(a) for a in angles]
         if not 1 <= len(self.angles) <= ops.ROTATE_MAX_DIM:
             raise ValueError("SeriesRotator: 1 .. %d view angles expected, got %d" % (ops.ROTATE_MAX_DIM, len(self.angles)))
@@ -424,9 +453,7 @@ class SeriesRotator:
         self.mode, self.code = mode, ops.PROJECT_MODES[mode]
         self.hu, self.window = bool(hu), (float(wc), float(ww))
         self.fill = (-1024 if self.hu else 0) if fill is None else int(fill)
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("SeriesRotator: a GPU device is required (no CPU fallback)")
+        self.device = self._gpu(device)
         self.table = ops.RotateTable([rotation_coefficients(a, self.h, self.w, self.u, self.t, self.oversample)
                                       for a in self.angles], self.device)
         shape = (len(self.angles), self.n, self.u)
@@ -436,14 +463,8 @@ class SeriesRotator:
         self.cued = torch.empty(shape, dtype=torch.uint8, device=self.device) if self.depth and level else None
         self._angles = torch.tensor(self.angles, dtype=torch.float64, device=self.device)
 
-    def reset(self):
-        """Nothing to refill (every update writes whole rows); kept for symmetry with `SeriesProjector`."""
-
     def update(self, pix_chunk, n0):
-        k = pix_chunk.shape[0]
-        if tuple(pix_chunk.shape[1:]) != (self.h, self.w) or int(n0) < 0 or int(n0) + k > self.n:
-            raise RuntimeError("SeriesRotator: chunk %s at slice %d does not lie in the volume (%d, %d, %d)"
-                               % (tuple(pix_chunk.shape), int(n0), self.n, self.h, self.w))
+        k = self._chunk(pix_chunk, n0)
         if k < 1:
             return
         if self.depth:
@@ -469,23 +490,10 @@ def rotate_volume(volume, angles, mode="max", detector=None, fill=None, wc=50.0,
     array / CPU tensor (chunks of `batch` slices cross PCIe one after another) or a device tensor; angles: degrees, or an int
     count of views around the full circle (`view_angles`); sampling, oversample, depth and cue as `SeriesRotator`.  Returns what
     `SeriesRotator.result` returns, of the input's kind."""
-    is_np = isinstance(volume, np.ndarray)
-    vol = torch.from_numpy(np.ascontiguousarray(volume)) if is_np else volume
-    if not torch.is_tensor(vol) or vol.dtype != torch.int16 or vol.dim() != 3:
-        raise RuntimeError("rotate_volume: an int16 volume [N, H, W] expected")
-    if int(batch) < 1:
-        raise ValueError("rotate_volume: batch >= 1 expected")
-    on_host = not vol.is_cuda
-    n, h, w = vol.shape
-    rot = SeriesRotator(n, h, w, _angle_list(angles), mode=mode, detector=detector, fill=fill, wc=wc, ww=ww, hu=hu, level=level,
-                        device=device if on_host else vol.device, sampling=sampling, oversample=oversample, depth=depth, cue=cue)
-    with torch.cuda.device(rot.device):
-        for s, e, _ in plan_chunks(n, batch):
-            rot.update(vol[s:e].to(rot.device) if on_host else vol[s:e], s)
-        out = rot.result()
-    if not on_host:
-        return out
-    return {k: None if t is None else (t.cpu().numpy() if is_np else t.cpu()) for k, t in out.items()}
+    return _view_of_volume("rotate_volume", volume, batch, device,
+                           lambda n, h, w, dev: SeriesRotator(n, h, w, _angle_list(angles), mode=mode, detector=detector, fill=fill,
+                                                              wc=wc, ww=ww, hu=hu, level=level, device=dev, sampling=sampling,
+                                                              oversample=oversample, depth=depth, cue=cue))
 
 
 def transfer_function(points, oversample=1):
@@ -546,7 +554,7 @@ def _transfer_table(who, transfer, oversample):
     return transfer_function(transfer, oversample)
 
 
-class SeriesRenderer:
+class SeriesRenderer(_SeriesView):
     """Volume-rendered rotating views of an int16 volume [n, h, w] that arrives in chunks on the device: the rays, angles,
     detector, sampling and oversample of `SeriesRotator`, composited front to back instead of reduced to a maximum, so that what
     lies in front hides what lies behind.  A sample's class is its 8-bit level in the transfer window (wc, ww) (with `hu` as
@@ -562,9 +570,7 @@ class SeriesRenderer:
                  oversample=1, background=(0, 0, 0), stop=128, surface=16384, depth=True, device=None):
         _check_sampling("SeriesRenderer", sampling, oversample)
         self.sampling, self.oversample = sampling, int(oversample)
-        self.n, self.h, self.w = int(n), int(h), int(w)
-        if min(self.n, self.h, self.w) < 1:
-            raise ValueError("SeriesRenderer: a volume of at least one voxel expected")
+        self._volume(n, h, w)
         self.angles = [float(a) for a in angles]
         if not 1 <= len(self.angles) <= ops.ROTATE_MAX_DIM:
             raise ValueError("SeriesRenderer: 1 .. %d view angles expected, got %d" % (ops.ROTATE_MAX_DIM, len(self.angles)))
@@ -582,9 +588,7 @@ class SeriesRenderer:
         self.steps = self.t * self.oversample
         self.hu, self.window = bool(hu), (float(wc), float(ww))
         lut = _transfer_table("SeriesRenderer", transfer, self.oversample)
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("SeriesRenderer: a GPU device is required (no CPU fallback)")
+        self.device = self._gpu(device)
         self.table = ops.RotateTable([rotation_coefficients(a, self.h, self.w, self.u, self.t, self.oversample)
                                       for a in self.angles], self.device)
         self.lut = ops.TransferTable(lut, self.device)
@@ -594,14 +598,8 @@ class SeriesRenderer:
         self.depth_plane = torch.empty(shape, dtype=torch.int16, device=self.device) if depth else None
         self._angles = torch.tensor(self.angles, dtype=torch.float64, device=self.device)
 
-    def reset(self):
-        """Nothing to refill (every update writes whole rows); kept for symmetry with `SeriesProjector`."""
-
     def update(self, pix_chunk, n0):
-        k = pix_chunk.shape[0]
-        if tuple(pix_chunk.shape[1:]) != (self.h, self.w) or int(n0) < 0 or int(n0) + k > self.n:
-            raise RuntimeError("SeriesRenderer: chunk %s at slice %d does not lie in the volume (%d, %d, %d)"
-                               % (tuple(pix_chunk.shape), int(n0), self.n, self.h, self.w))
+        k = self._chunk(pix_chunk, n0)
         if k < 1:
             return
         ops.project_render(pix_chunk, int(n0), self.table, self.steps, self.lut, rgb=self.rgb, opacity=self.opacity,
@@ -621,22 +619,8 @@ def render_volume(volume, angles, batch=64, device=None, **options):
     count of views around the full circle (`view_angles`); options: the keyword arguments of `SeriesRenderer` (transfer,
     detector, wc, ww, hu, sampling, oversample, background, stop, surface, depth).  Returns what `SeriesRenderer.result`
     returns, of the input's kind."""
-    is_np = isinstance(volume, np.ndarray)
-    vol = torch.from_numpy(np.ascontiguousarray(volume)) if is_np else volume
-    if not torch.is_tensor(vol) or vol.dtype != torch.int16 or vol.dim() != 3:
-        raise RuntimeError("render_volume: an int16 volume [N, H, W] expected")
-    if int(batch) < 1:
-        raise ValueError("render_volume: batch >= 1 expected")
-    on_host = not vol.is_cuda
-    n, h, w = vol.shape
-    ren = SeriesRenderer(n, h, w, _angle_list(angles), device=device if on_host else vol.device, **options)
-    with torch.cuda.device(ren.device):
-        for s, e, _ in plan_chunks(n, batch):
-            ren.update(vol[s:e].to(ren.device) if on_host else vol[s:e], s)
-        out = ren.result()
-    if not on_host:
-        return out
-    return {k: t.cpu().numpy() if is_np else t.cpu() for k, t in out.items()}
+    return _view_of_volume("render_volume", volume, batch, device,
+                           lambda n, h, w, dev: SeriesRenderer(n, h, w, _angle_list(angles), device=dev, **options))
 
 
 # ------------------------------------------------------------------------------------------------ lines in any direction
@@ -846,7 +830,7 @@ def curved_lines(n, h, w, centreline, angles=(0.0,), cols=65, depth=1, pitch=1.0
     return LineSet(np.stack(tables), depth * s, cols)
 
 
-class VolumeReformatter:
+class VolumeReformatter(_SeriesView):
     """Reformats of an int16 volume [n, h, w] that arrives in chunks and stays on the device: oblique planes, tumbling views,
     curved reformats -- every display whose rows cross slices (`ops.reformat_lines`, csrc/reformat.hip).  tables: {name: a
     `LineSet`, a pair (table [..., 9], T) with `cols` given here, or a callable (n, h, w) -> either}; mode "max" / "min" / "mean"
@@ -864,8 +848,8 @@ class VolumeReformatter:
             raise ValueError("%s: mode %r is not one of %s" % (who, mode, PROJECTIONS))
         if sampling not in REFORMAT_SAMPLINGS:
             raise ValueError("%s: sampling %r is not one of %s" % (who, sampling, REFORMAT_SAMPLINGS))
-        self.n, self.h, self.w = int(n), int(h), int(w)
-        if min(self.n, self.h, self.w) < 1 or max(self.n, self.h, self.w) > ops.REFORMAT_MAX_DIM:
+        self._volume(n, h, w)
+        if max(self.n, self.h, self.w) > ops.REFORMAT_MAX_DIM:      # the line tables address the sides in 16.16 fixed point
             raise ValueError("%s: n, h, w in 1 .. %d expected, got %d %d %d" % (who, ops.REFORMAT_MAX_DIM, self.n, self.h, self.w))
         if not isinstance(tables, dict) or not tables:
             raise ValueError("%s: tables: a dict {name: (table, T)} with at least one entry expected" % who)
@@ -882,9 +866,7 @@ class VolumeReformatter:
         self._seen = np.zeros(self.n, dtype=np.int64)
         per = 2 + (1 if self.want_level else 0)
         self.nbytes = 2 * self.n * self.h * self.w + sum(t.nbytes + per * (t.size // 9) * u for t, u, _ in self.lines.values())
-        self.device = None if device is None else torch.device(device)      # None: the current device at the first chunk
-        if self.device is not None and self.device.type != "cuda":
-            raise RuntimeError("%s: a GPU device is required (no CPU fallback)" % who)
+        self.device = None if device is None else self._gpu(device)      # None: the current device at the first chunk
         self.tables = self.volume = None      # on the device from the first chunk on
 
     def reset(self):
@@ -892,15 +874,12 @@ class VolumeReformatter:
         self._seen[:] = 0
 
     def update(self, pix_chunk, n0):
-        k, n0 = pix_chunk.shape[0], int(n0)
-        if tuple(pix_chunk.shape[1:]) != (self.h, self.w) or n0 < 0 or n0 + k > self.n or pix_chunk.dtype != torch.int16:
-            raise RuntimeError("VolumeReformatter: int16 chunk %s at slice %d does not lie in the volume (%d, %d, %d)"
-                               % (tuple(pix_chunk.shape), n0, self.n, self.h, self.w))
+        k, n0 = self._chunk(pix_chunk, n0, dtype=torch.int16), int(n0)      # (the copy below would convert another dtype)
         if k < 1:
             return
         if self.volume is None:
             if self.device is None:
-                self.device = torch.device("cuda", torch.cuda.current_device())
+                self.device = self._gpu(None)
             self.tables = {name: ops.LineTable(t, u, steps, self.device) for name, (t, u, steps) in self.lines.items()}
             self.volume = torch.empty((self.n, self.h, self.w), dtype=torch.int16, device=self.device)
         self.volume[n0:n0 + k].copy_(pix_chunk, non_blocking=True)
@@ -924,24 +903,12 @@ def reformat_volume(volume, tables, mode="max", sampling="trilinear", fill=None,
     """The reformats of a volume that already exists, the twin of `rotate_volume`: int16 [N, H, W], a host array / CPU tensor
     (chunks of `batch` slices cross PCIe one after another) or a device tensor; tables and the options as `VolumeReformatter`.
     Returns what `VolumeReformatter.result` returns, of the input's kind."""
-    is_np = isinstance(volume, np.ndarray)
-    vol = torch.from_numpy(np.ascontiguousarray(volume)) if is_np else volume
-    if not torch.is_tensor(vol) or vol.dtype != torch.int16 or vol.dim() != 3:
-        raise RuntimeError("reformat_volume: an int16 volume [N, H, W] expected")
-    if int(batch) < 1:
-        raise ValueError("reformat_volume: batch >= 1 expected")
-    on_host = not vol.is_cuda
-    n, h, w = vol.shape
-    dev = device if on_host else vol.device
-    ref = VolumeReformatter(n, h, w, tables, mode=mode, sampling=sampling, fill=fill, wc=wc, ww=ww, hu=hu, level=level,
-                            device=torch.device("cuda", torch.cuda.current_device()) if dev is None else dev, cols=cols)
-    with torch.cuda.device(ref.device):
-        for s, e, _ in plan_chunks(n, batch):
-            ref.update(vol[s:e], s)
-        out = ref.result()
-    if not on_host:
-        return out
-    return {name: {k: None if t is None else (t.cpu().numpy() if is_np else t.cpu()) for k, t in d.items()} for name, d in out.items()}
+    def make(n, h, w, dev):      # (the device is resolved here: the chunk loop runs under it)
+        return VolumeReformatter(n, h, w, tables, mode=mode, sampling=sampling, fill=fill, wc=wc, ww=ww, hu=hu, level=level,
+                                 device=torch.device("cuda", torch.cuda.current_device()) if dev is None else dev, cols=cols)
+
+    # host chunks go to `update` as they are: it copies them into the resident volume, the only time they cross PCIe
+    return _view_of_volume("reformat_volume", volume, batch, device, make, upload=False)
 
 
 def subtract_volume(cta, ct_hu, cta_is_hu=False, median=True, floor=0, ct_range=(None, None), wc=150.0, ww=300.0, level=True,
@@ -1044,7 +1011,6 @@ class SeriesTranslator:
         if self.reformat is not None and (not self.reformat or set(self.reformat_options) - set(REFORMAT_OPTIONS)):
             raise ValueError("SeriesTranslator: reformat needs at least one table, and reformat_options %r a dict with any of %s"
                              % (reformat_options, REFORMAT_OPTIONS))
-        self._reformatter = self._ref_host = None
         self.render = None if render is None else _angle_list(render)
         self.render_options = dict(render_options or {})
         if self.render is None and self.render_options:
@@ -1052,14 +1018,12 @@ class SeriesTranslator:
         if self.render is not None and (not self.render or set(self.render_options) - set(RENDER_OPTIONS)):
             raise ValueError("SeriesTranslator: render needs at least one angle, and render_options %r a dict with any of %s"
                              % (render_options, RENDER_OPTIONS))
-        self._renderer = self._ren_host = None
         if project_source not in PROJECT_SOURCES or (project_source == "sub" and not subtract):
             raise ValueError("SeriesTranslator: project_source %r: one of %s expected, and 'sub' needs subtract=True"
                              % (project_source, PROJECT_SOURCES))
         self.subtract, self.project_source = bool(subtract), project_source
         self.sub_median, self.sub_floor, self.sub_ct_range = bool(sub_median), sub_floor, tuple(sub_ct_range)
         self.sub_window = (float(sub_window[0]), float(sub_window[1]))
-        self._sub = self._sub_lvl = None
         if project is not None and project not in PROJECTIONS:
             raise ValueError("SeriesTranslator: project %r is not one of %s" % (project, PROJECTIONS))
         self.project, self.slab = project, slab
@@ -1075,13 +1039,10 @@ class SeriesTranslator:
         for mode in ([project] if project is not None else []) + ([self.rotate_mode] if self.rotate is not None else []):
             _check_depth("SeriesTranslator", self.depth, self.depth_cue, mode)
         self.rotate_sampling, self.rotate_oversample = rotate_sampling, int(rotate_oversample)
-        self._rotator = self._rot_host = None
         self.slabs = None if slabs is None else dict(slabs)
         if self.slabs is not None and ("thick" not in self.slabs or set(self.slabs) - {"thick", "step", "mode", "axes"}):
             raise ValueError("SeriesTranslator: slabs %r: a dict with 'thick' and any of 'step', 'mode', 'axes' expected" % (slabs,))
-        self._slabber = self._slab_host = None
         self.window = (float(wc), float(ww))
-        self._projector = self._proj_host = None
         self.generator = generator
         self.batch = int(batch)
         self.size = None if size is None else _pair(size)
@@ -1097,21 +1058,50 @@ class SeriesTranslator:
         self.h2d = torch.cuda.Stream(device=self.device)
         self.d2h = torch.cuda.Stream(device=self.device)
         self._hw = None
-        self._in = self._pix = self._lvl = None
+        self._in = self._out = None
+        # the planes a chunk brings back, by output key: the dtype, or None for a plane that is off and keeps its key
+        self._planes = {"pix": torch.int16, "level": torch.uint8 if self.level else None}
+        if self.subtract:
+            self._planes.update(sub=torch.int16, sub_level=torch.uint8 if self.level else None)
+        # the displays that are on, by output key: (the view of an (n, h, w) volume, its result, whether the output gains "angles")
+        self._displays = {}
+        if self.project is not None:
+            self._displays["projections"] = (
+                lambda n, h, w: SeriesProjector(n, h, w, mode=self.project, slab=self.slab, device=self.device, depth=self.depth,
+                                                cue=self.depth_cue),
+                lambda view: view.result(*self._view_window(), hu=self._view_hu()), False)
+        if self.rotate is not None:
+            self._displays["rotation"] = (
+                lambda n, h, w: SeriesRotator(n, h, w, self.rotate, mode=self.rotate_mode, **self._view_options(),
+                                              device=self.device, sampling=self.rotate_sampling, oversample=self.rotate_oversample,
+                                              depth=self.depth, cue=self.depth_cue),
+                SeriesRotator.result, True)
+        if self.slabs is not None:
+            self._displays["slabs"] = (
+                lambda n, h, w: SeriesSlabs(n, h, w, **self._view_options(), device=self.device, **self.slabs),
+                SeriesSlabs.result, False)
+        if self.render is not None:
+            self._displays["render"] = (
+                lambda n, h, w: SeriesRenderer(n, h, w, self.render, device=self.device, **{"hu": self._view_hu(), **self.render_options}),
+                SeriesRenderer.result, True)
+        if self.reformat is not None:
+            self._displays["reformat"] = (
+                lambda n, h, w: VolumeReformatter(n, h, w, self.reformat, **self._view_options(), device=self.device,
+                                                  **self.reformat_options),
+                VolumeReformatter.result, False)
+        self._views, self._view_host = {}, {}      # by output key: the view, the page-locked copy of its result
         # host seconds of the last call (scripts/export_bench.py): waiting to get a slot back, copying into the input slots,
         # copying out of the output slots, the whole call
         self.stats = {"wait": 0.0, "stage_in": 0.0, "stage_out": 0.0, "total": 0.0}
 
     def _stage(self, h, w):
-        """The page-locked slots for planes of h x w (kept between calls on volumes of one size)."""
+        """The page-locked slots for planes of h x w (kept between calls on volumes of one size): one input plane and one dict
+        of the output planes that are on per slot."""
         if self._hw != (h, w):
             shape = (self.batch, h, w)
             self._in = [torch.empty(shape, dtype=torch.int16, pin_memory=True) for _ in range(SLOTS)]
-            self._pix = [torch.empty(shape, dtype=torch.int16, pin_memory=True) for _ in range(SLOTS)]
-            self._lvl = [torch.empty(shape, dtype=torch.uint8, pin_memory=True) for _ in range(SLOTS)] if self.level else None
-            if self.subtract:
-                self._sub = [torch.empty(shape, dtype=torch.int16, pin_memory=True) for _ in range(SLOTS)]
-                self._sub_lvl = [torch.empty(shape, dtype=torch.uint8, pin_memory=True) for _ in range(SLOTS)] if self.level else None
+            self._out = [{key: torch.empty(shape, dtype=dtype, pin_memory=True) for key, dtype in self._planes.items() if dtype is not None}
+                         for _ in range(SLOTS)]
             self._hw = (h, w)
 
     def __call__(self, volume):
@@ -1127,20 +1117,13 @@ class SeriesTranslator:
         vol = vol.contiguous()
         n, h, w = vol.shape
         gsize = self.size or (h, w)
-        out_pix = torch.empty((n, h, w), dtype=torch.int16)
-        out_lvl = torch.empty((n, h, w), dtype=torch.uint8) if self.level else None
-        out_sub = torch.empty((n, h, w), dtype=torch.int16) if self.subtract else None
-        out_sub_lvl = torch.empty((n, h, w), dtype=torch.uint8) if self.subtract and self.level else None
+        out = {key: None if dtype is None else torch.empty((n, h, w), dtype=dtype) for key, dtype in self._planes.items()}
         if n == 0:
-            return self._with_sub(self._result(out_pix, out_lvl, is_np), out_sub, out_sub_lvl, is_np)
+            return _tree_to(out, (lambda t: t.numpy()) if is_np else (lambda t: t))
         self._stage(h, w)
         with torch.cuda.device(self.device):
             cur = torch.cuda.current_stream()
-            proj = self._projector_for(n, h, w)
-            rot = self._rotator_for(n, h, w)
-            slb = self._slabber_for(n, h, w)
-            ren = self._renderer_for(n, h, w)
-            ref = self._reformatter_for(n, h, w)
+            views = {key: self._view_for(key, n, h, w) for key in self._displays}
             in_free = [None] * SLOTS       # event: the slot's H2D copy has drained, the host may rewrite it
             pending = [None] * SLOTS       # (event, start, stop): the slot's D2H copy, not yet moved into the result
 
@@ -1151,13 +1134,8 @@ class SeriesTranslator:
                 t0 = clock()
                 ev.synchronize()
                 t1 = clock()
-                out_pix[s:e].copy_(self._pix[slot][:e - s])
-                if out_lvl is not None:
-                    out_lvl[s:e].copy_(self._lvl[slot][:e - s])
-                if out_sub is not None:
-                    out_sub[s:e].copy_(self._sub[slot][:e - s])
-                if out_sub_lvl is not None:
-                    out_sub_lvl[s:e].copy_(self._sub_lvl[slot][:e - s])
+                for key, buf in self._out[slot].items():
+                    out[key][s:e].copy_(buf[:e - s])
                 pending[slot] = None
                 stats["wait"] += t1 - t0
                 stats["stage_out"] += clock() - t1
@@ -1181,227 +1159,80 @@ class SeriesTranslator:
                 with torch.no_grad():
                     x = ops.series_inputs(dev_hu, gsize).unsqueeze(1)
                     fake = self.generator(x)
-                    pix, lvl = ops.export_slices(fake, self.wc[:k], self.ww[:k], size=(h, w), hu=self.hu, want_level=self.level)
-                    sub = sub_lvl = None
+                    planes = {}
+                    planes["pix"], planes["level"] = ops.export_slices(fake, self.wc[:k], self.ww[:k], size=(h, w), hu=self.hu,
+                                                                       want_level=self.level)
                     if self.subtract:
-                        sub, sub_lvl = ops.subtract_slices(pix, dev_hu, cta_is_hu=self.hu, median=self.sub_median,
-                                                           floor=self.sub_floor, ct_range=self.sub_ct_range, wc=self.sub_window[0],
-                                                           ww=self.sub_window[1], want_level=self.level)
-                    src = sub if self.project_source == "sub" else pix
-                    if proj is not None:
-                        proj.update(src, s)
-                    if rot is not None:
-                        rot.update(src, s)
-                    if slb is not None:
-                        slb.update(src, s)
-                    if ren is not None:
-                        ren.update(src, s)
-                    if ref is not None:
-                        ref.update(src, s)
+                        planes["sub"], planes["sub_level"] = ops.subtract_slices(
+                            planes["pix"], dev_hu, cta_is_hu=self.hu, median=self.sub_median, floor=self.sub_floor,
+                            ct_range=self.sub_ct_range, wc=self.sub_window[0], ww=self.sub_window[1], want_level=self.level)
+                    src = planes["sub" if self.project_source == "sub" else "pix"]
+                    for view in views.values():
+                        view.update(src, s)
                 computed = torch.cuda.Event()
                 computed.record(cur)
                 drain(slot)                          # the chunk that used this slot last: its D2H started two chunks ago
                 done = torch.cuda.Event()
                 with torch.cuda.stream(self.d2h):
                     self.d2h.wait_event(computed)
-                    self._pix[slot][:k].copy_(pix, non_blocking=True)
-                    pix.record_stream(self.d2h)
-                    if lvl is not None:
-                        self._lvl[slot][:k].copy_(lvl, non_blocking=True)
-                        lvl.record_stream(self.d2h)
-                    if sub is not None:
-                        self._sub[slot][:k].copy_(sub, non_blocking=True)
-                        sub.record_stream(self.d2h)
-                    if sub_lvl is not None:
-                        self._sub_lvl[slot][:k].copy_(sub_lvl, non_blocking=True)
-                        sub_lvl.record_stream(self.d2h)
+                    for key, buf in self._out[slot].items():
+                        buf[:k].copy_(planes[key], non_blocking=True)
+                        planes[key].record_stream(self.d2h)
                     done.record()
                 pending[slot] = (done, s, e)
-            proj_done = None
-            if proj is not None:      # one copy back, after the last chunk: it runs while the host drains the last slots
-                staged = self._stage_projections(proj.result(*self._view_window(), hu=self._view_hu()))
-                proj_done = torch.cuda.Event()
-                proj_done.record(cur)
-            rot_done = None
-            if rot is not None:       # the finished planes of every angle, staged the same way
-                rot_staged = self._stage_rotation(rot.result())
-                rot_done = torch.cuda.Event()
-                rot_done.record(cur)
-            slab_done = None
-            if slb is not None:       # the finished slab planes of every axis, staged the same way
-                slab_staged = self._stage_slabs(slb.result())
-                slab_done = torch.cuda.Event()
-                slab_done.record(cur)
-            ren_done = None
-            if ren is not None:       # the finished rendered views of every angle, staged the same way
-                ren_staged = self._stage_render(ren.result())
-                ren_done = torch.cuda.Event()
-                ren_done.record(cur)
-            ref_done = None
-            if ref is not None:       # the whole volume is on the device now: one launch per table, staged the same way
-                ref_staged = self._stage_reformat(ref.result())
-                ref_done = torch.cuda.Event()
-                ref_done.record(cur)
+            # one copy back per display, after the last chunk: the finished planes are staged here, before the last slots are
+            # drained, so that the copies run while the host drains (the reformats are one launch per table first: the whole
+            # volume is on the device now).  An event per display: the host clones one display's planes while the next one's
+            # are still being copied.
+            staged = {}
+            for key, view in views.items():
+                host, copied = self._stage_view(key, self._displays[key][1](view)), torch.cuda.Event()
+                copied.record(cur)
+                staged[key] = (host, copied)
             for slot in sorted(range(SLOTS), key=lambda q: pending[q][1] if pending[q] else -1):
                 drain(slot)
-            projections = None
-            if proj_done is not None:
+            shown = {}
+            for key, (host, copied) in staged.items():
                 t0 = clock()
-                proj_done.synchronize()
+                copied.synchronize()
                 stats["wait"] += clock() - t0
-                projections = {a: {k: t.clone().numpy() if is_np else t.clone() for k, t in d.items()} for a, d in staged.items()}
-            rotation = None
-            if rot_done is not None:
-                t0 = clock()
-                rot_done.synchronize()
-                stats["wait"] += clock() - t0
-                rotation = {k: t.clone().numpy() if is_np else t.clone() for k, t in rot_staged.items()}
-                rotation["angles"] = np.array(rot.angles, dtype=np.float64) if is_np else torch.tensor(rot.angles, dtype=torch.float64)
-            slab_out = None
-            if slab_done is not None:
-                t0 = clock()
-                slab_done.synchronize()
-                stats["wait"] += clock() - t0
-                slab_out = {a: {k: t.clone().numpy() if is_np else t.clone() for k, t in d.items()} for a, d in slab_staged.items()}
-            rendered = None
-            if ren_done is not None:
-                t0 = clock()
-                ren_done.synchronize()
-                stats["wait"] += clock() - t0
-                rendered = {k: t.clone().numpy() if is_np else t.clone() for k, t in ren_staged.items()}
-                rendered["angles"] = np.array(ren.angles, dtype=np.float64) if is_np else torch.tensor(ren.angles, dtype=torch.float64)
-            reformats = None
-            if ref_done is not None:
-                t0 = clock()
-                ref_done.synchronize()
-                stats["wait"] += clock() - t0
-                reformats = {a: {k: t.clone().numpy() if is_np else t.clone() for k, t in d.items()} for a, d in ref_staged.items()}
+                shown[key] = _tree_to(host, (lambda t: t.clone().numpy()) if is_np else (lambda t: t.clone()))
+                if self._displays[key][2]:
+                    angles = views[key].angles
+                    shown[key]["angles"] = np.array(angles, dtype=np.float64) if is_np else torch.tensor(angles, dtype=torch.float64)
         # the forwards above ran fused conv + InstanceNorm launches: none may have given up (raises)
         ops.nie_check("series inference")
         stats["total"] = clock() - t_call
-        out = self._with_sub(self._result(out_pix, out_lvl, is_np), out_sub, out_sub_lvl, is_np)
-        if projections is not None:
-            out["projections"] = projections
-        if rotation is not None:
-            out["rotation"] = rotation
-        if slab_out is not None:
-            out["slabs"] = slab_out
-        if rendered is not None:
-            out["render"] = rendered
-        if reformats is not None:
-            out["reformat"] = reformats
+        out = _tree_to(out, (lambda t: t.numpy()) if is_np else (lambda t: t))
+        out.update(shown)
         return out
 
-    def _stage_projections(self, dev):
-        """Start the copies of the finished projections into page-locked buffers (kept between calls on volumes of one shape)."""
-        shapes = {a: tuple(d["values"].shape) for a, d in dev.items()}
-        if self._proj_host is None or {a: tuple(d["values"].shape) for a, d in self._proj_host.items()} != shapes:
-            self._proj_host = {a: {k: torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for k, t in d.items()}
-                               for a, d in dev.items()}
-        for a, d in dev.items():
-            for k, t in d.items():
-                self._proj_host[a][k].copy_(t, non_blocking=True)
-        return self._proj_host
-
-    def _stage_rotation(self, dev):
-        """Start the copies of the rotating projections into page-locked buffers (kept between calls on volumes of one shape)."""
-        dev = {k: dev[k] for k in ("values", "level", "depth", "cued") if k in dev}
-        if self._rot_host is None or self._rot_host["values"].shape != dev["values"].shape or set(self._rot_host) != set(dev):
-            self._rot_host = {k: torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for k, t in dev.items()}
-        for k, t in dev.items():
-            self._rot_host[k].copy_(t, non_blocking=True)
-        return self._rot_host
-
-    def _stage_render(self, dev):
-        """Start the copies of the rendered views into page-locked buffers (kept between calls on volumes of one shape)."""
-        dev = {k: dev[k] for k in ("rgb", "opacity", "depth") if k in dev}
-        if self._ren_host is None or self._ren_host["rgb"].shape != dev["rgb"].shape or set(self._ren_host) != set(dev):
-            self._ren_host = {k: torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for k, t in dev.items()}
-        for k, t in dev.items():
-            self._ren_host[k].copy_(t, non_blocking=True)
-        return self._ren_host
-
-    def _stage_slabs(self, dev):
-        """Start the copies of the finished slab planes into page-locked buffers (kept between calls on volumes of one shape)."""
-        shapes = {a: tuple(d["values"].shape) for a, d in dev.items()}
-        if self._slab_host is None or {a: tuple(d["values"].shape) for a, d in self._slab_host.items()} != shapes:
-            self._slab_host = {a: {k: torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for k, t in d.items()}
-                               for a, d in dev.items()}
-        for a, d in dev.items():
-            for k, t in d.items():
-                self._slab_host[a][k].copy_(t, non_blocking=True)
-        return self._slab_host
-
-    def _stage_reformat(self, dev):
-        """Start the copies of the finished reformats into page-locked buffers (kept between calls on volumes of one shape)."""
-        shapes = {a: tuple(d["values"].shape) for a, d in dev.items()}
-        if self._ref_host is None or {a: tuple(d["values"].shape) for a, d in self._ref_host.items()} != shapes:
-            self._ref_host = {a: {k: torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for k, t in d.items()}
-                              for a, d in dev.items()}
-        for a, d in dev.items():
-            for k, t in d.items():
-                self._ref_host[a][k].copy_(t, non_blocking=True)
-        return self._ref_host
-
-    def _reformatter_for(self, n, h, w):
-        """The `VolumeReformatter` of an (n, h, w) volume, kept between calls on volumes of one shape; None without `reformat`."""
-        if self.reformat is None:
-            return None
-        r = self._reformatter
-        if r is None or (r.n, r.h, r.w) != (n, h, w):
-            wc, ww = self._view_window()
-            r = self._reformatter = VolumeReformatter(n, h, w, self.reformat, wc=wc, ww=ww, hu=self._view_hu(), device=self.device,
-                                                      **self.reformat_options)
+    def _view_for(self, key, n, h, w):
+        """The view of display `key` for an (n, h, w) volume, kept between calls on volumes of one shape (and reset for the next)."""
+        view = self._views.get(key)
+        if view is None or (view.n, view.h, view.w) != (n, h, w):
+            view = self._views[key] = self._displays[key][0](n, h, w)
         else:
-            r.reset()
-        return r
+            view.reset()
+        return view
 
-    def _slabber_for(self, n, h, w):
-        """The `SeriesSlabs` of an (n, h, w) volume, kept between calls on volumes of one shape; None without `slabs`."""
-        if self.slabs is None:
-            return None
-        s = self._slabber
-        if s is None or (s.n, s.h, s.w) != (n, h, w):
-            wc, ww = self._view_window()
-            s = self._slabber = SeriesSlabs(n, h, w, wc=wc, ww=ww, hu=self._view_hu(), device=self.device, **self.slabs)
-        else:
-            s.reset()
-        return s
+    def _stage_view(self, key, tree):
+        """Start the copies of a view's finished result into page-locked buffers, one per tensor of the tree (kept between calls
+        while every tensor's place, shape and dtype stay as they are).  A view's device "angles" are not staged: the output's are
+        made from the view's host list."""
+        if self._displays[key][2]:
+            tree = {k: t for k, t in tree.items() if k != "angles"}
+        dev, host = _tree_leaves(tree), self._view_host.get(key)
+        if host is None or [(p, t.shape, t.dtype) for p, t in _tree_leaves(host)] != [(p, t.shape, t.dtype) for p, t in dev]:
+            host = self._view_host[key] = _tree_to(tree, lambda t: torch.empty(t.shape, dtype=t.dtype, pin_memory=True))
+        for (_, buf), (_, t) in zip(_tree_leaves(host), dev):
+            buf.copy_(t, non_blocking=True)
+        return host
 
-    def _renderer_for(self, n, h, w):
-        """The renderer of an (n, h, w) volume, kept between calls on volumes of one shape; None without `render`."""
-        if self.render is None:
-            return None
-        r = self._renderer
-        if r is None or (r.n, r.h, r.w) != (n, h, w):
-            options = dict(self.render_options)
-            options.setdefault("hu", self._view_hu())
-            r = self._renderer = SeriesRenderer(n, h, w, self.render, device=self.device, **options)
-        return r
-
-    def _rotator_for(self, n, h, w):
-        """The rotator of an (n, h, w) volume, kept between calls on volumes of one shape; None without `rotate`."""
-        if self.rotate is None:
-            return None
-        r = self._rotator
-        if r is None or (r.n, r.h, r.w) != (n, h, w):
-            wc, ww = self._view_window()
-            r = self._rotator = SeriesRotator(n, h, w, self.rotate, mode=self.rotate_mode, wc=wc, ww=ww, hu=self._view_hu(),
-                                              device=self.device, sampling=self.rotate_sampling, oversample=self.rotate_oversample,
-                                              depth=self.depth, cue=self.depth_cue)
-        return r
-
-    def _projector_for(self, n, h, w):
-        """The projector of an (n, h, w) volume, kept between calls on volumes of one shape; None without `project`."""
-        if self.project is None:
-            return None
-        p = self._projector
-        if p is None or (p.n, p.h, p.w) != (n, h, w):
-            p = self._projector = SeriesProjector(n, h, w, mode=self.project, slab=self.slab, device=self.device, depth=self.depth,
-                                                  cue=self.depth_cue)
-        else:
-            p.reset()
-        return p
+    def _view_options(self):
+        """The window and `hu` of the views that take them at construction."""
+        wc, ww = self._view_window()
+        return {"wc": wc, "ww": ww, "hu": self._view_hu()}
 
     def _view_window(self):
         """The window of the projections' and the rotation's levels: the subtraction's when that is what they show."""
@@ -1410,15 +1241,3 @@ class SeriesTranslator:
     def _view_hu(self):
         """A subtraction value is a HU difference: 0 is the window's zero, whatever convention the synthesized pixels use."""
         return True if self.project_source == "sub" else self.hu
-
-    def _with_sub(self, out, sub, sub_lvl, is_np):
-        if self.subtract:
-            out["sub"] = sub.numpy() if is_np else sub
-            out["sub_level"] = None if sub_lvl is None else (sub_lvl.numpy() if is_np else sub_lvl)
-        return out
-
-    @staticmethod
-    def _result(pix, lvl, is_np):
-        if is_np:
-            return {"pix": pix.numpy(), "level": None if lvl is None else lvl.numpy()}
-        return {"pix": pix, "level": lvl}

@@ -1684,14 +1684,41 @@ def _project_mode(mode, what):
     return code
 
 
-def _project_acc(t, shape, name):
+def _project_acc(who, t, shape, name):
     if t is None:
         return
-    if not t.is_cuda or t.dtype != torch.int32 or not t.is_contiguous():
-        raise RuntimeError("project_accumulate: %s must be a contiguous int32 tensor on the GPU" % name)
+    if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.int32 or not t.is_contiguous():
+        raise RuntimeError("%s: %s must be a contiguous int32 tensor on the GPU" % (who, name))
     if t.dim() != len(shape) or t.shape[0] < shape[0] or tuple(t.shape[1:]) != tuple(shape[1:]):
-        raise RuntimeError("project_accumulate: %s of shape %s cannot take this chunk (needs [>= %d%s])"
-                           % (name, tuple(t.shape), shape[0], "".join(", %d" % v for v in shape[1:])))
+        raise RuntimeError("%s: %s of shape %s cannot take this chunk (needs [>= %d%s])"
+                           % (who, name, tuple(t.shape), shape[0], "".join(", %d" % v for v in shape[1:])))
+
+
+def _accumulate_args(who, pix, n0, thick, axial, coronal, sagittal, longest=None):
+    """The checks `project_accumulate` and `project_accumulate_depth` share -> (x, n0, thick): the contiguous chunk and the two
+    integers, or None for an empty chunk.  longest: the most voxels an axis may have (the depth's int16), None: no bound."""
+    if not torch.is_tensor(pix) or not pix.is_cuda:
+        raise RuntimeError("%s: CPU tensors are not supported (no CPU fallback)" % who)
+    if pix.dtype != torch.int16 or pix.dim() != 3:
+        raise RuntimeError("%s: pix must be int16 (K, H, W), got %s %s" % (who, pix.dtype, tuple(pix.shape)))
+    n0, thick = int(n0), int(thick)
+    if n0 < 0 or thick < 1:
+        raise RuntimeError("%s: n0 >= 0 and thick >= 1 expected, got n0=%d thick=%d" % (who, n0, thick))
+    if axial is None and coronal is None and sagittal is None:
+        raise RuntimeError("%s: at least one accumulator expected" % who)
+    x = pix.contiguous()
+    k, h, w = x.shape
+    if k < 1:
+        return None
+    if longest is not None and max(n0 + k, h, w) > longest:
+        raise RuntimeError("%s: a depth is an int16: no axis above %d voxels, got n0 + K = %d, H = %d, W = %d"
+                           % (who, longest, n0 + k, h, w))
+    _project_acc(who, axial, ((n0 + k - 1) // thick + 1, h, w), "axial")
+    _project_acc(who, coronal, (n0 + k, w), "coronal")
+    _project_acc(who, sagittal, (n0 + k, h), "sagittal")
+    if any(t is not None and t.device != x.device for t in (axial, coronal, sagittal)):
+        raise RuntimeError("%s: pix and the accumulators must live on one device" % who)
+    return x, n0, thick
 
 
 def project_accumulate(pix, n0, thick, mode, axial=None, coronal=None, sagittal=None):
@@ -1701,25 +1728,24 @@ def project_accumulate(pix, n0, thick, mode, axial=None, coronal=None, sagittal=
     the reduction over H, sagittal (N, H) = the reduction over W.  The caller fills them with PROJECT_IDENTITY[mode] before the
     first chunk; every call combines.  Exact integer arithmetic, the same bits on every run."""
     lib = _lib.load()
-    if not pix.is_cuda:
-        raise RuntimeError("project_accumulate: CPU tensors are not supported (no CPU fallback)")
-    if pix.dtype != torch.int16 or pix.dim() != 3:
-        raise RuntimeError("project_accumulate: pix must be int16 (K, H, W), got %s %s" % (pix.dtype, tuple(pix.shape)))
     code = _project_mode(mode, "project_accumulate")
-    n0, thick = int(n0), int(thick)
-    if n0 < 0 or thick < 1:
-        raise RuntimeError("project_accumulate: n0 >= 0 and thick >= 1 expected, got n0=%d thick=%d" % (n0, thick))
-    if axial is None and coronal is None and sagittal is None:
-        raise RuntimeError("project_accumulate: at least one accumulator expected")
-    x = pix.contiguous()
-    k, h, w = x.shape
-    if k < 1:
+    args = _accumulate_args("project_accumulate", pix, n0, thick, axial, coronal, sagittal)
+    if args is None:
         return
-    _project_acc(axial, ((n0 + k - 1) // thick + 1, h, w), "axial")
-    _project_acc(coronal, (n0 + k, w), "coronal")
-    _project_acc(sagittal, (n0 + k, h), "sagittal")
+    x, n0, thick = args
+    k, h, w = x.shape
     _lib.check(lib.ctg_project_accumulate(_p(x), k, h, w, n0, thick, code, _p(axial), _p(coronal), _p(sagittal), _stream()),
                "ctg_project_accumulate")
+
+
+def _finish_acc(who, acc):
+    """The accumulator check of `project_finish` and `project_finish_depth` -> its planes (1 for a 2-d accumulator)."""
+    if not torch.is_tensor(acc) or not acc.is_cuda:
+        raise RuntimeError("%s: CPU tensors are not supported (no CPU fallback)" % who)
+    if acc.dtype != torch.int32 or acc.dim() not in (2, 3) or not acc.is_contiguous():
+        raise RuntimeError("%s: a contiguous int32 accumulator of 2 or 3 dimensions expected, got %s %s"
+                           % (who, acc.dtype, tuple(acc.shape)))
+    return acc.shape[0] if acc.dim() == 3 else 1
 
 
 def project_finish(acc, mode, div=1, div_last=None, wc=50.0, ww=400.0, hu=False, want_values=True, want_level=True):
@@ -1728,11 +1754,7 @@ def project_finish(acc, mode, div=1, div_last=None, wc=50.0, ww=400.0, hu=False,
     the last axial slab may be shorter); level uint8 = the 8-bit window level `export_slices` gives a pixel of that stored value
     (hu: the values are stored values minus 1024).  Either is None when not wanted."""
     lib = _lib.load()
-    if not acc.is_cuda:
-        raise RuntimeError("project_finish: CPU tensors are not supported (no CPU fallback)")
-    if acc.dtype != torch.int32 or acc.dim() not in (2, 3) or not acc.is_contiguous():
-        raise RuntimeError("project_finish: a contiguous int32 accumulator of 2 or 3 dimensions expected, got %s %s"
-                           % (acc.dtype, tuple(acc.shape)))
+    planes = _finish_acc("project_finish", acc)
     if not (want_values or want_level):
         raise RuntimeError("project_finish: values, level or both expected")
     code = _project_mode(mode, "project_finish")
@@ -1740,7 +1762,6 @@ def project_finish(acc, mode, div=1, div_last=None, wc=50.0, ww=400.0, hu=False,
     div_last = div if div_last is None else int(div_last)
     if code == 2 and (div < 1 or div_last < 1):
         raise RuntimeError("project_finish: div >= 1 expected, got %d / %d" % (div, div_last))
-    planes = acc.shape[0] if acc.dim() == 3 else 1
     values = torch.empty(acc.shape, dtype=torch.int16, device=acc.device) if want_values else None
     level = torch.empty(acc.shape, dtype=torch.uint8, device=acc.device) if want_level else None
     if acc.numel() == 0:
@@ -1780,11 +1801,50 @@ class RotateTable:
         return self.count
 
 
-def _rotate_out(t, dtype, name):
-    if t is None:
-        return
-    if not torch.is_tensor(t) or not t.is_cuda or t.dtype != dtype or not t.is_contiguous() or t.dim() != 3:
-        raise RuntimeError("project_rotate: %s must be a contiguous %s tensor (A, N, U) on the GPU" % (name, dtype))
+def _fill_value(who, fill, hu):
+    """`fill` of the kernels that sample along rays: an int16 value, default air (0, or -1024 with hu)."""
+    fill = (-1024 if hu else 0) if fill is None else int(fill)
+    if not -32768 <= fill <= 32767:
+        raise RuntimeError("%s: fill %d is not an int16 value" % (who, fill))
+    return fill
+
+
+def _rotate_args(who, pix, n0, coef, t, sampling, outs):
+    """The checks `project_rotate`, `project_rotate_depth` and `project_render` share -> (x, table, (k, h, w, n0, n, a, u, t)):
+    the contiguous chunk, the `RotateTable` and the sizes the entry points take.  outs: (name, tensor or None, dtype) of every
+    output plane (A, N, U); the one named "rgb" is (A, N, U, 3)."""
+    if not torch.is_tensor(pix) or not pix.is_cuda:
+        raise RuntimeError("%s: CPU tensors are not supported (no CPU fallback)" % who)
+    if pix.dtype != torch.int16 or pix.dim() != 3:
+        raise RuntimeError("%s: pix must be int16 (K, H, W), got %s %s" % (who, pix.dtype, tuple(pix.shape)))
+    if sampling not in ROTATE_SAMPLINGS:
+        raise RuntimeError("%s: sampling %r is not one of %s" % (who, sampling, tuple(ROTATE_SAMPLINGS)))
+    for name, o, dtype in outs:
+        dims = 4 if name == "rgb" else 3
+        if o is not None and (not torch.is_tensor(o) or not o.is_cuda or o.dtype != dtype or not o.is_contiguous() or o.dim() != dims
+                              or (dims == 4 and o.shape[3] != 3)):
+            raise RuntimeError("%s: %s must be a contiguous %s tensor (A, N, U%s) on the GPU" % (who, name, dtype, ", 3" if dims == 4 else ""))
+    given = [o for _, o, _ in outs if o is not None]
+    if not given:
+        raise RuntimeError("%s: at least one of %s expected" % (who, ", ".join(name for name, _, _ in outs)))
+    if any(o.shape[:3] != given[0].shape[:3] for o in given):
+        raise RuntimeError("%s: the outputs differ in shape: %s" % (who, [tuple(o.shape) for o in given]))
+    if torch.is_tensor(coef) and coef.is_cuda:
+        raise RuntimeError("%s: the coefficients are checked on the host: pass a host table or an ops.RotateTable" % who)
+    table = coef if isinstance(coef, RotateTable) else RotateTable(coef, pix.device)
+    if any(o.device != pix.device for o in given + [table.dev]):
+        raise RuntimeError("%s: pix, the coefficient table and the outputs must live on one device" % who)
+    a, n, u = given[0].shape[:3]
+    x = pix.contiguous()
+    k, h, w = x.shape
+    n0, t = int(n0), int(t)
+    if a != table.count:
+        raise RuntimeError("%s: %d planes for a table of %d angles" % (who, a, table.count))
+    if k < 1 or n0 < 0 or n0 + k > n:
+        raise RuntimeError("%s: chunk of %d slices at slice %d does not lie in the volume of %d" % (who, k, n0, n))
+    if not (1 <= min(h, w, u, t) and max(h, w, u, t) <= ROTATE_MAX_DIM):
+        raise RuntimeError("%s: H, W, U, T in 1 .. %d expected, got %d %d %d %d" % (who, ROTATE_MAX_DIM, h, w, u, t))
+    return x, table, (k, h, w, n0, n, a, u, t)
 
 
 def project_rotate(pix, n0, coef, t, mode, values=None, level=None, fill=None, wc=50.0, ww=400.0, hu=False, sampling="nearest"):
@@ -1798,39 +1858,11 @@ def project_rotate(pix, n0, coef, t, mode, values=None, level=None, fill=None, w
     -1024 with hu) where a ray misses the slice, and the 8-bit window level of that value.  Exact integer arithmetic: equal to
     numpy bit for bit."""
     lib = _lib.load()
-    if not torch.is_tensor(pix) or not pix.is_cuda:
-        raise RuntimeError("project_rotate: CPU tensors are not supported (no CPU fallback)")
-    if pix.dtype != torch.int16 or pix.dim() != 3:
-        raise RuntimeError("project_rotate: pix must be int16 (K, H, W), got %s %s" % (pix.dtype, tuple(pix.shape)))
     code = _project_mode(mode, "project_rotate")
-    if sampling not in ROTATE_SAMPLINGS:
-        raise RuntimeError("project_rotate: sampling %r is not one of %s" % (sampling, tuple(ROTATE_SAMPLINGS)))
-    entry = ROTATE_SAMPLINGS[sampling]
-    if values is None and level is None:
-        raise RuntimeError("project_rotate: values, level or both expected")
-    _rotate_out(values, torch.int16, "values")
-    _rotate_out(level, torch.uint8, "level")
-    out = values if values is not None else level
-    if values is not None and level is not None and values.shape != level.shape:
-        raise RuntimeError("project_rotate: values %s and level %s differ in shape" % (tuple(values.shape), tuple(level.shape)))
-    if torch.is_tensor(coef) and coef.is_cuda:
-        raise RuntimeError("project_rotate: the coefficients are checked on the host: pass a host table or an ops.RotateTable")
-    table = coef if isinstance(coef, RotateTable) else RotateTable(coef, pix.device)
-    if any(x is not None and x.device != pix.device for x in (values, level, table.dev)):
-        raise RuntimeError("project_rotate: pix, the coefficient table, values and level must live on one device")
-    a, n, u = out.shape
-    x = pix.contiguous()
-    k, h, w = x.shape
-    n0, t, hu = int(n0), int(t), bool(hu)
-    fill = (-1024 if hu else 0) if fill is None else int(fill)
-    if a != table.count:
-        raise RuntimeError("project_rotate: %d planes for a table of %d angles" % (a, table.count))
-    if k < 1 or n0 < 0 or n0 + k > n:
-        raise RuntimeError("project_rotate: chunk of %d slices at slice %d does not lie in the volume of %d" % (k, n0, n))
-    if not (1 <= min(h, w, u, t) and max(h, w, u, t) <= ROTATE_MAX_DIM):
-        raise RuntimeError("project_rotate: H, W, U, T in 1 .. %d expected, got %d %d %d %d" % (ROTATE_MAX_DIM, h, w, u, t))
-    if not -32768 <= fill <= 32767:
-        raise RuntimeError("project_rotate: fill %d is not an int16 value" % fill)
+    x, table, (k, h, w, n0, n, a, u, t) = _rotate_args("project_rotate", pix, n0, coef, t, sampling,
+                                                       (("values", values, torch.int16), ("level", level, torch.uint8)))
+    entry, hu = ROTATE_SAMPLINGS[sampling], bool(hu)
+    fill = _fill_value("project_rotate", fill, hu)
     _lib.check(getattr(lib, entry)(_p(x), k, h, w, n0, n, _p(table.dev), a, u, t, code, fill, float(wc), float(ww), int(hu),
                                    _p(values), _p(level), _stream()), entry)
 
@@ -1862,40 +1894,12 @@ def project_rotate_depth(pix, n0, coef, t, mode, values=None, level=None, depth=
     level itself).  values and level are what `project_rotate` writes.  Any of the four may be None, not all."""
     lib = _lib.load()
     who = "project_rotate_depth"
-    if not torch.is_tensor(pix) or not pix.is_cuda:
-        raise RuntimeError("%s: CPU tensors are not supported (no CPU fallback)" % who)
-    if pix.dtype != torch.int16 or pix.dim() != 3:
-        raise RuntimeError("%s: pix must be int16 (K, H, W), got %s %s" % (who, pix.dtype, tuple(pix.shape)))
     code = _depth_mode(mode, who)
     cue = _depth_cue(cue, who)
-    if sampling not in _ROTATE_SAMPLING_CODES:
-        raise RuntimeError("%s: sampling %r is not one of %s" % (who, sampling, tuple(_ROTATE_SAMPLING_CODES)))
-    outs = (("values", values, torch.int16), ("level", level, torch.uint8), ("depth", depth, torch.int16), ("cued", cued, torch.uint8))
-    given = [o for _, o, _ in outs if o is not None]
-    if not given:
-        raise RuntimeError("%s: at least one of values, level, depth, cued expected" % who)
-    for name, o, dtype in outs:
-        _rotate_out(o, dtype, name)
-    if any(o.shape != given[0].shape for o in given):
-        raise RuntimeError("%s: the outputs differ in shape: %s" % (who, [tuple(o.shape) for o in given]))
-    if torch.is_tensor(coef) and coef.is_cuda:
-        raise RuntimeError("%s: the coefficients are checked on the host: pass a host table or an ops.RotateTable" % who)
-    table = coef if isinstance(coef, RotateTable) else RotateTable(coef, pix.device)
-    if any(o.device != pix.device for o in given + [table.dev]):
-        raise RuntimeError("%s: pix, the coefficient table and the outputs must live on one device" % who)
-    a, n, u = given[0].shape
-    x = pix.contiguous()
-    k, h, w = x.shape
-    n0, t, hu = int(n0), int(t), bool(hu)
-    fill = (-1024 if hu else 0) if fill is None else int(fill)
-    if a != table.count:
-        raise RuntimeError("%s: %d planes for a table of %d angles" % (who, a, table.count))
-    if k < 1 or n0 < 0 or n0 + k > n:
-        raise RuntimeError("%s: chunk of %d slices at slice %d does not lie in the volume of %d" % (who, k, n0, n))
-    if not (1 <= min(h, w, u, t) and max(h, w, u, t) <= ROTATE_MAX_DIM):
-        raise RuntimeError("%s: H, W, U, T in 1 .. %d expected, got %d %d %d %d" % (who, ROTATE_MAX_DIM, h, w, u, t))
-    if not -32768 <= fill <= 32767:
-        raise RuntimeError("%s: fill %d is not an int16 value" % (who, fill))
+    x, table, (k, h, w, n0, n, a, u, t) = _rotate_args(who, pix, n0, coef, t, sampling, (
+        ("values", values, torch.int16), ("level", level, torch.uint8), ("depth", depth, torch.int16), ("cued", cued, torch.uint8)))
+    hu = bool(hu)
+    fill = _fill_value(who, fill, hu)
     _lib.check(lib.ctg_project_rotate_depth(_p(x), k, h, w, n0, n, _p(table.dev), a, u, t, code, _ROTATE_SAMPLING_CODES[sampling], fill,
                                             cue, float(wc), float(ww), int(hu), _p(values), _p(level), _p(depth), _p(cued), _stream()),
                "ctg_project_rotate_depth")
@@ -1924,14 +1928,6 @@ class TransferTable:
         self.dev = torch.from_numpy(self.host.view(np.int16)).to(self.device).view(torch.uint16)
 
 
-def _render_out(t, dtype, dims, name):
-    if t is None:
-        return
-    if not torch.is_tensor(t) or not t.is_cuda or t.dtype != dtype or not t.is_contiguous() or t.dim() != dims \
-            or (dims == 4 and t.shape[3] != 3):
-        raise RuntimeError("project_render: %s must be a contiguous %s tensor (A, N, U%s) on the GPU" % (name, dtype, ", 3" if dims == 4 else ""))
-
-
 def _render_int(who, name, v, lo, hi):
     if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
         raise RuntimeError("%s: %s: an integer in %d .. %d expected, got %r" % (who, name, lo, hi, v))
@@ -1950,12 +1946,6 @@ def project_render(pix, n0, coef, t, lut, rgb=None, opacity=None, depth=None, ba
     nothing else.  Exact integer arithmetic: equal to numpy bit for bit."""
     lib = _lib.load()
     who = "project_render"
-    if not torch.is_tensor(pix) or not pix.is_cuda:
-        raise RuntimeError("%s: CPU tensors are not supported (no CPU fallback)" % who)
-    if pix.dtype != torch.int16 or pix.dim() != 3:
-        raise RuntimeError("%s: pix must be int16 (K, H, W), got %s %s" % (who, pix.dtype, tuple(pix.shape)))
-    if sampling not in _ROTATE_SAMPLING_CODES:
-        raise RuntimeError("%s: sampling %r is not one of %s" % (who, sampling, tuple(_ROTATE_SAMPLING_CODES)))
     stop = _render_int(who, "stop", stop, 0, RENDER_OPAQUE - 1)
     surface = _render_int(who, "surface", surface, 1, RENDER_OPAQUE)
     try:
@@ -1965,30 +1955,13 @@ def project_render(pix, n0, coef, t, lut, rgb=None, opacity=None, depth=None, ba
     if len(bg) != 3:
         raise RuntimeError("%s: background: three integers in 0 .. 255 expected, got %r" % (who, background))
     bg = tuple(_render_int(who, "background", v, 0, 255) for v in bg)
-    _render_out(rgb, torch.uint8, 4, "rgb")
-    _render_out(opacity, torch.uint8, 3, "opacity")
-    _render_out(depth, torch.int16, 3, "depth")
-    given = [o for o in (rgb, opacity, depth) if o is not None]
-    if not given:
-        raise RuntimeError("%s: at least one of rgb, opacity, depth expected" % who)
-    if any(o.shape[:3] != given[0].shape[:3] for o in given):
-        raise RuntimeError("%s: the outputs differ in shape: %s" % (who, [tuple(o.shape) for o in given]))
-    if (torch.is_tensor(coef) and coef.is_cuda) or (torch.is_tensor(lut) and lut.is_cuda):
+    if torch.is_tensor(lut) and lut.is_cuda:
         raise RuntimeError("%s: the tables are checked on the host: pass host tables or an ops.RotateTable / ops.TransferTable" % who)
-    table = coef if isinstance(coef, RotateTable) else RotateTable(coef, pix.device)
+    x, table, (k, h, w, n0, n, a, u, t) = _rotate_args(who, pix, n0, coef, t, sampling, (
+        ("rgb", rgb, torch.uint8), ("opacity", opacity, torch.uint8), ("depth", depth, torch.int16)))
     transfer = lut if isinstance(lut, TransferTable) else TransferTable(lut, pix.device)
-    if any(o.device != pix.device for o in given + [table.dev, transfer.dev]):
+    if transfer.dev.device != pix.device:
         raise RuntimeError("%s: pix, the two tables and the outputs must live on one device" % who)
-    a, n, u = given[0].shape[:3]
-    x = pix.contiguous()
-    k, h, w = x.shape
-    n0, t = int(n0), int(t)
-    if a != table.count:
-        raise RuntimeError("%s: %d planes for a table of %d angles" % (who, a, table.count))
-    if k < 1 or n0 < 0 or n0 + k > n:
-        raise RuntimeError("%s: chunk of %d slices at slice %d does not lie in the volume of %d" % (who, k, n0, n))
-    if not (1 <= min(h, w, u, t) and max(h, w, u, t) <= ROTATE_MAX_DIM):
-        raise RuntimeError("%s: H, W, U, T in 1 .. %d expected, got %d %d %d %d" % (who, ROTATE_MAX_DIM, h, w, u, t))
     _lib.check(lib.ctg_project_render(_p(x), k, h, w, n0, n, _p(table.dev), a, u, t, _p(transfer.dev), _ROTATE_SAMPLING_CODES[sampling],
                                       stop, surface, bg[0], bg[1], bg[2], float(wc), float(ww), int(bool(hu)), _p(rgb), _p(opacity),
                                       _p(depth), _stream()), "ctg_project_render")
@@ -2072,9 +2045,7 @@ def reformat_lines(vol, lines, u, t, mode, fill=None, wc=50.0, ww=400.0, hu=Fals
     n, h, w = x.shape
     if not (1 <= min(n, h, w) and max(n, h, w) <= REFORMAT_MAX_DIM):
         raise RuntimeError("%s: N, H, W in 1 .. %d expected, got %d %d %d" % (who, REFORMAT_MAX_DIM, n, h, w))
-    fill = (-1024 if hu else 0) if fill is None else int(fill)
-    if not -32768 <= fill <= 32767:
-        raise RuntimeError("%s: fill %d is not an int16 value" % (who, fill))
+    fill = _fill_value(who, fill, hu)
     with torch.cuda.device(vol.device):
         values = torch.empty(table.shape + (u,), dtype=torch.int16, device=vol.device) if want_values else None
         level = torch.empty(table.shape + (u,), dtype=torch.uint8, device=vol.device) if want_level else None
@@ -2090,29 +2061,12 @@ def project_accumulate_depth(pix, n0, thick, mode, axial=None, coronal=None, sag
     (sagittal) of the first voxel along the axis that attains the value; no axis may exceed 32767 voxels.  `project_finish_depth`
     unpacks an accumulator."""
     lib = _lib.load()
-    who = "project_accumulate_depth"
-    if not torch.is_tensor(pix) or not pix.is_cuda:
-        raise RuntimeError("%s: CPU tensors are not supported (no CPU fallback)" % who)
-    if pix.dtype != torch.int16 or pix.dim() != 3:
-        raise RuntimeError("%s: pix must be int16 (K, H, W), got %s %s" % (who, pix.dtype, tuple(pix.shape)))
-    code = _depth_mode(mode, who)
-    n0, thick = int(n0), int(thick)
-    if n0 < 0 or thick < 1:
-        raise RuntimeError("%s: n0 >= 0 and thick >= 1 expected, got n0=%d thick=%d" % (who, n0, thick))
-    if axial is None and coronal is None and sagittal is None:
-        raise RuntimeError("%s: at least one accumulator expected" % who)
-    x = pix.contiguous()
-    k, h, w = x.shape
-    if k < 1:
+    code = _depth_mode(mode, "project_accumulate_depth")
+    args = _accumulate_args("project_accumulate_depth", pix, n0, thick, axial, coronal, sagittal, longest=32767)
+    if args is None:
         return
-    if max(n0 + k, h, w) > 32767:
-        raise RuntimeError("%s: a depth is an int16: no axis above %d voxels, got n0 + K = %d, H = %d, W = %d"
-                           % (who, 32767, n0 + k, h, w))
-    _project_acc(axial, ((n0 + k - 1) // thick + 1, h, w), "axial")
-    _project_acc(coronal, (n0 + k, w), "coronal")
-    _project_acc(sagittal, (n0 + k, h), "sagittal")
-    if any(t is not None and t.device != x.device for t in (axial, coronal, sagittal)):
-        raise RuntimeError("%s: pix and the accumulators must live on one device" % who)
+    x, n0, thick = args
+    k, h, w = x.shape
     _lib.check(lib.ctg_project_accumulate_depth(_p(x), k, h, w, n0, thick, code, _p(axial), _p(coronal), _p(sagittal), _stream()),
                "ctg_project_accumulate_depth")
 
@@ -2128,17 +2082,12 @@ def project_finish_depth(acc, mode, thick, extent, cue=0, wc=50.0, ww=400.0, hu=
     level are what `project_finish` gives the plain accumulator."""
     lib = _lib.load()
     who = "project_finish_depth"
-    if not torch.is_tensor(acc) or not acc.is_cuda:
-        raise RuntimeError("%s: CPU tensors are not supported (no CPU fallback)" % who)
-    if acc.dtype != torch.int32 or acc.dim() not in (2, 3) or not acc.is_contiguous():
-        raise RuntimeError("%s: a contiguous int32 accumulator of 2 or 3 dimensions expected, got %s %s"
-                           % (who, acc.dtype, tuple(acc.shape)))
+    planes = _finish_acc(who, acc)
     if not (want_values or want_level or want_depth or want_cued):
         raise RuntimeError("%s: at least one of values, level, depth, cued expected" % who)
     code = _depth_mode(mode, who)
     cue = _depth_cue(cue, who)
     thick, extent = int(thick), int(extent)
-    planes = acc.shape[0] if acc.dim() == 3 else 1
     if thick < 1 or not 1 <= extent <= 32767 or (planes - 1) * thick >= extent:
         raise RuntimeError("%s: thick >= 1, 1 <= extent <= %d and (planes - 1) thick < extent expected, got thick=%d extent=%d "
                            "planes=%d" % (who, 32767, thick, extent, planes))

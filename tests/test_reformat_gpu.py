@@ -315,7 +315,7 @@ def test_series_translator_reformat(ops, monkeypatch):
         none = none_tr(vol)
         # with reformat=None the result and the launches are what they were, and nothing is kept
         assert sorted(none) == sorted(plain) == ["level", "pix", "rotation"] and launched == before and "ctg_reformat_lines" not in before
-        assert none_tr._reformatter is None and none_tr._ref_host is None and plain_tr._reformatter is None
+        assert "reformat" not in none_tr._views and "reformat" not in none_tr._view_host and "reformat" not in plain_tr._views
         tables = tables_for()
         tr = SeriesTranslator(g, batch=2, rotate=3, reformat=tables, reformat_options={"mode": "mean", "sampling": "nearest"})
         launched.clear()

@@ -323,7 +323,7 @@ def test_series_translator_render(ops, monkeypatch):
         monkeypatch.setattr(ops, "project_render", (lambda f: lambda *a, **k: (calls.append("project_render"), f(*a, **k))[1])(ops.project_render))
         plain_tr = SeriesTranslator(g, batch=2, rotate=3)
         plain = plain_tr(vol)
-        assert "render" not in plain and not calls and plain_tr._renderer is None and plain_tr._ren_host is None
+        assert "render" not in plain and not calls and "render" not in plain_tr._views and "render" not in plain_tr._view_host
         options = {"transfer": TABLES["mixed"], "wc": 1000.0, "ww": 4200.0, "background": BG}      # stored values 0 .. 4095
         tr = SeriesTranslator(g, batch=2, rotate=3, render=3, render_options=options)
         for out in (tr(vol), tr(vol)):      # the second call reuses the renderer and the page-locked planes

@@ -338,7 +338,7 @@ def test_series_translator_bilinear_rotation(ops):
         small = synthetic_hu(3, 48, 40, seed=8)
         out = tr(small)
         ds = rotate_np.detector(48, 40)
-        assert (tr._rotator.n, tr._rotator.sampling, tr._rotator.steps) == (3, "bilinear", 2 * ds)
+        assert (tr._views["rotation"].n, tr._views["rotation"].sampling, tr._views["rotation"].steps) == (3, "bilinear", 2 * ds)
         want = rotate_lerp_np.rotate(out["pix"], table(48, 40, ds, ds, 2, angles), ds, 2 * ds, "max")
         assert np.array_equal(out["rotation"]["values"], want)
         # the defaults: today's rotation, nearest sampling at unit steps

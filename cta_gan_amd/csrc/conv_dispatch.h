@@ -35,6 +35,20 @@ static inline bool taps_3x3(const int* taps, bool flipped) {
     }
     return true;
 }
+// The halo kernel's compile-time tap walk (conv_halo.h, walk3x3) serves a FULL 3x3 window whose tap t uses weight slice t and
+// sits at window position (t / 3, t % 3) -- 1: row-major, the forward convs -- or at (2 - t / 3, 2 - t % 3) -- 2: that order
+// flipped, the backward-data launches.  0: any other tap list (fewer rows, another order, other weight slices): the generic loop.
+static inline int taps_3x3_walk(const int* taps, int ntaps, int kh, int kw, int dy0, int dx0) {
+    if (ntaps != 9 || kh != 3 || kw != 3) return 0;
+    bool fwd = true, flip = true;
+    for (int t = 0; t < 9; ++t) {
+        if ((taps[t] >> 16) != t) return 0;
+        const int ky = tap_dy(taps[t]) - dy0, kx = tap_dx(taps[t]) - dx0;
+        fwd = fwd && ky == t / 3 && kx == t % 3;
+        flip = flip && ky == 2 - t / 3 && kx == 2 - t % 3;
+    }
+    return fwd ? 1 : (flip ? 2 : 0);
+}
 // Conv2d(k=3, s=2, p=1) as ctg_conv_igemm gets it: tap t = (ky, kx) reads input (2 oy + ky - 1, 2 ox + kx - 1) with weight t
 static inline bool taps_conv3x3_s2(const int* taps) {
     for (int t = 0; t < 9; ++t)

@@ -34,6 +34,9 @@ struct ConvArgs {
     int taps[64];      // (dy+64) | (dx+64) << 8 | widx << 16
     // halo kernel only: window extent and origin of the tap rectangle
     int kh, kw, dy0, dx0;
+    // halo kernel, KWC == 3 instantiations: taps_3x3_walk() of this launch (set by launch_halo_cfg, whatever the caller left here):
+    // 1 / 2 = the compile-time tap walk in row-major / flipped order, 0 = the generic tap loop
+    int walk3;
     // halo kernel only: when non-null, per-(sample, spatial tile, channel) partial sums (sum, sum of squares) of the
     // fp32 accumulators, [B][tiles][Cout][2]: InstanceNorm statistics without re-reading the output
     float* stats;
@@ -307,15 +310,8 @@ void conv_halo_kernel(const ConvArgs a) {
     // weight fragment of MFMA tile nt: rows (wn TN + nt) 16 + (lane & 15) of the tap's [BN][KCH] tile; its swizzle (swz<>:
     // row & 7 resp. (row >> 1) & 3) is invariant under + 16 rows, so it only depends on lane & 15: one loop-invariant offset
     const int wo0 = (((wn * TN) * 16 + (lane & 15)) * KCH + swz<KCH>(lane & 15, lane >> 4)) * 16;
-    auto compute = [&](int abuf, int bbuf, int tw) __attribute__((always_inline)) {
-        const char* pa = sA + abuf * HPC64 * 16;
-        const char* pb = sB + bbuf * B_CH * 16;
-        const int ky = (tw & 0xff) - 64 - dy0, kx = ((tw >> 8) & 0xff) - 64 - dx0;
-        // the halo is swizzled by its column, so a pixel fragment's address is a per-lane column offset (one per k-step
-        // of the tap) plus wave-uniform row offsets: one vector add per fragment read instead of a swizzle computation
-        const int hx = kx + (lane & 15);
-        const char* prow = pa + (ky + wm * TM) * (HPW * KCH * 16);
-        const int xo0 = (hx * KCH + swz<KCH>(hx, lane >> 4)) * 16;
+    // one tap step of the wave: pixel fragments at prow + xo0 (+ a tile row per fragment), weight fragments at pb + wo0
+    auto mma_tap = [&](const char* prow, int xo0, const char* pb) __attribute__((always_inline)) {
         if constexpr (PK) {
             // chunks 0-3 of a row are the hi halves (x_hi / w_hi), 4-7 the lo halves (offset ^ 64): hi.w_hi, hi.w_lo, lo.w_hi
             u32x4 fa[TM], fb[TN], fl[TN];
@@ -375,6 +371,15 @@ void conv_halo_kernel(const ConvArgs a) {
                 }
         }
     };
+    auto compute = [&](int abuf, int bbuf, int tw) __attribute__((always_inline)) {
+        const char* pa = sA + abuf * HPC64 * 16;
+        const char* pb = sB + bbuf * B_CH * 16;
+        const int ky = (tw & 0xff) - 64 - dy0, kx = ((tw >> 8) & 0xff) - 64 - dx0;
+        // the halo is swizzled by its column, so a pixel fragment's address is a per-lane column offset (one per k-step
+        // of the tap) plus wave-uniform row offsets: one vector add per fragment read instead of a swizzle computation
+        const int hx = kx + (lane & 15);
+        mma_tap(pa + (ky + wm * TM) * (HPW * KCH * 16), (hx * KCH + swz<KCH>(hx, lane >> 4)) * 16, pb);
+    };
 
     // ragged bottom tiles (e.g. the 130-row padded grid of a backward-data pass): waves whose pixel rows all lie
     // below the grid skip the MFMA work (they still take part in loads and barriers)
@@ -411,6 +416,89 @@ void conv_halo_kernel(const ConvArgs a) {
     }
     const int nslices = S2D ? nchunk * a.ncls : nchunk;
     int c = 0, t = 0;
+    // ---- full 3x3 windows (a.walk3, host-checked: taps_3x3_walk): the nine tap steps of a channel slice are unrolled, so a
+    // step's window position, tile-row offset and weight buffer are instruction immediates or values set up once per tile, the
+    // next weight tile is one running pointer, and no tap word is read or decoded.  The generic loop below spends 118
+    // instructions per step around its 32 MFMAs -- a scalar-memory round trip for the next tap word and ~25 instructions of
+    // bit fields and multiplies between the barrier and the weight DMA that has exactly this step to land -- in a kernel that
+    // is issue- and wait-bound; a step here is 68 (LAB_NOTES section 26).  Same steps, same fragments, same order of the
+    // MFMAs of an accumulator: the accumulators get the same bits.
+    // Not the split-pair instantiations (PK): three fragment sets per step fill the 128 registers, and the walk's per-tile offsets
+    // (3 window columns, their ^ 64 twins) went to scratch there; they keep the generic loop.
+    constexpr bool WALK = KWC == 3 && ABUF == 1 && !MC && !S2D && !PK && sizeof(T) == 2;
+    bool walked = false;
+    if constexpr (WALK) {
+        static_assert(KCH == 4 || KCH == 8, "walk3x3: the row pitch keeps bit 6 of a fragment offset free");
+        constexpr int ROWP = (HALO_W + 2) * KCH * 16;                              // bytes of a halo row
+        constexpr int HPC64_C = ((TH + 2) * (HALO_W + 2) * KCH + 63) & ~63;        // = HPC64 of a 3-row window
+        constexpr int WT = B_CH * 16;                                              // bytes of a weight tile
+        auto walk3x3 = [&](auto FL) __attribute__((always_inline)) {
+            constexpr bool FLIP = decltype(FL)::value;
+            // per-lane fragment offsets of the three window columns, the wave's first tile row included
+            int xa[3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const int hx = k + (lane & 15);
+                xa[k] = (hx * KCH + swz<KCH>(hx, lane >> 4)) * 16 + wm * TM * ROWP;
+            }
+            // halo refill: only the last piece can lie partly beyond the halo, and which waves it still concerns never changes
+            const bool tail_mine = NTH * (H_PRE - 1) + 64 * wave < HPC64_C;
+            const T* zsrc = (const T*)g_zero_chunk;
+            asm volatile("" : "+s"(zsrc));                                        // formed once, not once per piece
+            const char* sBc = smem + HPC64_C * 16;
+            const char* wp = reinterpret_cast<const char*>(W);                     // weight tile of the step in flight
+            const long wstep = (long)w_tap_stride * (long)sizeof(T);
+            const long wwrap = (long)BKE * (long)sizeof(T) - 8 * wstep;            // tap 8 of a slice -> tap 0 of the next
+            int wb0 = 0, wb1 = WT;                                                 // buffers of the slice's even / odd taps
+            unsigned boffb[B_IT];                                                  // a lane's byte offsets inside a weight tile's slab
+#pragma unroll
+            for (int it = 0; it < B_IT; ++it) boffb[it] = (unsigned)boff[it] * (unsigned)sizeof(T);
+            for (int cc = 0; cc < nchunk; ++cc) {
+                const bool more = cc + 1 < nchunk;
+#pragma unroll
+                for (int tt = 0; tt < 9; ++tt) {
+                    // the next weight tile first: it has this step to land
+                    if (tt < 8 || more) {
+                        wp += tt < 8 ? wstep : wwrap;
+                        if (b_active) {
+                            const int dst = ((tt + 1) & 1) ? wb1 : wb0;
+#pragma unroll
+                            for (int it = 0; it < B_IT; ++it)
+                                if (B_CH % NTH == 0 || NTH * it + 64 * wave < B_CH) {
+                                    // (redefined in place: the 32-bit lane offset stays the load's own operand beside the scalar
+                                    // base; hoisted out of the loop it became a 64-bit register pair and an add per load)
+                                    asm volatile("" : "+v"(boffb[it]));
+                                    __builtin_amdgcn_global_load_lds((gptr_t)(wp + boffb[it]),
+                                                                     (lptr_t)(sBc + dst + (NTH * it + 64 * wave) * 16), 16, 0, 0);
+                                }
+                        }
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (wave_rows_valid) {
+                        const int ky = FLIP ? 2 - tt / 3 : tt / 3, kx = FLIP ? 2 - tt % 3 : tt % 3;      // constants of the unrolled step
+                        mma_tap(smem + ky * ROWP, xa[kx], sBc + ((tt & 1) ? wb1 : wb0));
+                    }
+                    __syncthreads();
+                }
+                if (more) {
+                    // every wave is past its last read of slice cc (barrier above): refill the halo for cc + 1
+                    int kc0 = xslice(cc + 1);
+                    asm volatile("" : "+s"(kc0));      // (no running copy of every hoff[j] + kc0 across the loop: six registers)
+#pragma unroll
+                    for (int j = 0; j < H_PRE; ++j)
+                        if (NTH * (j + 1) <= HPC64_C || tail_mine) {
+                            const T* src = hoff[j] >= 0 ? X + (hoff[j] + kc0) : zsrc;
+                            __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(smem + (NTH * j + 64 * wave) * 16), 16, 0, 0);
+                        }
+                    __syncthreads();
+                    const int w = wb0; wb0 = wb1; wb1 = w;                          // nine taps: the parity flips per slice
+                }
+            }
+        };
+        if (a.walk3 == 1) { walk3x3(std::false_type{}); walked = true; }
+        else if (a.walk3 == 2) { walk3x3(std::true_type{}); walked = true; }
+    }
+    if (!walked)
     for (int s = 0; s < S; ++s) {
         int tn = t + 1, cn = c;
         if (tn == ntaps) { tn = 0; cn = c + 1; }
@@ -1032,7 +1120,9 @@ static int launch_halo_cfg(const ConvArgs& a, hipStream_t st, int* tiles_out = n
         if ((long)tiles * ntn * share > (long)occ_dev[dev] * ctg_cu_count()) return 2;      // not served: nothing launched
     }
     dim3 grid(tiles * ntn, a.B);
-    hipLaunchKernelGGL((conv_halo_kernel<T, OutT, BN, WM, WN, KCH, ABUF, TH, FUSE, KWC, MC, PK, S2D, NIE>), grid, dim3(NTH), smem, st, a);
+    ConvArgs b = a;
+    b.walk3 = (KWC == 3 && ABUF == 1 && !MC && !S2D && !PK) ? taps_3x3_walk(a.taps, a.ntaps, a.kh, a.kw, a.dy0, a.dx0) : 0;
+    hipLaunchKernelGGL((conv_halo_kernel<T, OutT, BN, WM, WN, KCH, ABUF, TH, FUSE, KWC, MC, PK, S2D, NIE>), grid, dim3(NTH), smem, st, b);
     return ctg_launch_status();
 }
 

@@ -92,6 +92,7 @@ SIGNATURES = {
     "ctg_project_finish_depth": "piliiiiffippppp",
     "ctg_project_render": "piiiiipiiipiiiiiiffipppp",
     "ctg_reformat_lines": "piiipiiiiiiffippp",
+    "ctg_render_lines": "piiipiiipiiiiiiffipiiipppp",
     "ctg_window_pairs": "ppppilipp",
     "ctg_maxpool3s2_fwd": "pipiiiiip",
     "ctg_lpips_layer": "pipiliippp",

@@ -49,14 +49,20 @@ stays on the device and one kernel samples it along lines given by a table of ni
 (`ops.reformat_lines`): nearest or trilinear sampling in exact integers, max / min / mean along rays of T steps, anisotropic
 voxels inside the table (`aspect`), one launch per table after the last chunk.
 
-The view protocol.  The five display classes above are views (`_SeriesView` holds what they share), and `SeriesTranslator` and
+Shaded rendering along lines (`VolumeRenderer`, `render_lines_volume`, `SeriesTranslator(render3d=...)`): the volume-rendered view on
+the same line tables -- rays in any direction, trilinear sampling, anisotropic voxels inside the geometry -- with every sample's
+colour shaded by the local gradient (`ops.render_lines`: the compositing chain of `ops.project_render`, central differences at the
+sample's voxel, a light per line from `headlight` or one fixed vector, all in exact integers).  It keeps the volume on the device
+as the reformats do (`_ResidentVolume` holds what the two share); `line_voxel` maps a depth back to its voxel.
+
+The view protocol.  The six display classes above are views (`_SeriesView` holds what they share), and `SeriesTranslator` and
 the `*_volume` functions drive every one of them the same way.  A view is made for one volume shape and has `.n`, `.h`, `.w` and
 `.device`; `update(pix_chunk, n0)` takes a device chunk of slices n0 .. n0+K-1 on the current stream, in any order, every slice
 once; `result()` returns a tree on the device -- a dict of tensors, Nones and nested dicts -- once they have all arrived;
 `reset()` makes the view ready for the next volume of the same shape.  A view whose result has one plane per view angle keeps the
 angles as the host list `.angles`.  Where the classes differ: `SeriesProjector.update` forwards an empty chunk to ops (the others
-return early) and its `result` takes the window (the others take it at construction); `VolumeReformatter` also bounds the sides
-by `ops.REFORMAT_MAX_DIM`, checks the chunk's dtype and resolves device=None at the first chunk only.
+return early) and its `result` takes the window (the others take it at construction); `VolumeReformatter` and `VolumeRenderer` also
+bound the sides by `ops.REFORMAT_MAX_DIM`, check the chunk's dtype and resolve device=None at the first chunk only.
 """
 from __future__ import annotations
 
@@ -168,7 +174,7 @@ def _view_of_volume(who, volume, batch, device, make, result=lambda view: view.r
 
 
 class _SeriesView:
-    """What the five views share: the volume check, the device check, the check that a chunk lies in the volume, and a `reset()`
+    """What the six views share: the volume check, the device check, the check that a chunk lies in the volume, and a `reset()`
     that does nothing.  A view takes `update(pix_chunk, n0)` for every chunk and gives `result()` once they have all arrived."""
 
     def _volume(self, n, h, w):
@@ -574,15 +580,7 @@ class SeriesRenderer(_SeriesView):
         self.angles = [float(a) for a in angles]
         if not 1 <= len(self.angles) <= ops.ROTATE_MAX_DIM:
             raise ValueError("SeriesRenderer: 1 .. %d view angles expected, got %d" % (ops.ROTATE_MAX_DIM, len(self.angles)))
-        self.background = tuple(background)
-        if len(self.background) != 3 or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v <= 255
-                                            for v in self.background):
-            raise ValueError("SeriesRenderer: background: three integers in 0 .. 255 expected, got %r" % (background,))
-        self.background = tuple(int(v) for v in self.background)
-        for name, v, lo in (("stop", stop, 0), ("surface", surface, 1)):
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= lo + ops.RENDER_OPAQUE - 1:
-                raise ValueError("SeriesRenderer: %s: an integer in %d .. %d expected, got %r" % (name, lo, lo + ops.RENDER_OPAQUE - 1, v))
-        self.stop, self.surface = int(stop), int(surface)
+        self.background, self.stop, self.surface = _check_compositing("SeriesRenderer", background, stop, surface)
         d = default_detector(self.h, self.w)
         self.u, self.t = (d, d) if detector is None else _pair(detector)
         self.steps = self.t * self.oversample
@@ -830,7 +828,62 @@ def curved_lines(n, h, w, centreline, angles=(0.0,), cols=65, depth=1, pitch=1.0
     return LineSet(np.stack(tables), depth * s, cols)
 
 
-class VolumeReformatter(_SeriesView):
+class _ResidentVolume(_SeriesView):
+    """What the views on the whole volume share (`VolumeReformatter`, `VolumeRenderer`): the int16 volume kept on the device, the
+    copy-in of a chunk in any order, the count of how often every slice has arrived and the refusal of a result unless that is
+    exactly once, the device resolved at the first chunk only, and `reset()`.  A subclass calls `_resident` from its constructor,
+    uploads its tables in `_upload` (run once, at the first chunk, on `self.device`) and `_whole` before it launches."""
+
+    def _sides(self, who, n, h, w):
+        self._volume(n, h, w)
+        if max(self.n, self.h, self.w) > ops.REFORMAT_MAX_DIM:      # the line tables address the sides in 16.16 fixed point
+            raise ValueError("%s: n, h, w in 1 .. %d expected, got %d %d %d" % (who, ops.REFORMAT_MAX_DIM, self.n, self.h, self.w))
+
+    def _resident(self, device):
+        self._seen = np.zeros(self.n, dtype=np.int64)
+        self.device = None if device is None else self._gpu(device)      # None: the current device at the first chunk
+        self.volume = None      # on the device from the first chunk on
+
+    def _line_tables(self, who, tables, cols):
+        """`tables` of the constructor -> {name: (host table, U, T)}, checked on the host."""
+        if not isinstance(tables, dict) or not tables:
+            raise ValueError("%s: tables: a dict {name: (table, T)} with at least one entry expected" % who)
+        lines = {}
+        for name, entry in tables.items():
+            entry = entry(self.n, self.h, self.w) if callable(entry) else entry
+            u = getattr(entry, "cols", cols)
+            if not isinstance(entry, tuple) or len(entry) != 2 or u is None:
+                raise ValueError("%s: table %r: a LineSet, or a pair (table, T) together with cols, expected" % (who, name))
+            lines[name] = (ops.line_table_host(entry[0], u, entry[1]), int(u), int(entry[1]))
+        return lines
+
+    def _upload(self):
+        """The view's tables onto `self.device`: once, at the first chunk."""
+
+    def reset(self):
+        """Forget which slices have arrived (the volume's memory is kept and overwritten)."""
+        self._seen[:] = 0
+
+    def update(self, pix_chunk, n0):
+        k, n0 = self._chunk(pix_chunk, n0, dtype=torch.int16), int(n0)      # (the copy below would convert another dtype)
+        if k < 1:
+            return
+        if self.volume is None:
+            if self.device is None:
+                self.device = self._gpu(None)
+            self._upload()
+            self.volume = torch.empty((self.n, self.h, self.w), dtype=torch.int16, device=self.device)
+        self.volume[n0:n0 + k].copy_(pix_chunk, non_blocking=True)
+        self._seen[n0:n0 + k] += 1
+
+    def _whole(self):
+        if (self._seen != 1).any():
+            missing, twice = int((self._seen == 0).sum()), int((self._seen > 1).sum())
+            raise RuntimeError("%s: every slice must have arrived exactly once: %d of %d missing, %d more than once"
+                               % (type(self).__name__, missing, self.n, twice))
+
+
+class VolumeReformatter(_ResidentVolume):
     """Reformats of an int16 volume [n, h, w] that arrives in chunks and stays on the device: oblique planes, tumbling views,
     curved reformats -- every display whose rows cross slices (`ops.reformat_lines`, csrc/reformat.hip).  tables: {name: a
     `LineSet`, a pair (table [..., 9], T) with `cols` given here, or a callable (n, h, w) -> either}; mode "max" / "min" / "mean"
@@ -848,48 +901,21 @@ class VolumeReformatter(_SeriesView):
             raise ValueError("%s: mode %r is not one of %s" % (who, mode, PROJECTIONS))
         if sampling not in REFORMAT_SAMPLINGS:
             raise ValueError("%s: sampling %r is not one of %s" % (who, sampling, REFORMAT_SAMPLINGS))
-        self._volume(n, h, w)
-        if max(self.n, self.h, self.w) > ops.REFORMAT_MAX_DIM:      # the line tables address the sides in 16.16 fixed point
-            raise ValueError("%s: n, h, w in 1 .. %d expected, got %d %d %d" % (who, ops.REFORMAT_MAX_DIM, self.n, self.h, self.w))
-        if not isinstance(tables, dict) or not tables:
-            raise ValueError("%s: tables: a dict {name: (table, T)} with at least one entry expected" % who)
+        self._sides(who, n, h, w)
+        self.lines = self._line_tables(who, tables, cols)      # name -> (host table, U, T), checked
         self.mode, self.sampling = mode, sampling
         self.hu, self.window, self.want_level = bool(hu), (float(wc), float(ww)), bool(level)
         self.fill = (-1024 if self.hu else 0) if fill is None else int(fill)
-        self.lines = {}      # name -> (host table, U, T), checked
-        for name, entry in tables.items():
-            entry = entry(self.n, self.h, self.w) if callable(entry) else entry
-            u = getattr(entry, "cols", cols)
-            if not isinstance(entry, tuple) or len(entry) != 2 or u is None:
-                raise ValueError("%s: table %r: a LineSet, or a pair (table, T) together with cols, expected" % (who, name))
-            self.lines[name] = (ops.line_table_host(entry[0], u, entry[1]), int(u), int(entry[1]))
-        self._seen = np.zeros(self.n, dtype=np.int64)
         per = 2 + (1 if self.want_level else 0)
         self.nbytes = 2 * self.n * self.h * self.w + sum(t.nbytes + per * (t.size // 9) * u for t, u, _ in self.lines.values())
-        self.device = None if device is None else self._gpu(device)      # None: the current device at the first chunk
-        self.tables = self.volume = None      # on the device from the first chunk on
+        self._resident(device)
+        self.tables = None      # on the device from the first chunk on
 
-    def reset(self):
-        """Forget which slices have arrived (the volume's memory is kept and overwritten)."""
-        self._seen[:] = 0
-
-    def update(self, pix_chunk, n0):
-        k, n0 = self._chunk(pix_chunk, n0, dtype=torch.int16), int(n0)      # (the copy below would convert another dtype)
-        if k < 1:
-            return
-        if self.volume is None:
-            if self.device is None:
-                self.device = self._gpu(None)
-            self.tables = {name: ops.LineTable(t, u, steps, self.device) for name, (t, u, steps) in self.lines.items()}
-            self.volume = torch.empty((self.n, self.h, self.w), dtype=torch.int16, device=self.device)
-        self.volume[n0:n0 + k].copy_(pix_chunk, non_blocking=True)
-        self._seen[n0:n0 + k] += 1
+    def _upload(self):
+        self.tables = {name: ops.LineTable(t, u, steps, self.device) for name, (t, u, steps) in self.lines.items()}
 
     def result(self):
-        if (self._seen != 1).any():
-            missing, twice = int((self._seen == 0).sum()), int((self._seen > 1).sum())
-            raise RuntimeError("VolumeReformatter: every slice must have arrived exactly once: %d of %d missing, %d more than once"
-                               % (missing, self.n, twice))
+        self._whole()
         out = {}
         for name, table in self.tables.items():
             values, level = ops.reformat_lines(self.volume, table, table.u, table.t, self.mode, fill=self.fill, wc=self.window[0],
@@ -909,6 +935,158 @@ def reformat_volume(volume, tables, mode="max", sampling="trilinear", fill=None,
 
     # host chunks go to `update` as they are: it copies them into the resident volume, the only time they cross PCIe
     return _view_of_volume("reformat_volume", volume, batch, device, make, upload=False)
+
+
+def _ray_table(who, lines):
+    """A `LineSet` / pair (table, T) or a bare table -> (int64 table [..., 9], T or None)."""
+    steps = None
+    if isinstance(lines, tuple):
+        if len(lines) != 2:
+            raise ValueError("%s: a LineSet, a pair (table, T) or a table [..., 9] expected" % who)
+        lines, steps = lines[0], int(lines[1])
+    table = np.asarray(lines.cpu() if torch.is_tensor(lines) else lines)
+    if table.ndim < 1 or table.shape[-1] != 9 or table.dtype.kind not in "iu":
+        raise ValueError("%s: a line table of [..., 9] integers expected, got %s %s" % (who, table.dtype, tuple(table.shape)))
+    return table.astype(np.int64), steps
+
+
+def headlight(lines, aspect=1.0):
+    """The light that shines along the rays of a line table, for `ops.render_lines` / `ops.LightTable`: int64 [..., 3], for every
+    line the unit vector of its ray -- (xk, yk, zk aspect), the step of the table in pixel units -- times 4096, rounded by
+    floor(v + 0.5).  The length of the step drops out, so every oversample of one view gets the same light (within the rounding
+    of the table's own coefficients).  lines: a `LineSet`, a pair (table, T) or a table [..., 9]; a table of T = 1 has no ray, and
+    a line whose step is (0, 0, 0) no direction: both are refused.  The shading is two-sided, so the sign does not matter."""
+    who = "headlight"
+    table, steps = _ray_table(who, lines)
+    aspect = float(aspect)
+    if not (aspect > 0 and math.isfinite(aspect)):
+        raise ValueError("%s: aspect: a positive ratio expected, got %r" % (who, aspect))
+    if steps is not None and steps < 2:
+        raise ValueError("%s: a table of T = %d has no ray: give the light as a vector" % (who, steps))
+    ray = table[..., 2::3].astype(np.float64) * np.array([1.0, 1.0, aspect])
+    length = np.sqrt((ray ** 2).sum(axis=-1, keepdims=True))
+    if (length <= 0).any():
+        raise ValueError("%s: %d of %d lines have no ray direction" % (who, int((length <= 0).sum()), length.size))
+    return np.floor(ray / length * float(ops.LIGHT_UNIT) + 0.5).astype(np.int64)
+
+
+def line_voxel(row, i, k):
+    """(z, y, x): the voxel that sample (i, k) of a line falls in, by the kernel's nearest rule x = (x0 + xu i + xk k) >> 16
+    (y, z likewise; arithmetic shift) for the line's row (x0, xu, xk, y0, yu, yk, z0, zu, zk) -- the `ray_voxel` of a line table.
+    With k = the "depth" of sample i of a rendered line it is the voxel at which the ray's opacity reached `surface` (with
+    trilinear sampling, the voxel the sample counts and is shaded by).  A pure host function; i and k may be integers or integer
+    arrays, a ray that never got there (depth -1) has no voxel."""
+    c = [int(v) for v in row]
+    if len(c) != 9:
+        raise ValueError("line_voxel: a row of nine integers expected, got %d" % len(c))
+    i, k = np.asarray(i, dtype=np.int64), np.asarray(k, dtype=np.int64)
+    x, y, z = ((c[3 * a] + c[3 * a + 1] * i + c[3 * a + 2] * k) >> 16 for a in range(3))
+    return (int(z), int(y), int(x)) if x.ndim == 0 else (z, y, x)
+
+
+SHADING_OPTIONS = ("ambient", "gmin", "light")
+SHADING_DEFAULTS = {"ambient": 0.3, "gmin": 40.0, "light": "head"}      # a first guess, like the presets: not tuned (DESIGN.md)
+
+
+def _check_compositing(who, background, stop, surface):
+    """-> ((r, g, b), stop, surface) of a compositing view, checked."""
+    bg = tuple(background)
+    if len(bg) != 3 or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v <= 255 for v in bg):
+        raise ValueError("%s: background: three integers in 0 .. 255 expected, got %r" % (who, background))
+    for name, v, lo in (("stop", stop, 0), ("surface", surface, 1)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= lo + ops.RENDER_OPAQUE - 1:
+            raise ValueError("%s: %s: an integer in %d .. %d expected, got %r" % (who, name, lo, lo + ops.RENDER_OPAQUE - 1, v))
+    return tuple(int(v) for v in bg), int(stop), int(surface)
+
+
+class VolumeRenderer(_ResidentVolume):
+    """Shaded volume-rendered views of an int16 volume [n, h, w] that arrives in chunks and stays on the device, along rays in any
+    direction (`ops.render_lines`, csrc/render_lines.hip): the compositing of `SeriesRenderer` on the line tables of
+    `VolumeReformatter` -- tumbling and oblique views, trilinear sampling, anisotropic voxels inside the geometry -- with every
+    sample's colour shaded by the local gradient.  tables: {name: a `LineSet`, a pair (table, T) with `cols` given here, or a
+    callable (n, h, w) -> either}; transfer, (wc, ww), hu, background, stop, surface and depth as `SeriesRenderer` (a preset name
+    or a point list is made for one step per voxel: for oversampled tables pass `transfer_function(points, oversample)`);
+    sampling "trilinear" or "nearest".  shading: None (flat class colours) or a dict with any of "ambient" (0 .. 1, default 0.3:
+    the share of the colour a wall edge-on to the light keeps), "gmin" (default 40, in stored units per two voxels: a sample
+    whose gradient is shorter keeps its colour, so that noise in soft tissue is not shaded) and "light" ("head", default: along
+    every line's own ray, `headlight`; or one vector (x, y, z) in pixel units for all).  aspect (slice spacing / pixel spacing,
+    the one the tables were made with) scales the gradient's z component, zscale = floor(256 / aspect + 0.5) in 1 .. 4096, and
+    the headlight.  `update(pix_chunk, n0)` copies a chunk in, in any order; `result()` raises unless every slice has arrived
+    exactly once since the last `reset()`, then makes one launch per table -> {name: {"rgb": uint8 [..., U, 3], "opacity": uint8
+    [..., U], "depth": int16 [..., U] or None (-1 where the ray never reaches `surface`; `line_voxel` maps a hit back to the
+    voxel)}} on the device.  `.nbytes`: the device memory held (the volume and the tables) plus that of one result, known before
+    the first chunk.  Exact integer arithmetic on the current stream: equal to numpy bit for bit."""
+
+    def __init__(self, n, h, w, tables, transfer="vessels", wc=300.0, ww=1500.0, hu=False, sampling="trilinear", shading=None,
+                 aspect=1.0, background=(0, 0, 0), stop=128, surface=16384, depth=True, device=None, cols=None):
+        who = "VolumeRenderer"
+        if sampling not in REFORMAT_SAMPLINGS:
+            raise ValueError("%s: sampling %r is not one of %s" % (who, sampling, REFORMAT_SAMPLINGS))
+        self._sides(who, n, h, w)
+        self.lines = self._line_tables(who, tables, cols)      # name -> (host table, U, T), checked
+        self.sampling, self.hu, self.window, self.want_depth = sampling, bool(hu), (float(wc), float(ww)), bool(depth)
+        self.background, self.stop, self.surface = _check_compositing(who, background, stop, surface)
+        self.aspect = float(aspect)
+        if not (self.aspect > 0 and math.isfinite(self.aspect)) or not 1 <= math.floor(256.0 / self.aspect + 0.5) <= ops.RENDER_ZSCALE_MAX:
+            raise ValueError("%s: aspect: a ratio with floor(256 / aspect + 0.5) in 1 .. %d expected, got %r"
+                             % (who, ops.RENDER_ZSCALE_MAX, aspect))
+        self.zscale = int(math.floor(256.0 / self.aspect + 0.5))
+        self.lights = None      # name -> host light table [L, 3], or None: no shading
+        self.ambient, self.gmin2 = 256, 1
+        if shading is not None:
+            if not isinstance(shading, dict) or set(shading) - set(SHADING_OPTIONS):
+                raise ValueError("%s: shading %r: None or a dict with any of %s expected" % (who, shading, SHADING_OPTIONS))
+            opts = {**SHADING_DEFAULTS, **shading}
+            ambient, gmin = float(opts["ambient"]), float(opts["gmin"])
+            if not 0.0 <= ambient <= 1.0:
+                raise ValueError("%s: shading: ambient in 0 .. 1 expected, got %r" % (who, opts["ambient"]))
+            if not (gmin >= 0.0 and gmin * gmin <= ops.RENDER_GMIN2_MAX):
+                raise ValueError("%s: shading: gmin in 0 .. %d expected, got %r" % (who, math.isqrt(ops.RENDER_GMIN2_MAX), opts["gmin"]))
+            self.ambient = int(math.floor(ambient * 256.0 + 0.5))
+            self.gmin2 = max(1, int(math.floor(gmin * gmin + 0.5)))
+            self.lights = {}
+            for name, (t, u, steps) in self.lines.items():
+                if isinstance(opts["light"], str) and opts["light"] == "head":
+                    vec = headlight((t, steps), self.aspect)
+                else:
+                    unit = np.floor(_unit(who, "light", opts["light"]) * float(ops.LIGHT_UNIT) + 0.5).astype(np.int64)
+                    vec = np.broadcast_to(unit, t.shape[:-1] + (3,))
+                self.lights[name] = ops.light_table_host(vec, t.size // 9)
+        self.lut_host = np.asarray(_transfer_table(who, transfer, 1))
+        per = 3 + 1 + (2 if self.want_depth else 0)
+        self.nbytes = 2 * self.n * self.h * self.w + 2 * 4 * 256 + sum(
+            t.nbytes + (12 * (t.size // 9) if self.lights is not None else 0) + per * (t.size // 9) * u for t, u, _ in self.lines.values())
+        self._resident(device)
+        self.tables = self.lamps = self.lut = None      # on the device from the first chunk on
+
+    def _upload(self):
+        self.tables = {name: ops.LineTable(t, u, steps, self.device) for name, (t, u, steps) in self.lines.items()}
+        self.lut = ops.TransferTable(self.lut_host, self.device)
+        if self.lights is not None:
+            self.lamps = {name: ops.LightTable(v, len(v), self.device) for name, v in self.lights.items()}
+
+    def result(self):
+        self._whole()
+        out = {}
+        for name, table in self.tables.items():
+            rgb, opacity, depth = ops.render_lines(
+                self.volume, table, table.u, table.t, self.lut, light=None if self.lamps is None else self.lamps[name],
+                zscale=self.zscale, ambient=self.ambient, gmin2=self.gmin2, sampling=self.sampling, background=self.background,
+                stop=self.stop, surface=self.surface, wc=self.window[0], ww=self.window[1], hu=self.hu, want_depth=self.want_depth)
+            out[name] = {"rgb": rgb, "opacity": opacity, "depth": depth}
+        return out
+
+
+def render_lines_volume(volume, tables, batch=64, device=None, **options):
+    """The shaded renderings of a volume that already exists, the twin of `reformat_volume`: int16 [N, H, W], a host array / CPU
+    tensor (chunks of `batch` slices cross PCIe one after another) or a device tensor; tables and the options as
+    `VolumeRenderer`.  Returns what `VolumeRenderer.result` returns, of the input's kind."""
+    def make(n, h, w, dev):      # (the device is resolved here: the chunk loop runs under it)
+        return VolumeRenderer(n, h, w, tables, device=torch.device("cuda", torch.cuda.current_device()) if dev is None else dev,
+                              **options)
+
+    # host chunks go to `update` as they are: it copies them into the resident volume, the only time they cross PCIe
+    return _view_of_volume("render_lines_volume", volume, batch, device, make, upload=False)
 
 
 def subtract_volume(cta, ct_hu, cta_is_hu=False, median=True, floor=0, ct_range=(None, None), wc=150.0, ww=300.0, level=True,
@@ -954,6 +1132,7 @@ def subtract_volume(cta, ct_hu, cta_is_hu=False, median=True, floor=0, ct_range=
 PROJECT_SOURCES = ("cta", "sub")
 REFORMAT_OPTIONS = ("mode", "sampling", "fill", "cols")
 RENDER_OPTIONS = ("transfer", "detector", "wc", "ww", "hu", "sampling", "oversample", "background", "stop", "surface", "depth")
+RENDER3D_OPTIONS = ("transfer", "wc", "ww", "hu", "sampling", "shading", "aspect", "background", "stop", "surface", "depth", "cols")
 
 
 def _angle_list(rotate):
@@ -992,6 +1171,12 @@ class SeriesTranslator:
     in sub_window).  Their rows cross slices, so the source volume is kept on the device (`VolumeReformatter.nbytes`), every table
     is one launch after the last chunk, and the planes are copied back once.  With reformat=None nothing of it is allocated or
     launched.
+    render3d = tables as `reformat` (render3d_options: a dict of `VolumeRenderer` keyword arguments -- transfer, wc, ww, hu (default:
+    that of the source), sampling, shading, aspect, background, stop, surface, depth, cols) adds "render3d": {name: {"rgb": uint8
+    [..., U, 3], "opacity": uint8, "depth": int16 or None}}: the shaded volume-rendered views of the same source
+    (`project_source`) along rays in any direction, one launch per table after the last chunk, copied back once.  It keeps the
+    source volume on the device (`VolumeRenderer.nbytes`); with `reformat` on as well the two hold a copy each (sharing one is not
+    built).  With render3d=None nothing of it is allocated or launched.
 
     size: the side(s) the generator runs at (None: the volume's own); a volume of another size is resized (nearest) on the way
     in and comes back at its own size.  wc / ww: the window of the 8-bit level; hu: pixels minus 1024 (SimpleITK) instead of
@@ -1001,9 +1186,17 @@ class SeriesTranslator:
     def __init__(self, generator, batch=16, size=None, wc=50.0, ww=400.0, hu=False, level=True, device=None, project=None,
                  slab=None, rotate=None, rotate_mode=None, subtract=False, sub_median=True, sub_floor=0, sub_ct_range=(None, None),
                  sub_window=(150.0, 300.0), project_source="cta", slabs=None, rotate_sampling="nearest", rotate_oversample=1,
-                 depth=False, depth_cue=0, render=None, render_options=None, reformat=None, reformat_options=None):
+                 depth=False, depth_cue=0, render=None, render_options=None, reformat=None, reformat_options=None, render3d=None,
+                 render3d_options=None):
         if int(batch) < 1:
             raise ValueError("SeriesTranslator: batch >= 1 expected")
+        self.render3d = None if render3d is None else dict(render3d)
+        self.render3d_options = dict(render3d_options or {})
+        if self.render3d is None and self.render3d_options:
+            raise ValueError("SeriesTranslator: render3d_options need render3d")
+        if self.render3d is not None and (not self.render3d or set(self.render3d_options) - set(RENDER3D_OPTIONS)):
+            raise ValueError("SeriesTranslator: render3d needs at least one table, and render3d_options %r a dict with any of %s"
+                             % (render3d_options, RENDER3D_OPTIONS))
         self.reformat = None if reformat is None else dict(reformat)
         self.reformat_options = dict(reformat_options or {})
         if self.reformat is None and self.reformat_options:
@@ -1089,6 +1282,11 @@ class SeriesTranslator:
                 lambda n, h, w: VolumeReformatter(n, h, w, self.reformat, **self._view_options(), device=self.device,
                                                   **self.reformat_options),
                 VolumeReformatter.result, False)
+        if self.render3d is not None:
+            self._displays["render3d"] = (
+                lambda n, h, w: VolumeRenderer(n, h, w, self.render3d, device=self.device,
+                                               **{"hu": self._view_hu(), **self.render3d_options}),
+                VolumeRenderer.result, False)
         self._views, self._view_host = {}, {}      # by output key: the view, the page-locked copy of its result
         # host seconds of the last call (scripts/export_bench.py): waiting to get a slot back, copying into the input slots,
         # copying out of the output slots, the whole call

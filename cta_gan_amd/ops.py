@@ -1934,6 +1934,19 @@ def _render_int(who, name, v, lo, hi):
     return v
 
 
+def _render_scalars(who, stop, surface, background):
+    """-> (stop, surface, (r, g, b)) of a compositing call, checked."""
+    stop = _render_int(who, "stop", stop, 0, RENDER_OPAQUE - 1)
+    surface = _render_int(who, "surface", surface, 1, RENDER_OPAQUE)
+    try:
+        bg = tuple(background)
+    except TypeError:
+        bg = ()
+    if len(bg) != 3:
+        raise RuntimeError("%s: background: three integers in 0 .. 255 expected, got %r" % (who, background))
+    return stop, surface, tuple(_render_int(who, "background", v, 0, 255) for v in bg)
+
+
 def project_render(pix, n0, coef, t, lut, rgb=None, opacity=None, depth=None, background=(0, 0, 0), stop=128, surface=16384,
                    wc=50.0, ww=400.0, hu=False, sampling="nearest"):
     """One chunk of an int16 volume into its volume-rendered views, in place, one launch of ctg_project_render: pix, n0, coef, t,
@@ -1946,15 +1959,7 @@ def project_render(pix, n0, coef, t, lut, rgb=None, opacity=None, depth=None, ba
     nothing else.  Exact integer arithmetic: equal to numpy bit for bit."""
     lib = _lib.load()
     who = "project_render"
-    stop = _render_int(who, "stop", stop, 0, RENDER_OPAQUE - 1)
-    surface = _render_int(who, "surface", surface, 1, RENDER_OPAQUE)
-    try:
-        bg = tuple(background)
-    except TypeError:
-        bg = ()
-    if len(bg) != 3:
-        raise RuntimeError("%s: background: three integers in 0 .. 255 expected, got %r" % (who, background))
-    bg = tuple(_render_int(who, "background", v, 0, 255) for v in bg)
+    stop, surface, bg = _render_scalars(who, stop, surface, background)
     if torch.is_tensor(lut) and lut.is_cuda:
         raise RuntimeError("%s: the tables are checked on the host: pass host tables or an ops.RotateTable / ops.TransferTable" % who)
     x, table, (k, h, w, n0, n, a, u, t) = _rotate_args(who, pix, n0, coef, t, sampling, (
@@ -2012,6 +2017,31 @@ class LineTable:
         return self.count
 
 
+def _lines_volume(who, vol):
+    if not torch.is_tensor(vol) or not vol.is_cuda:
+        raise RuntimeError("%s: CPU tensors are not supported (no CPU fallback)" % who)
+    if vol.dtype != torch.int16 or vol.dim() != 3:
+        raise RuntimeError("%s: vol must be int16 (N, H, W), got %s %s" % (who, vol.dtype, tuple(vol.shape)))
+
+
+def _lines_args(who, vol, lines, u, t):
+    """What the calls on a line table share, after `_lines_volume` and their own option checks: -> (the contiguous volume, the
+    `LineTable`, (n, h, w, u, t)), the table made for this u and t and on the volume's device."""
+    if torch.is_tensor(lines) and lines.is_cuda:
+        raise RuntimeError("%s: the line table is checked on the host: pass a host table or an ops.LineTable" % who)
+    u, t = int(u), int(t)
+    table = lines if isinstance(lines, LineTable) else LineTable(lines, u, t, vol.device)
+    if (table.u, table.t) != (u, t):
+        raise RuntimeError("%s: the line table was checked for U = %d, T = %d, not for %d, %d" % (who, table.u, table.t, u, t))
+    if table.dev.device != vol.device:
+        raise RuntimeError("%s: vol and the line table must live on one device" % who)
+    x = vol.contiguous()
+    n, h, w = x.shape
+    if not (1 <= min(n, h, w) and max(n, h, w) <= REFORMAT_MAX_DIM):
+        raise RuntimeError("%s: N, H, W in 1 .. %d expected, got %d %d %d" % (who, REFORMAT_MAX_DIM, n, h, w))
+    return x, table, (n, h, w, u, t)
+
+
 def reformat_lines(vol, lines, u, t, mode, fill=None, wc=50.0, ww=400.0, hu=False, sampling="nearest", want_values=True,
                    want_level=True):
     """The whole int16 volume sampled along lines in any direction, one launch of ctg_reformat_lines: vol (N, H, W) int16 on the
@@ -2024,27 +2054,14 @@ def reformat_lines(vol, lines, u, t, mode, fill=None, wc=50.0, ww=400.0, hu=Fals
     numpy bit for bit."""
     lib = _lib.load()
     who = "reformat_lines"
-    if not torch.is_tensor(vol) or not vol.is_cuda:
-        raise RuntimeError("%s: CPU tensors are not supported (no CPU fallback)" % who)
-    if vol.dtype != torch.int16 or vol.dim() != 3:
-        raise RuntimeError("%s: vol must be int16 (N, H, W), got %s %s" % (who, vol.dtype, tuple(vol.shape)))
+    _lines_volume(who, vol)
     code = _project_mode(mode, who)
     if sampling not in REFORMAT_SAMPLINGS:
         raise RuntimeError("%s: sampling %r is not one of %s" % (who, sampling, tuple(REFORMAT_SAMPLINGS)))
     if not want_values and not want_level:
         raise RuntimeError("%s: values, level or both expected" % who)
-    if torch.is_tensor(lines) and lines.is_cuda:
-        raise RuntimeError("%s: the line table is checked on the host: pass a host table or an ops.LineTable" % who)
-    u, t, hu = int(u), int(t), bool(hu)
-    table = lines if isinstance(lines, LineTable) else LineTable(lines, u, t, vol.device)
-    if (table.u, table.t) != (u, t):
-        raise RuntimeError("%s: the line table was checked for U = %d, T = %d, not for %d, %d" % (who, table.u, table.t, u, t))
-    if table.dev.device != vol.device:
-        raise RuntimeError("%s: vol and the line table must live on one device" % who)
-    x = vol.contiguous()
-    n, h, w = x.shape
-    if not (1 <= min(n, h, w) and max(n, h, w) <= REFORMAT_MAX_DIM):
-        raise RuntimeError("%s: N, H, W in 1 .. %d expected, got %d %d %d" % (who, REFORMAT_MAX_DIM, n, h, w))
+    hu = bool(hu)
+    x, table, (n, h, w, u, t) = _lines_args(who, vol, lines, u, t)
     fill = _fill_value(who, fill, hu)
     with torch.cuda.device(vol.device):
         values = torch.empty(table.shape + (u,), dtype=torch.int16, device=vol.device) if want_values else None
@@ -2052,6 +2069,85 @@ def reformat_lines(vol, lines, u, t, mode, fill=None, wc=50.0, ww=400.0, hu=Fals
         _lib.check(lib.ctg_reformat_lines(_p(x), n, h, w, _p(table.dev), table.count, u, t, code, REFORMAT_SAMPLINGS[sampling], fill,
                                           float(wc), float(ww), int(hu), _p(values), _p(level), _stream()), "ctg_reformat_lines")
     return values, level
+
+
+# ---------------------------------------------------------------------------- shaded rendering along lines (csrc/render_lines.hip)
+LIGHT_UNIT = 4096          # the length of a unit light vector
+RENDER_ZSCALE_MAX = 4096   # zscale = 256 / aspect in 8.8 fixed point, 1 .. 4096
+RENDER_GMIN2_MAX = 1 << 26
+
+
+def light_table_host(light, count):
+    """The host half of `LightTable`: light [..., 3] integers, |c| <= 4096, `count` rows -> the int32 copy [count, 3].  Needs no
+    GPU."""
+    import numpy as np
+    host = np.asarray(light.cpu() if torch.is_tensor(light) else light)
+    if host.ndim < 1 or host.shape[-1] != 3 or host.dtype.kind not in "iu":
+        raise RuntimeError("render_lines: a light table of [..., 3] integers expected, got %s %s" % (host.dtype, tuple(host.shape)))
+    if host.size != 3 * int(count):
+        raise RuntimeError("render_lines: a light vector for each of the %d lines expected, got %d" % (int(count), host.size // 3))
+    if (np.abs(host.astype(np.float64)) > LIGHT_UNIT).any():
+        raise RuntimeError("render_lines: light components in -%d .. %d expected (%d = unit length)" % (LIGHT_UNIT, LIGHT_UNIT, LIGHT_UNIT))
+    return np.ascontiguousarray(host.astype(np.int32).reshape(-1, 3))
+
+
+class LightTable:
+    """The light table of `render_lines`: [..., 3] integers, one vector (x, y, z) per line of the line table, 4096 = unit length
+    (`infer.headlight` makes them), checked on the host (`light_table_host`) and uploaded once.  `.host`: the numpy table
+    [count, 3], `.dev`: its device copy, `.count`."""
+
+    def __init__(self, light, count, device=None):
+        self.host = light_table_host(light, count)
+        self.count = int(count)
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("render_lines: a GPU device is required (no CPU fallback)")
+        self.dev = torch.from_numpy(self.host).to(self.device)
+
+    def __len__(self):
+        return self.count
+
+
+def render_lines(vol, lines, u, t, lut, light=None, zscale=256, ambient=77, gmin2=1600, sampling="nearest", background=(0, 0, 0),
+                 stop=128, surface=16384, wc=300.0, ww=1500.0, hu=False, want_rgb=True, want_opacity=True, want_depth=True):
+    """The whole int16 volume composited front to back along the rays of a line table, one launch of ctg_render_lines: vol, lines,
+    u, t and sampling as `reformat_lines`; lut, background, stop, surface, (wc, ww) and hu as `project_render`.  light: None (every
+    sample takes its class colour), an `ops.LightTable`, or a host table [..., 3] with one vector per line, 4096 = unit length,
+    that is checked and uploaded by this call: the colour of a sample is then scaled by ambient + (256 - ambient) |g . light| / |g|
+    (of 256) with g the central-difference gradient at the sample's voxel, its z component times zscale / 256 (zscale = 256 /
+    aspect, 1 .. 4096); ambient 0 .. 256; a sample whose squared gradient is below gmin2 (1 .. 2^26) keeps its colour.  Returns
+    (rgb uint8 [..., u, 3], opacity uint8 [..., u], depth int16 [..., u]) on the GPU, None for those not wanted (not all):
+    depth is the first step at which the accumulated opacity reaches `surface`, -1 if never.  Opacity and depth do not depend
+    on the light.  Exact integer arithmetic: equal to numpy bit for bit."""
+    lib = _lib.load()
+    who = "render_lines"
+    _lines_volume(who, vol)
+    if sampling not in REFORMAT_SAMPLINGS:
+        raise RuntimeError("%s: sampling %r is not one of %s" % (who, sampling, tuple(REFORMAT_SAMPLINGS)))
+    if not (want_rgb or want_opacity or want_depth):
+        raise RuntimeError("%s: rgb, opacity or depth expected" % who)
+    stop, surface, bg = _render_scalars(who, stop, surface, background)
+    zscale = _render_int(who, "zscale", zscale, 1, RENDER_ZSCALE_MAX)
+    ambient = _render_int(who, "ambient", ambient, 0, 256)
+    gmin2 = _render_int(who, "gmin2", gmin2, 1, RENDER_GMIN2_MAX)
+    if any(torch.is_tensor(v) and v.is_cuda for v in (lut, light)):
+        raise RuntimeError("%s: the tables are checked on the host: pass host tables or an ops.TransferTable / ops.LightTable" % who)
+    x, table, (n, h, w, u, t) = _lines_args(who, vol, lines, u, t)
+    transfer = lut if isinstance(lut, TransferTable) else TransferTable(lut, vol.device)
+    lamp = None if light is None else (light if isinstance(light, LightTable) else LightTable(light, table.count, vol.device))
+    if lamp is not None and lamp.count != table.count:
+        raise RuntimeError("%s: a light vector for each of the %d lines expected, got %d" % (who, table.count, lamp.count))
+    if transfer.dev.device != vol.device or (lamp is not None and lamp.dev.device != vol.device):
+        raise RuntimeError("%s: vol and the tables must live on one device" % who)
+    with torch.cuda.device(vol.device):
+        rgb = torch.empty(table.shape + (u, 3), dtype=torch.uint8, device=vol.device) if want_rgb else None
+        opacity = torch.empty(table.shape + (u,), dtype=torch.uint8, device=vol.device) if want_opacity else None
+        depth = torch.empty(table.shape + (u,), dtype=torch.int16, device=vol.device) if want_depth else None
+        _lib.check(lib.ctg_render_lines(_p(x), n, h, w, _p(table.dev), table.count, u, t, _p(transfer.dev), REFORMAT_SAMPLINGS[sampling],
+                                        stop, surface, bg[0], bg[1], bg[2], float(wc), float(ww), int(bool(hu)),
+                                        _p(None if lamp is None else lamp.dev), zscale, ambient, gmin2, _p(rgb), _p(opacity),
+                                        _p(depth), _stream()), "ctg_render_lines")
+    return rgb, opacity, depth
 
 
 def project_accumulate_depth(pix, n0, thick, mode, axial=None, coronal=None, sagittal=None):

@@ -609,6 +609,46 @@ int ctg_project_render(const short* pix, int K, int H, int W, int n0, int N, con
 int ctg_reformat_lines(const short* vol, int N, int H, int W, const int* lines, int L, int U, int T, int mode, int sampling,
                        int fill, float wc, float ww, int hu, short* values, unsigned char* level, void* stream);
 
+/* ---- series inference, shaded volume rendering along lines in any direction (added under ABI 15: purely additive, no existing
+ * signature or meaning moves, so the version stays 15): the compositing of ctg_project_render along the rays of a line table,
+ * with trilinear sampling, anisotropic voxels inside the geometry and every sample's colour shaded by the local gradient.
+ * cta_gan_amd/infer.py: VolumeRenderer, render_lines_volume, headlight, line_voxel, SeriesTranslator(render3d=...);
+ * ops.render_lines, ops.LightTable.  The reference has no counterpart.
+ * ctg_render_lines: vol, N, H, W, lines, L, U, T, the positions of the samples, the "counted" rule and the value v of a sample
+ *   (sampling 0 = nearest, 1 = trilinear) are exactly those of ctg_reformat_lines; lut, stop, surface, bg_r, bg_g, bg_b, wc, ww, hu,
+ *   the class of a counted sample, col = min(R, G, B, 255) and A = min(alpha, 32768) are exactly those of ctg_project_render.
+ *   Compositing: over the ray's counted samples in ascending step k, from Tr = 32768 and C[3] = 0, all uint32:
+ *       wgt = (Tr A) >> 15;   C[c] += wgt cols[c];   Tr -= wgt;
+ *       if depth < 0 and 32768 - Tr >= surface: depth = k;     if Tr <= stop: the ray ends (later samples take no part)
+ *   Shading: light = int32 [L][3] on the device, 4-byte aligned, one vector per line (4096 = unit length), or NULL: cols = col.
+ *     Otherwise the colour of a counted sample is shaded at its own voxel (xi, yi, zi) = (X >> 16, Y >> 16, Z >> 16), the same for
+ *     both samplings, p = the stored int16 values:
+ *       dx = p[zi][yi][min(xi+1, W-1)] - p[zi][yi][max(xi-1, 0)], dy and dz likewise along y and z (central differences, the edge
+ *         replicated; `hu` cancels);
+ *       gx = clamp(dx, -4095, 4095), gy likewise, gz = clamp((dz zscale + 128) >> 8, -4095, 4095) (arithmetic shift), zscale =
+ *         256 / aspect in 8.8 fixed point (aspect = slice spacing / pixel spacing);  m = gx^2 + gy^2 + gz^2 < 2^26;
+ *       l[c] = clamp(light[l][c], -4096, 4096) -- clamped in the kernel, so any table is defined;
+ *       dot = |gx l[0] + gy l[1] + gz l[2]| < 2^26: the absolute value makes the lighting two-sided;
+ *       shade = 256 if m < gmin2 (a flat region shows its class colour); otherwise, with n = floor(sqrt(m)) >= 1 exactly,
+ *         diff = min((dot / n) >> 4, 256) (C division) and shade = ambient + (((256 - ambient) diff + 128) >> 8);
+ *       cols[c] = (col[c] shade + 128) >> 8 <= 255.
+ *     So C[c] <= 32768 * 255 as in ctg_project_render and no output needs a clamp.  Opacity and depth do not depend on the shading.
+ *   Outputs, any subset, at least one: rgb uint8 [L][U][3] = (C[c] + bg_c Tr + 16384) >> 15; opacity uint8 [L][U] =
+ *     ((32768 - Tr) 255 + 16384) >> 15; depth int16 [L][U] (2-byte aligned) = the step of the first counted sample at which
+ *     32768 - Tr reaches `surface`, -1 if it never does.  A ray that misses the volume gives bg, opacity 0 and depth -1.
+ *   Every volume address is bounds-checked or clamped whatever the tables hold, and an uncounted sample reads voxel 0, its gradient
+ *   included; the fixed-point sums are unsigned as in ctg_reformat_lines (the caller keeps the same range).  No floating point
+ *   enters the gradient: a float square root only seeds the integer one, which is corrected to the exact floor.
+ *   Exact integer arithmetic: the same bits as numpy (tests/render_lines_np.py).  One launch, no accumulator, no atomics.
+ *   CTG_EINVAL, nothing launched: a null vol, lines or lut; no output; N, H, W, U or T outside 1 .. 4096; L < 1; sampling outside
+ *   0 .. 1; stop outside 0 .. 32767; surface outside 1 .. 32768; a bg outside 0 .. 255; zscale outside 1 .. 4096; ambient outside
+ *   0 .. 256; gmin2 outside 1 .. 67108864; vol, lut or depth not 2-byte aligned, lines or light not 4-byte aligned; a grid beyond
+ *   2^31 - 1 workgroups (L ceil(U / 32)). ---- */
+int ctg_render_lines(const short* vol, int N, int H, int W, const int* lines, int L, int U, int T, const unsigned short* lut,
+                     int sampling, int stop, int surface, int bg_r, int bg_g, int bg_b, float wc, float ww, int hu,
+                     const int* light, int zscale, int ambient, int gmin2, unsigned char* rgb, unsigned char* opacity,
+                     short* depth, void* stream);
+
 /* ---- LPIPS (AlexNet, lpips 0.1) of the test() loops (ABI 14): `loss_fn_alex = lpips.LPIPS(net='alex')` (trainer/HdTrainer.py:26-28)
  * and its calls `loss_fn_alex.forward(torch.tensor(c), torch.tensor(b))` on the windowed and on the raw masked pair of every slice
  * (HdTrainer.py:504-513, 531-536, 1029-1031, 1054-1056; the twins in CycTrainer.py, p2pTrainer.py, RegTrainer.py).  The five

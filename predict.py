@@ -13,6 +13,8 @@
                       [--depth [--depth-cue C]]
                       [--vr-dir DIR [--vr-angles 36] [--vr-span 360] [--vr-preset grey|vessels|bone] [--vr-wc 300 --vr-ww 1500]
                        [--vr-sampling nearest|bilinear] [--vr-oversample S] [--vr-background R,G,B] [--aspect R]]
+                      [--vr3d-dir DIR [--vr3d-axis x|y|z|X,Y,Z] [--vr3d-sampling nearest|trilinear]
+                       [--vr3d-shade [--vr3d-ambient 0.3] [--vr3d-gmin 40]]]
                       [--mpr-dir DIR --mpr-normal X,Y,Z [--mpr-count P] [--mpr-pitch D] [--mpr-thick T]]
                       [--tumble-dir DIR [--tumble-angles 36] [--tumble-axis x|y|z]]
                       [--cpr-dir DIR --cpr-centreline pts.npy [--cpr-angles A] [--cpr-width U] [--cpr-thick T]]
@@ -58,6 +60,15 @@ transfer function that gives every class its colour and opacity (cta_gan_amd/inf
 shows through where a ray stays transparent.  vr_%03d.png, one RGB frame [round(N R), D] per angle, and render.npz with rgb
 (uint8 [A, N, D, 3]), opacity (uint8), depth (int16: the step at which a ray becomes half opaque, -1 if never), angles and lut
 (the uint16 [256, 4] transfer table that was used).
+--vr3d-dir: the volume-rendered view along rays in any direction, made after the last chunk from the volume kept on the device
+(cta_gan_amd/infer.py: VolumeRenderer): --vr-angles views over --vr-span degrees about --vr3d-axis x (default: the tumble), y, z
+or any X,Y,Z through the centre, with --vr-preset, --vr-wc / --vr-ww, --vr-oversample, --vr-background and --mip-source as for
+--vr-dir and --vr3d-sampling trilinear (default) or nearest.  --aspect R is inside the geometry: the frames are isotropic and no
+row is repeated.  --vr3d-shade shades every sample by the local gradient under a light along the rays: --vr3d-ambient (0 .. 1)
+is the share of its colour a wall edge-on to the light keeps, --vr3d-gmin the gradient (stored units over two voxels) below
+which a sample keeps its colour.  vr3d_%03d.png, one RGB frame per angle, and render3d.npz with rgb (uint8 [A, R, U, 3]), opacity
+(uint8), depth (int16), angles, lut, lines (the int64 [A, R, 9] line table) and light (int64 [A, R, 3]; empty without
+--vr3d-shade).
 --mpr-dir, --tumble-dir, --cpr-dir: reformats whose rows cross slices, made after the last chunk from the volume kept on the
 device (cta_gan_amd/infer.py: VolumeReformatter), of the same source (--mip-source) in the same window, with --mip-mode along
 their rays and --reformat-sampling trilinear (default) or nearest.  --aspect R is inside their geometry: the images are isotropic
@@ -109,6 +120,13 @@ def build_parser():
     parser.add_argument("--vr-sampling", choices=["nearest", "bilinear"], default="nearest", help="how a ray samples the slice (with --vr-dir)")
     parser.add_argument("--vr-oversample", type=int, default=1, help="steps per voxel along a ray (with --vr-dir)")
     parser.add_argument("--vr-background", type=str, default="0,0,0", help="R,G,B in 0 .. 255 behind the rendered view (with --vr-dir)")
+    parser.add_argument("--vr3d-dir", type=str, default=None, help="also write the volume-rendered view about --vr3d-axis here")
+    parser.add_argument("--vr3d-axis", type=str, default="x", help="the axis of the orbit: x, y, z or X,Y,Z (with --vr3d-dir)")
+    parser.add_argument("--vr3d-sampling", choices=["nearest", "trilinear"], default="trilinear",
+                        help="how a ray samples the volume (with --vr3d-dir)")
+    parser.add_argument("--vr3d-shade", action="store_true", help="shade every sample by the local gradient (with --vr3d-dir)")
+    parser.add_argument("--vr3d-ambient", type=float, default=0.3, help="the share of its colour an unlit wall keeps (with --vr3d-shade)")
+    parser.add_argument("--vr3d-gmin", type=float, default=40.0, help="the gradient below which a sample is not shaded (with --vr3d-shade)")
     parser.add_argument("--mpr-dir", type=str, default=None, help="also write oblique planes (MPR) here")
     parser.add_argument("--mpr-normal", type=str, default=None, help="X,Y,Z: the normal of the oblique planes (with --mpr-dir)")
     parser.add_argument("--mpr-count", type=int, default=1, help="parallel oblique planes (with --mpr-dir)")
@@ -197,6 +215,15 @@ def parse_args(argv=None):
         parser.error("--vr-background: three values R,G,B in 0 .. 255 expected")
     if opts.vr_angles < 1 or opts.vr_oversample < 1:
         parser.error("--vr-angles and --vr-oversample: at least 1 expected")
+    if opts.vr3d_axis not in ("x", "y", "z"):
+        try:
+            opts.vr3d_axis = tuple(float(v) for v in opts.vr3d_axis.split(","))
+        except ValueError:
+            parser.error("--vr3d-axis: x, y, z or numbers X,Y,Z expected, got %r" % opts.vr3d_axis)
+        if len(opts.vr3d_axis) != 3 or not any(opts.vr3d_axis):
+            parser.error("--vr3d-axis: x, y, z or three numbers X,Y,Z, not all zero, expected")
+    if not 0.0 <= opts.vr3d_ambient <= 1.0 or not 0.0 <= opts.vr3d_gmin <= 8192.0:
+        parser.error("--vr3d-ambient: 0 .. 1 and --vr3d-gmin: 0 .. 8192 expected")
     if (opts.mpr_dir is None) != (opts.mpr_normal is None):
         parser.error("--mpr-dir and --mpr-normal need each other")
     if opts.mpr_normal is not None:
@@ -272,6 +299,16 @@ def main(argv=None):
         vr_lut = transfer_function(TRANSFER_PRESETS[opts.vr_preset], opts.vr_oversample)
         vr_options = {"transfer": vr_lut, "wc": opts.vr_wc, "ww": opts.vr_ww, "sampling": opts.vr_sampling,
                       "oversample": opts.vr_oversample, "background": opts.vr_background}
+    vr3d = vr3d_options = vr3d_lut = vr3d_light = None
+    if opts.vr3d_dir is not None:      # the geometry, the table and the light are made here, so that render3d.npz can record them
+        from cta_gan_amd.infer import TRANSFER_PRESETS, headlight, orbit_lines, transfer_function
+        vr3d_lut = transfer_function(TRANSFER_PRESETS[opts.vr_preset], opts.vr_oversample)
+        vr3d = orbit_lines(*volume.shape, view_angles(opts.vr_angles, opts.vr_span), axis=opts.vr3d_axis,
+                           oversample=opts.vr_oversample, aspect=opts.aspect)
+        vr3d_light = headlight(vr3d, opts.aspect) if opts.vr3d_shade else np.zeros((0, 3), dtype=np.int64)
+        vr3d_options = {"transfer": vr3d_lut, "wc": opts.vr_wc, "ww": opts.vr_ww, "sampling": opts.vr3d_sampling,
+                        "background": opts.vr_background, "aspect": opts.aspect,
+                        "shading": {"ambient": opts.vr3d_ambient, "gmin": opts.vr3d_gmin, "light": "head"} if opts.vr3d_shade else None}
     reformat, reformat_angles = reformat_tables(opts)
     translate =SeriesTranslator(generator, batch=opts.batch, size=config.get("size"), wc=opts.wc, ww=opts.ww, hu=opts.hu,
                                  level=opts.level_dir is not None or opts.sub_level_dir is not None, device=device,
@@ -284,7 +321,8 @@ def main(argv=None):
                                  slabs=opts.sts, depth=opts.depth, depth_cue=opts.depth_cue,
                                  render=view_angles(opts.vr_angles, opts.vr_span) if opts.vr_dir is not None else None,
                                  render_options=vr_options, reformat=reformat,
-                                 reformat_options={"mode": opts.mip_mode, "sampling": opts.reformat_sampling} if reformat else None)
+                                 reformat_options={"mode": opts.mip_mode, "sampling": opts.reformat_sampling} if reformat else None,
+                                 render3d=None if vr3d is None else {"vr3d": vr3d}, render3d_options=vr3d_options)
     shown = "cued" if opts.depth_cue > 0 else "level"      # the plane the PNGs of the projections are written from
     out = translate(volume)
     np.save(opts.output, out["pix"])
@@ -345,6 +383,17 @@ os.path.join(opts.vr_dir, "vr_%03d.png" % i))
         np.savez(os.path.join(opts.vr_dir, "render.npz"), rgb=ren["rgb"], opacity=ren["opacity"], depth=ren["depth"],
                  angles=ren["angles"], lut=vr_lut)
         print("wrote %d volume-rendered views (%s) to %s" % (len(ren["angles"]), opts.vr_preset, opts.vr_dir), flush=True)
+    if opts.vr3d_dir is not None:
+        from PIL import Image
+        os.makedirs(opts.vr3d_dir, exist_ok=True)
+        ren = out["render3d"]["vr3d"]
+        for i, frame in enumerate(ren["rgb"]):
+            Image.fromarray(np.ascontiguousarray(frame)).save(os.path.join(opts.vr3d_dir, "vr3d_%03d.png" % i))      # mode "RGB"
+        np.savez(os.path.join(opts.vr3d_dir, "render3d.npz"), rgb=ren["rgb"], opacity=ren["opacity"], depth=ren["depth"],
+                 angles=np.array(view_angles(opts.vr_angles, opts.vr_span), dtype=np.float64), lut=vr3d_lut, lines=vr3d[0],
+                 light=vr3d_light)
+        print("wrote %d %s volume-rendered views (%s, %s sampling) to %s"
+              % (len(ren["rgb"]), "shaded" if opts.vr3d_shade else "flat", opts.vr_preset, opts.vr3d_sampling, opts.vr3d_dir), flush=True)
     for kind, where in (("mpr", opts.mpr_dir), ("tumble", opts.tumble_dir), ("cpr", opts.cpr_dir)):
         if where is None:
             continue

@@ -93,6 +93,9 @@ SIGNATURES = {
     "ctg_project_render": "piiiiipiiipiiiiiiffipppp",
     "ctg_reformat_lines": "piiipiiiiiiffippp",
     "ctg_render_lines": "piiipiiipiiiiiiffipiiipppp",
+    "ctg_components_label": "piiiiiippp",
+    "ctg_components_select": "plipiiippppp",
+    "ctg_components_apply": "pppliiffippp",
     "ctg_window_pairs": "ppppilipp",
     "ctg_maxpool3s2_fwd": "pipiiiiip",
     "ctg_lpips_layer": "pipiliippp",

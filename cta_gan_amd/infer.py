@@ -55,7 +55,13 @@ colour shaded by the local gradient (`ops.render_lines`: the compositing chain o
 sample's voxel, a light per line from `headlight` or one fixed vector, all in exact integers).  It keeps the volume on the device
 as the reformats do (`_ResidentVolume` holds what the two share); `line_voxel` maps a depth back to its voxel.
 
-The view protocol.  The six display classes above are views (`_SeriesView` holds what they share), and `SeriesTranslator` and
+Connected components (`VolumeComponents`, `components_volume`, `SeriesTranslator(components=..., project_source="vessels")`): the
+volume with only the wanted connected components of a threshold band left -- islands below a size dropped, the K largest kept, or
+the component a seed voxel (`ray_voxel`, `line_voxel`) lies in -- labelled on the device after the last chunk (`ops.components_label`
+/ `components_select` / `components_apply`: a block union-find whose labels are the smallest linear index of a component, so the
+result does not depend on the order of the kernels' atomics).  A third `_ResidentVolume`; `root_voxel` maps a root to its voxel.
+
+The view protocol.  The seven display classes above are views (`_SeriesView` holds what they share), and `SeriesTranslator` and
 the `*_volume` functions drive every one of them the same way.  A view is made for one volume shape and has `.n`, `.h`, `.w` and
 `.device`; `update(pix_chunk, n0)` takes a device chunk of slices n0 .. n0+K-1 on the current stream, in any order, every slice
 once; `result()` returns a tree on the device -- a dict of tensors, Nones and nested dicts -- once they have all arrived;
@@ -1089,6 +1095,124 @@ def render_lines_volume(volume, tables, batch=64, device=None, **options):
     return _view_of_volume("render_lines_volume", volume, batch, device, make, upload=False)
 
 
+COMPONENTS_OPTIONS = ("threshold", "connectivity", "min_voxels", "largest", "seeds", "background", "fill", "wc", "ww", "hu", "level",
+                      "labels", "top")
+
+
+def root_voxel(root, h, w):
+    """(z, y, x) of a component's root, the linear index (z h + y) w + x that `VolumeComponents` labels it with (the smallest in
+    the component: its first voxel in slice, row, column order).  A pure host function; root may be an integer or an integer
+    array, a row (-1, 0) of "top" has no voxel."""
+    h, w = int(h), int(w)
+    if h < 1 or w < 1:
+        raise ValueError("root_voxel: h, w >= 1 expected, got %d %d" % (h, w))
+    r = np.asarray(root, dtype=np.int64)
+    if (r < 0).any():
+        raise ValueError("root_voxel: a root is a linear index >= 0 (a (-1, 0) row of `top` stands for no component)")
+    z, y, x = r // (h * w), (r // w) % h, r % w
+    return (int(z), int(y), int(x)) if r.ndim == 0 else (z, y, x)
+
+
+class VolumeComponents(_ResidentVolume):
+    """The connected components of an int16 volume [n, h, w] that arrives in chunks and stays on the device, and the volume with
+    only the wanted ones left (`ops.components_label` / `components_select` / `components_apply`, csrc/components.hip): despeckle,
+    the K largest vessels, the vessel tree a click lies in.  threshold: lo, or (lo, hi) with hi = 32767 by default -- a voxel is
+    foreground when lo <= value <= hi (stored values: HU differences for the subtraction volume); connectivity 6 / 18 / 26 in index
+    space.  Kept are the components of at least `min_voxels` voxels that, where `seeds` (a sequence of (z, y, x), e.g. from
+    `ray_voxel` / `line_voxel`) is given, hold a seed; of those the `largest` = K biggest (0: all; ties: the smaller root first).
+    background=False masks: everything but the kept components becomes `fill` (default: air, 0 or -1024 with `hu`);
+    background=True despeckles: only the dropped components do.  `update(pix_chunk, n0)` copies a chunk in, in any order;
+    `result()` raises unless every slice has arrived exactly once since the last `reset()` -> {"values": int16 [n, h, w],
+    "level": uint8 in the window (wc, ww) or None, "labels": int32 [n, h, w] (-1 on background, otherwise the component's root:
+    its smallest linear index, `root_voxel`) or None, "top": int32 [top, 2] = (root, size) of the biggest kept components in
+    order, (-1, 0) beyond them, "stats": int32 [8] = foreground voxels, components, candidates, kept components, kept voxels,
+    seeds that selected nothing, the internal-error flag (whoever reads stats on the host raises unless it is 0:
+    `check_components_stats`), 0} on the device.  `.nbytes`: the device memory held (the volume, labels, sizes, marks: 11 bytes
+    per voxel) plus that of one result (2, or 3 with level, per voxel), known before the first chunk.  It holds its own copy of
+    the volume.  Exact integer arithmetic on the current stream: equal to numpy bit for bit, whatever order the atomics land in."""
+
+    def __init__(self, n, h, w, threshold, connectivity=26, min_voxels=1, largest=0, seeds=None, background=False, fill=None,
+                 wc=50.0, ww=400.0, hu=False, level=True, labels=False, top=8, device=None):
+        who = "VolumeComponents"
+        self._sides(who, n, h, w)
+        if self.n * self.h * self.w > 2 ** 31 - 1:
+            raise ValueError("%s: at most 2^31 - 1 voxels expected, got %d x %d x %d" % (who, self.n, self.h, self.w))
+        band = tuple(threshold) if isinstance(threshold, (tuple, list)) else (threshold, 32767)
+        if len(band) != 2 or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in band):
+            raise ValueError("%s: threshold: an integer lo or a pair (lo, hi) expected, got %r" % (who, threshold))
+        self.lo, self.hi = int(band[0]), int(band[1])
+        if not -32768 <= self.lo <= self.hi <= 32767:
+            raise ValueError("%s: threshold: -32768 <= lo <= hi <= 32767 expected, got %r" % (who, threshold))
+        if connectivity not in ops.COMPONENTS_CONNECTIVITY:
+            raise ValueError("%s: connectivity %r is not one of %s" % (who, connectivity, ops.COMPONENTS_CONNECTIVITY))
+        self.connectivity = int(connectivity)
+        for name, v, lo, hi in (("min_voxels", min_voxels, 1, 2 ** 31 - 1), ("largest", largest, 0, ops.COMPONENTS_MAX_TOP),
+                                ("top", top, 0, ops.COMPONENTS_MAX_TOP)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+                raise ValueError("%s: %s: an integer in %d .. %d expected, got %r" % (who, name, lo, hi, v))
+        self.min_voxels, self.largest, self.top = int(min_voxels), int(largest), int(top)
+        self.seeds_host = None
+        if seeds is not None:
+            pts = np.asarray(list(seeds))
+            if pts.size == 0 or pts.ndim != 2 or pts.shape[1] != 3 or pts.dtype.kind not in "iu":
+                raise ValueError("%s: seeds: a sequence of integer (z, y, x), at least one, expected, got %r" % (who, seeds))
+            pts = pts.astype(np.int64)
+            if (pts < 0).any() or (pts >= np.array([self.n, self.h, self.w])).any():
+                raise ValueError("%s: a seed lies outside the volume (%d, %d, %d)" % (who, self.n, self.h, self.w))
+            self.seeds_host = ((pts[:, 0] * self.h + pts[:, 1]) * self.w + pts[:, 2]).astype(np.int32)
+        self.background, self.hu, self.window = bool(background), bool(hu), (float(wc), float(ww))
+        self.want_level, self.want_labels = bool(level), bool(labels)
+        self.fill = (-1024 if self.hu else 0) if fill is None else int(fill)
+        if not -32768 <= self.fill <= 32767:
+            raise ValueError("%s: fill %d is not an int16 value" % (who, self.fill))
+        v = self.n * self.h * self.w
+        self.nbytes = (2 + 4 + 4 + 1) * v + (2 + (1 if self.want_level else 0)) * v + 4 * (8 + 2 * self.top) + \
+            (0 if self.seeds_host is None else self.seeds_host.nbytes)
+        self._resident(device)
+        self.seeds = self._labels = self._sizes = self._keep = None      # on the device from the first chunk / result on
+
+    def _upload(self):
+        if self.seeds_host is not None:
+            self.seeds = torch.from_numpy(self.seeds_host).to(self.device)
+
+    def result(self):
+        self._whole()
+        # the labels a caller asked for are theirs: a fresh array per result; otherwise the working arrays are kept between calls
+        labels, stats = ops.components_label(self.volume, self.lo, self.hi, self.connectivity,
+                                             labels=None if self.want_labels else self._labels)
+        self._sizes, self._keep, top = ops.components_select(labels, stats, min_voxels=self.min_voxels, seeds=self.seeds,
+                                                             largest=self.largest, ntop=self.top, sizes=self._sizes, keep=self._keep)
+        if not self.want_labels:
+            self._labels = labels
+        values, level = ops.components_apply(self.volume, labels, self._keep, background=self.background, fill=self.fill,
+                                             wc=self.window[0], ww=self.window[1], hu=self.hu, want_level=self.want_level)
+        return {"values": values, "level": level, "labels": labels if self.want_labels else None, "top": top, "stats": stats}
+
+
+def check_components_stats(stats):
+    """Raise unless the internal-error flag of a `VolumeComponents` result's "stats", read on the host, is 0."""
+    flag = int(np.asarray(stats.cpu() if torch.is_tensor(stats) else stats).reshape(-1)[6])
+    if flag != 0:
+        raise RuntimeError("VolumeComponents: the labelling met a value that cannot be a parent (stats[6] = %d): the result is not "
+                           "to be trusted" % flag)
+
+
+def components_volume(volume, threshold, batch=64, device=None, **options):
+    """The components view of a volume that already exists, the twin of `reformat_volume`: int16 [N, H, W], a host array / CPU
+    tensor (chunks of `batch` slices cross PCIe one after another) or a device tensor; threshold and the options as
+    `VolumeComponents`.  Returns what `VolumeComponents.result` returns, of the input's kind; a result that comes back to the
+    host has had its error flag checked."""
+    def make(n, h, w, dev):      # (the device is resolved here: the chunk loop runs under it)
+        return VolumeComponents(n, h, w, threshold, device=torch.device("cuda", torch.cuda.current_device()) if dev is None else dev,
+                                **options)
+
+    # host chunks go to `update` as they are: it copies them into the resident volume, the only time they cross PCIe
+    out = _view_of_volume("components_volume", volume, batch, device, make, upload=False)
+    if not torch.is_tensor(out["stats"]) or not out["stats"].is_cuda:
+        check_components_stats(out["stats"])
+    return out
+
+
 def subtract_volume(cta, ct_hu, cta_is_hu=False, median=True, floor=0, ct_range=(None, None), wc=150.0, ww=300.0, level=True,
                     batch=64, device=None):
     """The subtraction of two volumes that already exist (a real CTA and its registered CT for a side-by-side view, or a
@@ -1129,7 +1253,8 @@ def subtract_volume(cta, ct_hu, cta_is_hu=False, median=True, floor=0, ct_range=
     return {"sub": conv(sub), "level": None if lvl is None else conv(lvl)}
 
 
-PROJECT_SOURCES = ("cta", "sub")
+PROJECT_SOURCES = ("cta", "sub", "vessels")
+COMPONENTS_SOURCES = ("cta", "sub")
 REFORMAT_OPTIONS = ("mode", "sampling", "fill", "cols")
 RENDER_OPTIONS = ("transfer", "detector", "wc", "ww", "hu", "sampling", "oversample", "background", "stop", "surface", "depth")
 RENDER3D_OPTIONS = ("transfer", "wc", "ww", "hu", "sampling", "shading", "aspect", "background", "stop", "surface", "depth", "cols")
@@ -1177,6 +1302,15 @@ class SeriesTranslator:
     (`project_source`) along rays in any direction, one launch per table after the last chunk, copied back once.  It keeps the
     source volume on the device (`VolumeRenderer.nbytes`); with `reformat` on as well the two hold a copy each (sharing one is not
     built).  With render3d=None nothing of it is allocated or launched.
+    components = a dict of `VolumeComponents` keyword arguments (threshold, and any of connectivity, min_voxels, largest, seeds,
+    background, fill, wc, ww, hu, level, labels, top) adds "vessels": {"values": int16 [N, H, W], "level": uint8 or None, "labels":
+    int32 or None, "top": int32 [top, 2], "stats": int32 [8]}, the volume of components_source ("cta" or "sub", which needs
+    subtract=True; default: what `project_source` shows, "cta" for "vessels") with only the wanted connected components left, in
+    that source's window and `hu`, labelled after the last chunk and copied back once; a stats[6] other than 0 raises.  It keeps
+    the source volume on the device (`VolumeComponents.nbytes`).  project_source="vessels" (needs components) makes every other
+    display show that cleaned volume: the chunk loop then feeds only the components view, and the cleaned volume is handed to the
+    other displays after the last chunk, device to device, in chunks of `batch` slices.  With components=None nothing of it is
+    allocated or launched.
 
     size: the side(s) the generator runs at (None: the volume's own); a volume of another size is resized (nearest) on the way
     in and comes back at its own size.  wc / ww: the window of the 8-bit level; hu: pixels minus 1024 (SimpleITK) instead of
@@ -1187,9 +1321,23 @@ class SeriesTranslator:
                  slab=None, rotate=None, rotate_mode=None, subtract=False, sub_median=True, sub_floor=0, sub_ct_range=(None, None),
                  sub_window=(150.0, 300.0), project_source="cta", slabs=None, rotate_sampling="nearest", rotate_oversample=1,
                  depth=False, depth_cue=0, render=None, render_options=None, reformat=None, reformat_options=None, render3d=None,
-                 render3d_options=None):
+                 render3d_options=None, components=None, components_source=None):
         if int(batch) < 1:
             raise ValueError("SeriesTranslator: batch >= 1 expected")
+        self.components = None if components is None else dict(components)
+        if self.components is None and components_source is not None:
+            raise ValueError("SeriesTranslator: components_source needs components")
+        if self.components is not None and ("threshold" not in self.components or set(self.components) - set(COMPONENTS_OPTIONS)):
+            raise ValueError("SeriesTranslator: components %r: a dict with 'threshold' and any of %s expected"
+                             % (components, COMPONENTS_OPTIONS))
+        if project_source == "vessels" and self.components is None:
+            raise ValueError("SeriesTranslator: project_source 'vessels' needs components")
+        if components_source is None:
+            components_source = "cta" if project_source not in COMPONENTS_SOURCES else project_source
+        if components_source not in COMPONENTS_SOURCES or (self.components is not None and components_source == "sub" and not subtract):
+            raise ValueError("SeriesTranslator: components_source %r: one of %s expected, and 'sub' needs subtract=True"
+                             % (components_source, COMPONENTS_SOURCES))
+        self.components_source = components_source
         self.render3d = None if render3d is None else dict(render3d)
         self.render3d_options = dict(render3d_options or {})
         if self.render3d is None and self.render3d_options:
@@ -1287,6 +1435,14 @@ class SeriesTranslator:
                 lambda n, h, w: VolumeRenderer(n, h, w, self.render3d, device=self.device,
                                                **{"hu": self._view_hu(), **self.render3d_options}),
                 VolumeRenderer.result, False)
+        if self.components is not None:
+            # its window and `hu` are those of its own source, which is also what the other displays show with "vessels"
+            sub = self.components_source == "sub"
+            wc_, ww_ = self.sub_window if sub else self.window
+            self._displays["vessels"] = (
+                lambda n, h, w: VolumeComponents(n, h, w, device=self.device,
+                                                 **{"wc": wc_, "ww": ww_, "hu": True if sub else self.hu, **self.components}),
+                VolumeComponents.result, False)
         self._views, self._view_host = {}, {}      # by output key: the view, the page-locked copy of its result
         # host seconds of the last call (scripts/export_bench.py): waiting to get a slot back, copying into the input slots,
         # copying out of the output slots, the whole call
@@ -1365,8 +1521,11 @@ class SeriesTranslator:
                             planes["pix"], dev_hu, cta_is_hu=self.hu, median=self.sub_median, floor=self.sub_floor,
                             ct_range=self.sub_ct_range, wc=self.sub_window[0], ww=self.sub_window[1], want_level=self.level)
                     src = planes["sub" if self.project_source == "sub" else "pix"]
-                    for view in views.values():
-                        view.update(src, s)
+                    for key, view in views.items():
+                        if key == "vessels":
+                            view.update(planes["sub" if self.components_source == "sub" else "pix"], s)
+                        elif self.project_source != "vessels":      # (with "vessels" they are fed after the last chunk)
+                            view.update(src, s)
                 computed = torch.cuda.Event()
                 computed.record(cur)
                 drain(slot)                          # the chunk that used this slot last: its D2H started two chunks ago
@@ -1382,9 +1541,19 @@ class SeriesTranslator:
             # drained, so that the copies run while the host drains (the reformats are one launch per table first: the whole
             # volume is on the device now).  An event per display: the host clones one display's planes while the next one's
             # are still being copied.
-            staged = {}
+            staged, trees = {}, {}
+            if "vessels" in views:
+                trees["vessels"] = self._displays["vessels"][1](views["vessels"])
+                if self.project_source == "vessels":
+                    # the cleaned volume to the other displays, device to device on this stream, in the chunks they are used to
+                    with torch.no_grad():
+                        for s, e, _ in plan_chunks(n, self.batch):
+                            for key, view in views.items():
+                                if key != "vessels":
+                                    view.update(trees["vessels"]["values"][s:e], s)
             for key, view in views.items():
-                host, copied = self._stage_view(key, self._displays[key][1](view)), torch.cuda.Event()
+                tree = trees[key] if key in trees else self._displays[key][1](view)
+                host, copied = self._stage_view(key, tree), torch.cuda.Event()
                 copied.record(cur)
                 staged[key] = (host, copied)
             for slot in sorted(range(SLOTS), key=lambda q: pending[q][1] if pending[q] else -1):
@@ -1395,6 +1564,8 @@ class SeriesTranslator:
                 copied.synchronize()
                 stats["wait"] += clock() - t0
                 shown[key] = _tree_to(host, (lambda t: t.clone().numpy()) if is_np else (lambda t: t.clone()))
+                if key == "vessels":
+                    check_components_stats(shown[key]["stats"])      # on the host now: no extra synchronisation
                 if self._displays[key][2]:
                     angles = views[key].angles
                     shown[key]["angles"] = np.array(angles, dtype=np.float64) if is_np else torch.tensor(angles, dtype=torch.float64)
@@ -1434,8 +1605,12 @@ class SeriesTranslator:
 
     def _view_window(self):
         """The window of the projections' and the rotation's levels: the subtraction's when that is what they show."""
-        return self.sub_window if self.project_source == "sub" else self.window
+        return self.sub_window if self._view_source() == "sub" else self.window
 
     def _view_hu(self):
         """A subtraction value is a HU difference: 0 is the window's zero, whatever convention the synthesized pixels use."""
-        return True if self.project_source == "sub" else self.hu
+        return True if self._view_source() == "sub" else self.hu
+
+    def _view_source(self):
+        """What the displays show: with "vessels" the cleaned copy of the components' own source."""
+        return self.components_source if self.project_source == "vessels" else self.project_source

@@ -2339,3 +2339,114 @@ def subtract_slices(cta, ct_hu, *, cta_is_hu=False, median=True, floor=0, ct_ran
     _lib.check(lib.ctg_subtract_slices(_p(cta), _p(ct_hu), b, h, w, int(bool(cta_is_hu)), int(bool(median)), floor, ct_min, ct_max,
                                        float(wc), float(ww), _p(sub), _p(level), _stream()), "ctg_subtract_slices")
     return sub, level
+
+
+# ---------------------------------------------------------------------------- connected components (csrc/components.hip)
+COMPONENTS_TILE = (4, 16, 64)      # (TZ, TY, TX) of csrc/components.hip: CC_TZ, CC_TY, CC_TX -- the tests build their shapes from it
+COMPONENTS_MAX_TOP = 64            # most ranked components: `largest` and the rows of `top`
+COMPONENTS_CONNECTIVITY = (6, 18, 26)
+COMPONENTS_STATS = ("foreground", "components", "candidates", "kept", "kept_voxels", "seeds_missed", "error", "reserved")
+
+
+def _components_array(who, name, t, dtype, count, like):
+    """A flat device array of the components family: `dtype`, contiguous, `count` elements (None: any), on the device of `like`."""
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise RuntimeError("%s: %s: CPU tensors are not supported (no CPU fallback)" % (who, name))
+    if t.dtype != dtype or not t.is_contiguous() or (count is not None and t.numel() != count):
+        raise RuntimeError("%s: %s must be a contiguous %s tensor%s, got %s %s"
+                           % (who, name, dtype, "" if count is None else " of %d elements" % count, t.dtype, tuple(t.shape)))
+    if like is not None and t.device != like.device:
+        raise RuntimeError("%s: %s lives on %s, not on %s" % (who, name, t.device, like.device))
+    return t
+
+
+def _components_int(who, name, v, lo, hi):
+    if isinstance(v, bool) or int(v) != v or not lo <= int(v) <= hi:
+        raise RuntimeError("%s: %s: an integer in %d .. %d expected, got %r" % (who, name, lo, hi, v))
+    return int(v)
+
+
+def components_label(vol, lo, hi=32767, connectivity=26, labels=None, stats=None):
+    """The connected components of the foreground lo <= vol <= hi of an int16 volume (N, H, W) on the GPU (a contiguous view is
+    taken as it is: 2-byte alignment is enough), connectivity 6, 18 or 26 in index space -> (labels int32 (N, H, W), stats int32
+    [8]): labels = -1 on background, otherwise the smallest linear index (z H + y) W + x of the voxel's component; stats[0] = the
+    foreground voxels, stats[6] = the internal-error flag (must read 0), the rest 0 until `components_select`.  `labels` / `stats`
+    may be handed in to be reused.  The result does not depend on the order in which the kernels' atomics land."""
+    lib = _lib.load()
+    who = "components_label"
+    _lines_volume(who, vol)
+    if not vol.is_contiguous():
+        raise RuntimeError("%s: a contiguous volume expected" % who)
+    n, h, w = vol.shape
+    if not (1 <= min(n, h, w) and max(n, h, w) <= REFORMAT_MAX_DIM) or n * h * w > 2 ** 31 - 1:
+        raise RuntimeError("%s: N, H, W in 1 .. %d and at most 2^31 - 1 voxels expected, got %d %d %d" % (who, REFORMAT_MAX_DIM, n, h, w))
+    lo, hi = _components_int(who, "lo", lo, -32768, 32767), _components_int(who, "hi", hi, -32768, 32767)
+    if lo > hi:
+        raise RuntimeError("%s: the threshold band (%d, %d) is empty" % (who, lo, hi))
+    if connectivity not in COMPONENTS_CONNECTIVITY:
+        raise RuntimeError("%s: connectivity %r is not one of %s" % (who, connectivity, COMPONENTS_CONNECTIVITY))
+    with torch.cuda.device(vol.device):
+        labels = torch.empty((n, h, w), dtype=torch.int32, device=vol.device) if labels is None else \
+            _components_array(who, "labels", labels, torch.int32, n * h * w, vol)
+        stats = torch.empty(8, dtype=torch.int32, device=vol.device) if stats is None else \
+            _components_array(who, "stats", stats, torch.int32, 8, vol)
+        _lib.check(lib.ctg_components_label(_p(vol), n, h, w, lo, hi, int(connectivity), _p(labels), _p(stats), _stream()),
+                   "ctg_components_label")
+    return labels, stats
+
+
+def components_select(labels, stats, min_voxels=1, seeds=None, largest=0, ntop=8, sizes=None, keep=None):
+    """Which components of `components_label`'s labels are kept -> (sizes int32, keep uint8, both of labels' shape, top int32
+    [ntop, 2]); `stats` (that call's) gains entries 1 .. 5.  Candidates: the roots with at least `min_voxels` voxels and, where
+    `seeds` (an int32 device tensor [S] of linear indices, or None) is given, holding a seed; ordered by size descending, then
+    root ascending; largest = K > 0 keeps the first K, 0 all of them.  top = (root, size) of the first ntop kept, (-1, 0) beyond
+    them.  `sizes` / `keep` may be handed in to be reused."""
+    lib = _lib.load()
+    who = "components_select"
+    _components_array(who, "labels", labels, torch.int32, None, None)
+    v = labels.numel()
+    if not 1 <= v <= 2 ** 31 - 1:
+        raise RuntimeError("%s: 1 .. 2^31 - 1 voxels expected, got %d" % (who, v))
+    _components_array(who, "stats", stats, torch.int32, 8, labels)
+    min_voxels = _components_int(who, "min_voxels", min_voxels, 1, 2 ** 31 - 1)
+    largest = _components_int(who, "largest", largest, 0, COMPONENTS_MAX_TOP)
+    ntop = _components_int(who, "ntop", ntop, 0, COMPONENTS_MAX_TOP)
+    s = 0
+    if seeds is not None:
+        s = _components_array(who, "seeds", seeds, torch.int32, None, labels).numel()
+    with torch.cuda.device(labels.device):
+        sizes = torch.empty(labels.shape, dtype=torch.int32, device=labels.device) if sizes is None else \
+            _components_array(who, "sizes", sizes, torch.int32, v, labels)
+        keep = torch.empty(labels.shape, dtype=torch.uint8, device=labels.device) if keep is None else \
+            _components_array(who, "keep", keep, torch.uint8, v, labels)
+        top = torch.empty((ntop, 2), dtype=torch.int32, device=labels.device)
+        _lib.check(lib.ctg_components_select(_p(labels), v, min_voxels, _p(seeds) if s else None, s, largest, ntop, _p(sizes),
+                                             _p(keep), _p(top) if ntop else None, _p(stats), _stream()), "ctg_components_select")
+    return sizes, keep, top
+
+
+def components_apply(vol, labels, keep, background=False, fill=None, wc=50.0, ww=400.0, hu=False, want_values=True, want_level=True):
+    """The volume with only the kept components (`components_select`'s keep) -> (values int16, level uint8), each of vol's shape,
+    None for the one not wanted: a voxel of a kept component keeps its value, one of a dropped component gets `fill` (default:
+    air, 0 or -1024 with hu); background keeps its value with background=True (despeckle) and gets `fill` otherwise (mask).
+    level = the 8-bit window level of every value in (wc, ww), as `project_finish` forms it, in the same pass."""
+    lib = _lib.load()
+    who = "components_apply"
+    _lines_volume(who, vol)
+    if not vol.is_contiguous():
+        raise RuntimeError("%s: a contiguous volume expected" % who)
+    v = vol.numel()
+    if not 1 <= v <= 2 ** 31 - 1:
+        raise RuntimeError("%s: 1 .. 2^31 - 1 voxels expected, got %d" % (who, v))
+    _components_array(who, "labels", labels, torch.int32, v, vol)
+    _components_array(who, "keep", keep, torch.uint8, v, vol)
+    if not want_values and not want_level:
+        raise RuntimeError("%s: values, level or both expected" % who)
+    hu = bool(hu)
+    fill = _fill_value(who, fill, hu)
+    with torch.cuda.device(vol.device):
+        values = torch.empty(vol.shape, dtype=torch.int16, device=vol.device) if want_values else None
+        level = torch.empty(vol.shape, dtype=torch.uint8, device=vol.device) if want_level else None
+        _lib.check(lib.ctg_components_apply(_p(vol), _p(labels), _p(keep), v, int(bool(background)), fill, float(wc), float(ww), int(hu),
+                                            _p(values), _p(level), _stream()), "ctg_components_apply")
+    return values, level

@@ -649,6 +649,43 @@ int ctg_render_lines(const short* vol, int N, int H, int W, const int* lines, in
                      const int* light, int zscale, int ambient, int gmin2, unsigned char* rgb, unsigned char* opacity,
                      short* depth, void* stream);
 
+/* ---- series inference, connected components of the volume (added under ABI 15: purely additive, no existing signature or meaning
+ * moves, so the version stays 15): despeckle, keep the K largest components, keep the component a seed voxel lies in -- the cleanup
+ * in front of every projection-type display.  cta_gan_amd/infer.py: VolumeComponents, components_volume, root_voxel,
+ * SeriesTranslator(components=...); ops.components_label, components_select, components_apply.  The reference has no counterpart.
+ * Definitions.  vol = the whole int16 volume [N][H][W] on the device, contiguous, every side in 1 .. 4096 and V = N H W <= 2^31 - 1;
+ *   the linear index of a voxel is i = (z H + y) W + x.  A voxel is foreground when lo <= vol[i] <= hi (lo <= hi, both inside int16;
+ *   the stored values).  Two foreground voxels are adjacent when max(|dz|, |dy|, |dx|) = 1 and |dz| + |dy| + |dx| <= 1, 2, 3 for
+ *   connectivity 6, 18, 26 -- in index space, no aspect -- and a component is a class of the transitive closure.
+ * ctg_components_label: labels int32 [V] = -1 on background, otherwise the smallest linear index of the voxel's component (its
+ *   root).  stats int32 [8] is zeroed, then [0] = the foreground voxels and [6] = the internal-error flag, which must read 0: it is
+ *   set when a union-find walk meets a value that cannot be a parent (every such walk ends at once, inside the array).
+ * ctg_components_select: labels as ctg_components_label left them.  sizes int32 [V]: sizes[r] = the voxels of the component with root
+ *   r, 0 at every index that is no root.  Candidates are the roots with sizes[r] >= min_voxels and, if S > 0 seeds are given, with
+ *   labels[seed] == r for some seed (seeds int32 [S], linear indices; a seed outside 0 .. V - 1 or on background selects nothing
+ *   and is counted).  Candidates are ordered by size descending, then root ascending; largest = K > 0 keeps the first K, largest = 0
+ *   keeps all.  keep uint8 [V] = 1 at kept roots, 0 elsewhere.  top int32 [ntop][2] = (root, size) of the first ntop kept components
+ *   in that order, (-1, 0) beyond the kept count.  sizes and keep are zeroed by the call.  stats [1] = components, [2] = candidates,
+ *   [3] = kept components, [4] = kept voxels, [5] = seeds that selected nothing; [0] and [7] are left alone, [6] is set (never
+ *   cleared) when a label lies outside -1 .. V - 1 -- such a voxel counts as background.  The library keeps the ranking's pass keys
+ *   in device memory of its own, one set per call in rotation: at most 16 calls of ctg_components_select in flight at once.
+ * ctg_components_apply: out[i] = vol[i] where labels[i] >= 0 and keep[labels[i]] == 1; `fill` on foreground voxels whose component
+ *   is dropped; on background vol[i] with background = 1 (despeckle: only dropped islands are erased) and `fill` with background = 0
+ *   (mask: only kept components survive).  level[i] = the 8-bit window level of out[i] + (hu ? 1024 : 0) in (wc, ww), as
+ *   ctg_project_finish writes it, in the same pass.  out int16 [V], level uint8 [V], either may be NULL (not both).
+ * Nothing allocates or synchronises; no workgroup waits for another; exact integer arithmetic, the same bits as numpy
+ *   (tests/components_np.py) whatever the order in which atomics land.
+ * CTG_EINVAL, nothing launched: a null required pointer; N, H or W outside 1 .. 4096 or V outside 1 .. 2^31 - 1; lo > hi or either
+ *   outside int16; connectivity not 6 / 18 / 26; min_voxels < 1; S < 0, or S > 0 with null seeds; largest or ntop outside 0 .. 64, or
+ *   ntop > 0 with null top; fill outside int16; background outside 0 .. 1; vol or out not 2-byte aligned, an int32 array not 4-byte
+ *   aligned. ---- */
+int ctg_components_label(const short* vol, int N, int H, int W, int lo, int hi, int connectivity, int* labels, int* stats,
+                         void* stream);
+int ctg_components_select(const int* labels, long V, int min_voxels, const int* seeds, int S, int largest, int ntop, int* sizes,
+                          unsigned char* keep, int* top, int* stats, void* stream);
+int ctg_components_apply(const short* vol, const int* labels, const unsigned char* keep, long V, int background, int fill, float wc,
+                         float ww, int hu, short* out, unsigned char* level, void* stream);
+
 /* ---- LPIPS (AlexNet, lpips 0.1) of the test() loops (ABI 14): `loss_fn_alex = lpips.LPIPS(net='alex')` (trainer/HdTrainer.py:26-28)
  * and its calls `loss_fn_alex.forward(torch.tensor(c), torch.tensor(b))` on the windowed and on the raw masked pair of every slice
  * (HdTrainer.py:504-513, 531-536, 1029-1031, 1054-1056; the twins in CycTrainer.py, p2pTrainer.py, RegTrainer.py).  The five

@@ -19,6 +19,9 @@
                       [--tumble-dir DIR [--tumble-angles 36] [--tumble-axis x|y|z]]
                       [--cpr-dir DIR --cpr-centreline pts.npy [--cpr-angles A] [--cpr-width U] [--cpr-thick T]]
                       [--reformat-sampling nearest|trilinear]
+                      [--cc-output vessels.npy --cc-threshold LO[,HI] [--cc-level-dir DIR] [--cc-connectivity 6|18|26]
+                       [--cc-min-voxels M] [--cc-largest K] [--cc-seed Z,Y,X ...] [--cc-despeckle] [--cc-source cta|sub]
+                       [--cc-labels labels.npy] [--mip-source vessels]]
 
 --input: int16 [N, H, W] .npy in SimpleITK's convention (what the reference's loaders read from the DICOMs); --weights: the
 reference-format `state_dict` of Model.HdGan.Generator (what train() saves as netG_A2B*.pth).  --output receives the int16
@@ -79,6 +82,18 @@ circle about --tumble-axis x (default: the tumble), y or z through the centre: t
 curved reformat along --cpr-centreline (a .npy of M >= 2 points (z, y, x) in voxels), --cpr-width samples across the vessel,
 --cpr-angles views around it, slabs --cpr-thick voxels deep: cpr_%03d.png.  Each directory also receives reformat.npz with values
 (int16), level (uint8) and, for the rotating kinds, angles (degrees).
+--cc-output: the volume with only the wanted connected components left (int16 [N, H, W] .npy), made on the device after the
+last chunk (cta_gan_amd/infer.py: VolumeComponents).  A voxel is foreground when --cc-threshold LO <= value <= HI (default HI:
+32767; stored values of --cc-source cta, the default, or HU differences of --cc-source sub, which needs --sub-output);
+--cc-connectivity 6, 18 or 26 (default) joins foreground voxels by faces, faces and edges, or all 26 neighbours.  Kept are the
+components of at least --cc-min-voxels voxels, of those only the ones a --cc-seed Z,Y,X (repeatable: the voxel a click on a MIP
+maps to) lies in, of those the --cc-largest K biggest (0: all).  Everything else becomes air; with --cc-despeckle the background
+keeps its values and only the dropped components are erased.  --cc-level-dir: one 8-bit PNG per slice in the source's window;
+--cc-labels: the int32 label volume (-1 on background, otherwise the smallest linear index of the voxel's component).  Next to
+--cc-output, components.npz holds top (int32 [8, 2]: root and size of the biggest kept components, (-1, 0) beyond them), stats
+(int32 [8]) and roots_zyx (the voxel of every root in top, -1 where there is none), and one line reports the components found,
+kept and the voxels kept.  --mip-source vessels makes --mip-dir, --rot-dir, --sts-dir, --vr-dir and the reformats show that
+cleaned volume, in the window of its source.
 DICOM reading and writing are not part of this build.
 """
 import argparse
@@ -154,7 +169,17 @@ def build_parser():
     parser.add_argument("--sub-ct-max", type=int, default=None, help="pixels whose input HU is above this become 0")
     parser.add_argument("--sub-wc", type=float, default=150.0, help="window centre of the subtraction's 8-bit level")
     parser.add_argument("--sub-ww", type=float, default=300.0, help="window width of the subtraction's 8-bit level")
-    parser.add_argument("--mip-source", choices=["cta", "sub"], default="cta", help="what --mip-dir / --rot-dir project")
+    parser.add_argument("--mip-source", choices=["cta", "sub", "vessels"], default="cta", help="what --mip-dir / --rot-dir project")
+    parser.add_argument("--cc-output", type=str, default=None, help="also write the volume with only the kept components here")
+    parser.add_argument("--cc-level-dir", type=str, default=None, help="one 8-bit PNG per slice of it (with --cc-output)")
+    parser.add_argument("--cc-threshold", type=str, default=None, help="LO or LO,HI: the foreground band (with --cc-output; a negative LO as --cc-threshold=-5,300)")
+    parser.add_argument("--cc-connectivity", type=int, choices=[6, 18, 26], default=26, help="which neighbours join (with --cc-output)")
+    parser.add_argument("--cc-min-voxels", type=int, default=1, help="drop components smaller than this (with --cc-output)")
+    parser.add_argument("--cc-largest", type=int, default=0, help="keep only the K biggest components, 0: all (with --cc-output)")
+    parser.add_argument("--cc-seed", type=str, action="append", default=None, help="Z,Y,X: keep the component of this voxel (repeatable)")
+    parser.add_argument("--cc-despeckle", action="store_true", help="keep the background, erase only the dropped components")
+    parser.add_argument("--cc-source", choices=["cta", "sub"], default=None, help="the volume the components are taken from")
+    parser.add_argument("--cc-labels", type=str, default=None, help="also write the int32 label volume here (with --cc-output)")
     parser.add_argument("--dtype", choices=DTYPES, default=None, help="compute mode (default %s, as train.py)" % DEFAULT_DTYPE)
     return parser
 
@@ -193,10 +218,44 @@ def sts_options(parser, opts):
     return {"thick": {a: thick[a] for a in axes}, "step": {a: step[a] for a in axes}, "mode": opts.mip_mode, "axes": axes}
 
 
+def cc_options(parser, opts):
+    """The `SeriesTranslator(components=...)` dict of --cc-output (None without it); bad values end in parser.error."""
+    if opts.cc_output is None:
+        if (opts.cc_threshold is not None or opts.cc_level_dir is not None or opts.cc_seed is not None or opts.cc_labels is not None
+                or opts.cc_source is not None or opts.cc_despeckle or opts.mip_source == "vessels"):
+            parser.error("the --cc options and --mip-source vessels need --cc-output")
+        return None
+    if opts.cc_threshold is None:
+        parser.error("--cc-output needs --cc-threshold")
+    try:
+        band = [int(v) for v in opts.cc_threshold.split(",")]
+    except ValueError:
+        parser.error("--cc-threshold: whole numbers LO or LO,HI expected, got %r" % opts.cc_threshold)
+    band = band + [32767] if len(band) == 1 else band
+    if len(band) != 2 or not -32768 <= band[0] <= band[1] <= 32767:
+        parser.error("--cc-threshold: -32768 <= LO <= HI <= 32767 expected, got %r" % opts.cc_threshold)
+    if opts.cc_min_voxels < 1 or not 0 <= opts.cc_largest <= 64:
+        parser.error("--cc-min-voxels: at least 1 and --cc-largest: 0 .. 64 expected")
+    seeds = None
+    if opts.cc_seed is not None:
+        try:
+            seeds = [tuple(int(v) for v in text.split(",")) for text in opts.cc_seed]
+        except ValueError:
+            parser.error("--cc-seed: whole numbers Z,Y,X expected, got %r" % (opts.cc_seed,))
+        if any(len(p) != 3 or min(p) < 0 for p in seeds):
+            parser.error("--cc-seed: three whole numbers Z,Y,X >= 0 expected, got %r" % (opts.cc_seed,))
+    if opts.cc_source == "sub" and opts.sub_output is None:
+        parser.error("--cc-source sub needs --sub-output")
+    return {"threshold": tuple(band), "connectivity": opts.cc_connectivity, "min_voxels": opts.cc_min_voxels,
+            "largest": opts.cc_largest, "seeds": seeds, "background": opts.cc_despeckle, "level": opts.cc_level_dir is not None,
+            "labels": opts.cc_labels is not None, "top": 8}
+
+
 def parse_args(argv=None):
     parser = build_parser()
     opts = parser.parse_args(argv)
     opts.sts = sts_options(parser, opts)
+    opts.cc = cc_options(parser, opts)
     if opts.sub_output is None and (opts.mip_source == "sub" or opts.sub_level_dir is not None):
         parser.error("--mip-source sub and --sub-level-dir need --sub-output")
     if opts.sub_ct_min is not None and opts.sub_ct_max is not None and opts.sub_ct_min > opts.sub_ct_max:
@@ -322,7 +381,8 @@ def main(argv=None):
                                  render=view_angles(opts.vr_angles, opts.vr_span) if opts.vr_dir is not None else None,
                                  render_options=vr_options, reformat=reformat,
                                  reformat_options={"mode": opts.mip_mode, "sampling": opts.reformat_sampling} if reformat else None,
-                                 render3d=None if vr3d is None else {"vr3d": vr3d}, render3d_options=vr3d_options)
+                                 render3d=None if vr3d is None else {"vr3d": vr3d}, render3d_options=vr3d_options,
+                                 components=opts.cc, components_source=opts.cc_source)
     shown = "cued" if opts.depth_cue > 0 else "level"      # the plane the PNGs of the projections are written from
     out = translate(volume)
     np.save(opts.output, out["pix"])
@@ -339,6 +399,25 @@ def main(argv=None):
             for i, plane in enumerate(out["sub_level"]):
                 Image.fromarray(plane).save(os.path.join(opts.sub_level_dir, "%06d.png" % i))
         print("wrote the subtraction volume to %s" % opts.sub_output, flush=True)
+    if opts.cc_output is not None:
+        from cta_gan_amd.infer import root_voxel
+        ves = out["vessels"]
+        np.save(opts.cc_output, ves["values"])
+        if opts.cc_labels is not None:
+            np.save(opts.cc_labels, ves["labels"])
+        if opts.cc_level_dir is not None:
+            from PIL import Image
+            os.makedirs(opts.cc_level_dir, exist_ok=True)
+            for i, plane in enumerate(ves["level"]):
+                Image.fromarray(plane).save(os.path.join(opts.cc_level_dir, "%06d.png" % i))
+        roots = np.full((len(ves["top"]), 3), -1, dtype=np.int64)
+        found = ves["top"][:, 0] >= 0
+        if found.any():
+            roots[found] = np.stack(root_voxel(ves["top"][found, 0], volume.shape[1], volume.shape[2]), axis=1)
+        np.savez(os.path.join(os.path.dirname(os.path.abspath(opts.cc_output)), "components.npz"), top=ves["top"], stats=ves["stats"],
+                 roots_zyx=roots)
+        print("components: %d found, %d kept, %d voxels kept (wrote %s)" % (ves["stats"][1], ves["stats"][3], ves["stats"][4],
+                                                                            opts.cc_output), flush=True)
     if opts.mip_dir is not None:
         from PIL import Image
         from cta_gan_amd.infer import aspect_rows

@@ -96,6 +96,11 @@ SIGNATURES = {
     "ctg_components_label": "piiiiiippp",
     "ctg_components_select": "plipiiippppp",
     "ctg_components_apply": "pppliiffippp",
+    "ctg_centreline_clearance": "piiiiiiippp",
+    "ctg_centreline_seed": "piiilpppipp",
+    "ctg_centreline_relax": "piiipiiiiiipppiiipp",
+    "ctg_centreline_saturated": "plpp",
+    "ctg_centreline_trace": "piiipiiiiiippiipppp",
     "ctg_window_pairs": "ppppilipp",
     "ctg_maxpool3s2_fwd": "pipiiiiip",
     "ctg_lpips_layer": "pipiliippp",

@@ -144,9 +144,11 @@ def _check_depth(who, depth, cue, mode):
 
 
 def _tree_to(tree, conv):
-    """A result tree -- a dict of tensors, Nones and nested dicts -- with `conv` applied to every tensor."""
+    """A result tree -- a dict of tensors, Nones and nested dicts or lists -- with `conv` applied to every tensor."""
     if isinstance(tree, dict):
         return {k: _tree_to(v, conv) for k, v in tree.items()}
+    if isinstance(tree, list):
+        return [_tree_to(v, conv) for v in tree]
     return None if tree is None else conv(tree)
 
 
@@ -154,6 +156,8 @@ def _tree_leaves(tree, path=()):
     """[(path, tensor), ...]: the tensors of a result tree in its own order, each with the keys that lead to it."""
     if isinstance(tree, dict):
         return [leaf for k, v in tree.items() for leaf in _tree_leaves(v, path + (k,))]
+    if isinstance(tree, list):
+        return [leaf for k, v in enumerate(tree) for leaf in _tree_leaves(v, path + (k,))]
     return [] if tree is None else [(path, tree)]
 
 
@@ -1213,6 +1217,198 @@ def components_volume(volume, threshold, batch=64, device=None, **options):
     return out
 
 
+CENTRELINE_OPTIONS = ("threshold", "start", "ends", "radius", "aspect", "penalty", "max_points", "smooth", "cpr", "clearance",
+                      "rounds_per_call", "max_rounds", "fill", "wc", "ww", "hu", "level")
+CPR_OPTIONS = ("angles", "cols", "depth", "pitch", "sampling", "mode")
+
+
+def centreline_penalty(radius, far=1, near=64):
+    """The penalty table of `VolumeCentreline`, uint16 [radius^2 + 1], indexed by the capped squared clearance c: floor(far + (near -
+    far) (1 - sqrt(c) / radius)^2 + 0.5), so a voxel `radius` or more from the wall costs `far` per unit step and one at the wall
+    close to `near`; entry 0 (background, never read) = near.  far and near are integers in 1 .. 4095.  The defaults are a first
+    guess, as the transfer presets were: not tuned on patient data."""
+    r = int(radius)
+    if isinstance(radius, bool) or r != radius or not 1 <= r <= ops.CENTRELINE_MAX_RADIUS:
+        raise ValueError("centreline_penalty: radius: an integer in 1 .. %d expected, got %r" % (ops.CENTRELINE_MAX_RADIUS, radius))
+    for name, v in (("far", far), ("near", near)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= v <= 4095:
+            raise ValueError("centreline_penalty: %s: an integer in 1 .. 4095 expected, got %r" % (name, v))
+    c = np.arange(r * r + 1, dtype=np.float64)
+    pen = np.floor(far + (near - far) * (1.0 - np.sqrt(c) / r) ** 2 + 0.5)
+    pen[0] = near
+    return np.clip(pen, 1, 4095).astype(np.uint16)
+
+
+def _centreline_aspect(who, aspect):
+    """-> (aspect, zq = floor(256 aspect^2 + 0.5), which must lie in 16 .. 65535)."""
+    aspect = float(aspect)
+    if not (aspect > 0 and math.isfinite(aspect)) or not 16 <= math.floor(256.0 * aspect * aspect + 0.5) <= 65535:
+        raise ValueError("%s: aspect: a ratio with floor(256 aspect^2 + 0.5) in 16 .. 65535 expected, got %r" % (who, aspect))
+    return aspect, int(math.floor(256.0 * aspect * aspect + 0.5))
+
+
+def centreline_steps(aspect=1.0):
+    """The five step lengths of a move to a 26-neighbour, floor(10 sqrt(k + aspect^2 dz^2) + 0.5) for k in-plane axes: in-plane
+    face, in-plane edge, z alone, z + one in-plane, z + two in-plane -- (10, 14, 10, 14, 17) at aspect 1.  Each must fit 1 .. 255."""
+    aspect, _ = _centreline_aspect("centreline_steps", aspect)
+    steps = tuple(int(math.floor(10.0 * math.sqrt(k + aspect * aspect * dz) + 0.5)) for k, dz in ((1, 0), (2, 0), (0, 1), (1, 1), (2, 1)))
+    if not all(1 <= s <= 255 for s in steps):
+        raise ValueError("centreline_steps: aspect %r gives step lengths %r outside 1 .. 255" % (aspect, steps))
+    return steps
+
+
+def smooth_centreline(points, window=5):
+    """A centred moving average over `window` (odd, >= 1) points of a path float [M, 3], the end points repeated beyond the ends;
+    float64, on the host.  The voxel path of a trace is a staircase, and `curved_lines` takes its tangents by central differences."""
+    pts = np.asarray(points, dtype=np.float64)
+    if pts.ndim != 2 or pts.shape[1] != 3 or pts.shape[0] < 1:
+        raise ValueError("smooth_centreline: points [M >= 1, 3] expected, got an array of shape %s" % (pts.shape,))
+    if isinstance(window, bool) or not isinstance(window, (int, np.integer)) or window < 1 or window % 2 != 1:
+        raise ValueError("smooth_centreline: window: an odd integer >= 1 expected, got %r" % (window,))
+    half = int(window) // 2
+    padded = np.concatenate([np.repeat(pts[:1], half, axis=0), pts, np.repeat(pts[-1:], half, axis=0)])
+    total = np.cumsum(np.concatenate([np.zeros((1, 3)), padded]), axis=0)
+    return (total[int(window):] - total[:-int(window)]) / float(window)
+
+
+class VolumeCentreline(_ResidentVolume):
+    """The vessel centreline from a start voxel to each of up to 64 end voxels of an int16 volume [n, h, w] that arrives in chunks
+    and stays on the device (`ops.centreline_clearance` / `centreline_field` / `centreline_trace`, csrc/centreline.hip): the
+    cheapest 26-connected path through the foreground when a move into a voxel costs its length times a penalty that falls with
+    the voxel's distance from the vessel wall -- the path `curved_lines` wants.  threshold: lo, or (lo, hi), as `VolumeComponents`;
+    start and ends: (z, y, x) voxels, e.g. from `ray_voxel` / `line_voxel` (a click is not snapped to the vessel: it must lie on
+    foreground); radius R in 1 .. 32 caps the clearance (in pixels); aspect = slice spacing / pixel spacing scales z in the
+    clearance and the step lengths (`centreline_steps`); penalty: a uint16 table [R^2 + 1] (default `centreline_penalty(R)`);
+    max_points: the longest path in voxels (default 4 (n + h + w)); smooth: the window of `smooth_centreline`.  cpr = a dict with
+    any of angles, cols, depth, pitch (as `curved_lines`), sampling, mode (as `VolumeReformatter`) adds the curved reformat along
+    every end's smoothed path, one `ops.reformat_lines` launch per end on the resident volume, in the window (wc, ww) / `hu`.
+    `update(pix_chunk, n0)` copies a chunk in, in any order; `result()` raises unless every slice has arrived exactly once since
+    the last `reset()` -> {"paths": int32 [E, max_points] (linear indices, end first, -1 beyond the count), "counts": int32 [E],
+    "points": a list of float64 [M, 3] (z, y, x), start to end, smoothed, "clearance": uint16 [n, h, w] (clearance=True) or None,
+    "stats": int32 [8] (`ops.CENTRELINE_STATS`), and with cpr "cpr": [{"values": int16 [A, rows, cols], "level": uint8 or None}]} on
+    the device.  It reads the counts on the host (one synchronisation beyond those of the relaxation) and raises ValueError for a
+    start on background, an end on background or in another component, or a path longer than max_points, and RuntimeError when the
+    field saturated or the error flag is set.  `.nbytes`: the device memory held (the volume, the scratch and the clearance at 2
+    bytes per voxel, the field at 4, the tables) plus paths and counts, known before the first chunk; the cpr planes are not in
+    it (their rows follow the length of the path).  Exact integer arithmetic on the current stream up to the path; the smoothing
+    is float64 on the host."""
+
+    def __init__(self, n, h, w, threshold, start, ends, radius=8, aspect=1.0, penalty=None, max_points=None, smooth=5, cpr=None,
+                 clearance=False, rounds_per_call=16, max_rounds=4096, fill=None, wc=50.0, ww=400.0, hu=False, level=True, device=None):
+        who = "VolumeCentreline"
+        self._sides(who, n, h, w)
+        v = self.n * self.h * self.w
+        if v > 2 ** 31 - 1:
+            raise ValueError("%s: at most 2^31 - 1 voxels expected, got %d x %d x %d" % (who, self.n, self.h, self.w))
+        band = tuple(threshold) if isinstance(threshold, (tuple, list)) else (threshold, 32767)
+        if len(band) != 2 or any(isinstance(t, bool) or not isinstance(t, (int, np.integer)) for t in band):
+            raise ValueError("%s: threshold: an integer lo or a pair (lo, hi) expected, got %r" % (who, threshold))
+        self.lo, self.hi = int(band[0]), int(band[1])
+        if not -32768 <= self.lo <= self.hi <= 32767:
+            raise ValueError("%s: threshold: -32768 <= lo <= hi <= 32767 expected, got %r" % (who, threshold))
+        pts = np.asarray([tuple(start)] + [tuple(e) for e in ends])
+        if pts.ndim != 2 or pts.shape[1] != 3 or pts.dtype.kind not in "iu" or not 2 <= len(pts) <= 1 + ops.CENTRELINE_MAX_ENDS:
+            raise ValueError("%s: start: an integer (z, y, x), ends: 1 .. %d of them expected, got %r, %r"
+                             % (who, ops.CENTRELINE_MAX_ENDS, start, ends))
+        pts = pts.astype(np.int64)
+        if (pts < 0).any() or (pts >= np.array([self.n, self.h, self.w])).any():
+            raise ValueError("%s: the start or an end lies outside the volume (%d, %d, %d)" % (who, self.n, self.h, self.w))
+        index = (pts[:, 0] * self.h + pts[:, 1]) * self.w + pts[:, 2]
+        self.start, self.ends_host = int(index[0]), index[1:].astype(np.int32)
+        for name, t, lo_, hi_ in (("radius", radius, 1, ops.CENTRELINE_MAX_RADIUS), ("rounds_per_call", rounds_per_call, 1, ops.CENTRELINE_MAX_ROUNDS),
+                                  ("max_rounds", max_rounds, 1, ops.CENTRELINE_MAX_ROUNDS)):
+            if isinstance(t, bool) or not isinstance(t, (int, np.integer)) or not lo_ <= t <= hi_:
+                raise ValueError("%s: %s: an integer in %d .. %d expected, got %r" % (who, name, lo_, hi_, t))
+        self.radius, self.rounds_per_call, self.max_rounds = int(radius), int(rounds_per_call), int(max_rounds)
+        self.aspect, self.zq = _centreline_aspect(who, aspect)
+        self.steps = centreline_steps(self.aspect)
+        pen = centreline_penalty(self.radius) if penalty is None else np.asarray(penalty)
+        if pen.shape != (self.radius ** 2 + 1,) or pen.dtype.kind not in "iu" or (pen[1:] < 1).any() or (pen[1:] > 4095).any():
+            raise ValueError("%s: penalty: %d integers in 1 .. 4095 expected" % (who, self.radius ** 2 + 1))
+        self.pen_host = np.clip(pen, 1, 4095).astype(np.uint16)
+        max_points = min(v, 4 * (self.n + self.h + self.w), ops.CENTRELINE_MAX_POINTS) if max_points is None else max_points
+        if isinstance(max_points, bool) or not isinstance(max_points, (int, np.integer)) or not 1 <= max_points <= ops.CENTRELINE_MAX_POINTS:
+            raise ValueError("%s: max_points: an integer in 1 .. %d expected, got %r" % (who, ops.CENTRELINE_MAX_POINTS, max_points))
+        self.max_points = int(max_points)
+        smooth_centreline(np.zeros((1, 3)), smooth)
+        self.smooth = int(smooth)
+        self.cpr = None
+        if cpr is not None:
+            if not isinstance(cpr, dict) or set(cpr) - set(CPR_OPTIONS):
+                raise ValueError("%s: cpr %r: a dict with any of %s expected" % (who, cpr, CPR_OPTIONS))
+            self.cpr = {"angles": (0.0,), "cols": 65, "depth": 1, "pitch": 1.0, "sampling": "trilinear", "mode": "max", **cpr}
+            if self.cpr["mode"] not in PROJECTIONS or self.cpr["sampling"] not in REFORMAT_SAMPLINGS:
+                raise ValueError("%s: cpr: mode one of %s and sampling one of %s expected" % (who, PROJECTIONS, REFORMAT_SAMPLINGS))
+            curved_lines(self.n, self.h, self.w, np.array([[0.0, 0.0, 0.0], [0.0, 0.0, 1.0]]), aspect=self.aspect,
+                         **{k: self.cpr[k] for k in ("angles", "cols", "depth", "pitch")})      # (the options, checked now)
+        self.want_clearance = bool(clearance)
+        self.hu, self.window, self.want_level = bool(hu), (float(wc), float(ww)), bool(level)
+        self.fill = (-1024 if self.hu else 0) if fill is None else int(fill)
+        tz, ty, tx = ops.CENTRELINE_TILE
+        tiles = -(-self.n // tz) * -(-self.h // ty) * -(-self.w // tx)
+        e = len(self.ends_host)
+        self.nbytes = (2 + 2 + 2 + 4) * v + self.pen_host.nbytes + 4 * e + 8 * tiles + 4 * self.max_rounds + 4 * e * (self.max_points + 1) + 32
+        self._resident(device)
+        self.pen = self.ends = self._scratch = self._clear = self._dist = None      # on the device from the first chunk / result on
+
+    def _upload(self):
+        self.pen = torch.from_numpy(self.pen_host.view(np.int16)).to(self.device).view(torch.uint16)
+        self.ends = torch.from_numpy(self.ends_host).to(self.device)
+
+    def result(self):
+        who = "VolumeCentreline"
+        self._whole()
+        # a clearance the caller asked for is theirs: a fresh array per result; otherwise the working arrays are kept between calls
+        if self._scratch is None:
+            self._scratch = torch.empty((self.n, self.h, self.w), dtype=torch.uint16, device=self.device)
+        clear = ops.centreline_clearance(self.volume, self.lo, self.hi, self.radius, self.zq, scratch=self._scratch,
+                                         clear=None if self.want_clearance else self._clear)
+        if not self.want_clearance:
+            self._clear = clear
+        self._dist, stats = ops.centreline_field(clear, self.pen, self.steps, self.start, self.radius, rounds_per_call=self.rounds_per_call,
+                                                 max_rounds=self.max_rounds, dist=self._dist)
+        paths, counts = ops.centreline_trace(clear, self.pen, self.steps, self._dist, self.ends, self.radius, self.max_points, stats=stats)
+        found, flags = counts.cpu().numpy(), stats.cpu().numpy()      # (the synchronisation: the points are made on the host)
+        if flags[0] != 0:
+            raise ValueError("%s: the start lies on background (threshold %d .. %d): a click is not snapped to the vessel" % (who, self.lo, self.hi))
+        if flags[3] != 0 or flags[6] != 0:
+            raise RuntimeError("%s: the cost field %s: the paths are not to be trusted"
+                               % (who, "saturated (stats[3])" if flags[3] != 0 else "does not explain itself (stats[6])"))
+        if (found == 0).any():
+            raise ValueError("%s: %d of %d ends lie on background or in another component than the start" % (who, int((found == 0).sum()), len(found)))
+        if (found < 0).any():
+            raise ValueError("%s: a path is longer than max_points = %d voxels" % (who, self.max_points))
+        points = []
+        for e, m in enumerate(found.tolist()):
+            i = paths[e, :m].cpu().numpy()[::-1].astype(np.int64)
+            points.append(smooth_centreline(np.stack([i // (self.h * self.w), (i // self.w) % self.h, i % self.w], axis=1), self.smooth))
+        out = {"paths": paths, "counts": counts, "points": [torch.from_numpy(p).to(self.device) for p in points],
+               "clearance": clear if self.want_clearance else None, "stats": stats}
+        if self.cpr is not None:
+            out["cpr"] = []
+            for p in points:
+                if len(p) < 2:
+                    raise ValueError("%s: cpr: an end is the start itself: there is no line to reformat along" % who)
+                lines = curved_lines(self.n, self.h, self.w, p, aspect=self.aspect, **{k: self.cpr[k] for k in ("angles", "cols", "depth", "pitch")})
+                table = ops.LineTable(lines[0], lines.cols, lines[1], self.device)
+                values, level = ops.reformat_lines(self.volume, table, table.u, table.t, self.cpr["mode"], fill=self.fill, wc=self.window[0],
+                                                   ww=self.window[1], hu=self.hu, sampling=self.cpr["sampling"], want_level=self.want_level)
+                out["cpr"].append({"values": values, "level": level})
+        return out
+
+
+def centreline_volume(volume, threshold, start, ends, batch=64, device=None, **options):
+    """The centreline view of a volume that already exists, the twin of `components_volume`: int16 [N, H, W], a host array / CPU
+    tensor (chunks of `batch` slices cross PCIe one after another) or a device tensor; threshold, start, ends and the options as
+    `VolumeCentreline`.  Returns what `VolumeCentreline.result` returns, of the input's kind."""
+    def make(n, h, w, dev):      # (the device is resolved here: the chunk loop runs under it)
+        return VolumeCentreline(n, h, w, threshold, start, ends, device=torch.device("cuda", torch.cuda.current_device()) if dev is None else dev,
+                                **options)
+
+    # host chunks go to `update` as they are: it copies them into the resident volume, the only time they cross PCIe
+    return _view_of_volume("centreline_volume", volume, batch, device, make, upload=False)
+
+
 def subtract_volume(cta, ct_hu, cta_is_hu=False, median=True, floor=0, ct_range=(None, None), wc=150.0, ww=300.0, level=True,
                     batch=64, device=None):
     """The subtraction of two volumes that already exist (a real CTA and its registered CT for a side-by-side view, or a
@@ -1311,6 +1507,13 @@ class SeriesTranslator:
     display show that cleaned volume: the chunk loop then feeds only the components view, and the cleaned volume is handed to the
     other displays after the last chunk, device to device, in chunks of `batch` slices.  With components=None nothing of it is
     allocated or launched.
+    centreline = a dict of `VolumeCentreline` keyword arguments (threshold, start, ends, and any of radius, aspect, penalty,
+    max_points, smooth, cpr, clearance, rounds_per_call, max_rounds, fill, wc, ww, hu, level) adds "centreline": {"paths", "counts",
+    "points": a list of float64 [M, 3], "clearance", "stats", and with cpr "cpr": [{"values", "level"}]}, the vessel centreline
+    from `start` to every end through the same source as the other displays (`project_source`; with "vessels" the cleaned volume,
+    handed over device to device), traced after the last chunk and copied back once.  It keeps the source volume on the device
+    (`VolumeCentreline.nbytes`) and waits for the relaxation on the host.  With centreline=None nothing of it is allocated or
+    launched.
 
     size: the side(s) the generator runs at (None: the volume's own); a volume of another size is resized (nearest) on the way
     in and comes back at its own size.  wc / ww: the window of the 8-bit level; hu: pixels minus 1024 (SimpleITK) instead of
@@ -1321,9 +1524,14 @@ class SeriesTranslator:
                  slab=None, rotate=None, rotate_mode=None, subtract=False, sub_median=True, sub_floor=0, sub_ct_range=(None, None),
                  sub_window=(150.0, 300.0), project_source="cta", slabs=None, rotate_sampling="nearest", rotate_oversample=1,
                  depth=False, depth_cue=0, render=None, render_options=None, reformat=None, reformat_options=None, render3d=None,
-                 render3d_options=None, components=None, components_source=None):
+                 render3d_options=None, components=None, components_source=None, centreline=None):
         if int(batch) < 1:
             raise ValueError("SeriesTranslator: batch >= 1 expected")
+        self.centreline = None if centreline is None else dict(centreline)
+        if self.centreline is not None and (not {"threshold", "start", "ends"} <= set(self.centreline)
+                                            or set(self.centreline) - set(CENTRELINE_OPTIONS)):
+            raise ValueError("SeriesTranslator: centreline %r: a dict with 'threshold', 'start', 'ends' and any of %s expected"
+                             % (centreline, CENTRELINE_OPTIONS))
         self.components = None if components is None else dict(components)
         if self.components is None and components_source is not None:
             raise ValueError("SeriesTranslator: components_source needs components")
@@ -1443,6 +1651,10 @@ class SeriesTranslator:
                 lambda n, h, w: VolumeComponents(n, h, w, device=self.device,
                                                  **{"wc": wc_, "ww": ww_, "hu": True if sub else self.hu, **self.components}),
                 VolumeComponents.result, False)
+        if self.centreline is not None:
+            self._displays["centreline"] = (
+                lambda n, h, w: VolumeCentreline(n, h, w, device=self.device, **{**self._view_options(), **self.centreline}),
+                VolumeCentreline.result, False)
         self._views, self._view_host = {}, {}      # by output key: the view, the page-locked copy of its result
         # host seconds of the last call (scripts/export_bench.py): waiting to get a slot back, copying into the input slots,
         # copying out of the output slots, the whole call

@@ -2450,3 +2450,134 @@ def components_apply(vol, labels, keep, background=False, fill=None, wc=50.0, ww
         _lib.check(lib.ctg_components_apply(_p(vol), _p(labels), _p(keep), v, int(bool(background)), fill, float(wc), float(ww), int(hu),
                                             _p(values), _p(level), _stream()), "ctg_components_apply")
     return values, level
+
+
+# ---------------------------------------------------------------------------- vessel centreline (csrc/centreline.hip)
+CENTRELINE_TILE = (8, 16, 32)      # (TZ, TY, TX) of csrc/centreline.hip: CL_TZ, CL_TY, CL_TX -- the tests build their shapes from it
+CENTRELINE_MAX_RADIUS = 32
+CENTRELINE_MAX_ENDS = 64
+CENTRELINE_MAX_ROUNDS = 1 << 20
+CENTRELINE_MAX_POINTS = 1 << 24
+CENTRELINE_UNREACHED = 0xFFFFFFFF
+CENTRELINE_SAT = 0xFFFFFFFE
+CENTRELINE_STATS = ("start_missed", "ends_missed", "ends_overflowed", "saturated", "ends_stuck", "reserved", "error", "reserved")
+
+
+def _centreline_sides(who, t):
+    if t.dim() != 3:
+        raise RuntimeError("%s: a volume (N, H, W) expected, got %s" % (who, tuple(t.shape)))
+    n, h, w = t.shape
+    if not (1 <= min(n, h, w) and max(n, h, w) <= REFORMAT_MAX_DIM) or n * h * w > 2 ** 31 - 1:
+        raise RuntimeError("%s: N, H, W in 1 .. %d and at most 2^31 - 1 voxels expected, got %d %d %d" % (who, REFORMAT_MAX_DIM, n, h, w))
+    return n, h, w
+
+
+def _centreline_cost(who, clear, pen, steps, radius):
+    """The checks the field and the trace share -> (n, h, w, R, the five step lengths)."""
+    _components_array(who, "clear", clear, torch.uint16, None, None)
+    n, h, w = _centreline_sides(who, clear)
+    radius = _components_int(who, "radius", radius, 1, CENTRELINE_MAX_RADIUS)
+    _components_array(who, "pen", pen, torch.uint16, radius * radius + 1, clear)
+    steps = tuple(steps)
+    if len(steps) != 5:
+        raise RuntimeError("%s: steps: five step lengths expected, got %r" % (who, steps))
+    return n, h, w, radius, tuple(_components_int(who, "steps", s, 1, 255) for s in steps)
+
+
+def centreline_clearance(vol, lo, hi=32767, radius=8, zq=256, scratch=None, clear=None):
+    """The capped squared clearance of the foreground lo <= vol <= hi of an int16 volume (N, H, W) on the GPU (a contiguous view is
+    taken as it is) -> clear uint16 (N, H, W): 0 on background, on a foreground voxel min(R^2, the smallest dx^2 + dy^2 + q(|dz|) to a
+    background voxel inside the volume), q(d) = (d^2 zq + 128) >> 8, zq = floor(256 aspect^2 + 0.5) in 16 .. 65535, R = radius in
+    1 .. 32.  Three launches; `scratch` / `clear` (uint16, V elements each) may be handed in to be reused."""
+    lib = _lib.load()
+    who = "centreline_clearance"
+    _lines_volume(who, vol)
+    if not vol.is_contiguous():
+        raise RuntimeError("%s: a contiguous volume expected" % who)
+    n, h, w = _centreline_sides(who, vol)
+    lo, hi = _components_int(who, "lo", lo, -32768, 32767), _components_int(who, "hi", hi, -32768, 32767)
+    if lo > hi:
+        raise RuntimeError("%s: the threshold band (%d, %d) is empty" % (who, lo, hi))
+    radius = _components_int(who, "radius", radius, 1, CENTRELINE_MAX_RADIUS)
+    zq = _components_int(who, "zq", zq, 16, 65535)
+    with torch.cuda.device(vol.device):
+        scratch = torch.empty((n, h, w), dtype=torch.uint16, device=vol.device) if scratch is None else \
+            _components_array(who, "scratch", scratch, torch.uint16, n * h * w, vol)
+        clear = torch.empty((n, h, w), dtype=torch.uint16, device=vol.device) if clear is None else \
+            _components_array(who, "clear", clear, torch.uint16, n * h * w, vol)
+        if scratch.data_ptr() == clear.data_ptr():
+            raise RuntimeError("%s: scratch and clear must be two arrays" % who)
+        _lib.check(lib.ctg_centreline_clearance(_p(vol), n, h, w, lo, hi, radius, zq, _p(scratch), _p(clear), _stream()),
+                   "ctg_centreline_clearance")
+    return clear
+
+
+def centreline_field(clear, pen, steps, start, radius, rounds_per_call=16, max_rounds=4096, dist=None):
+    """The cost of the cheapest path from voxel `start` (a linear index) to every voxel of its component -> (dist uint32 (N, H, W),
+    stats int32 [8]): 0xFFFFFFFF = unreached, dist[start] = 0, a move into voxel v costs steps[kind] * pen[clear[v]] (pen uint16
+    [radius^2 + 1] on the device, read clamped into 1 .. 4095; steps: five lengths in 1 .. 255), sums saturate at 0xFFFFFFFE
+    (stats[3] = 1 then).  A start outside the volume or on background reaches nothing and sets stats[0].  The relaxation runs in
+    rounds of one launch each, `rounds_per_call` to a batch; after each batch the host reads whether the last round still marked
+    a tile -- one synchronisation per batch, so this runs outside a captured graph -- and RuntimeError is raised when `max_rounds`
+    rounds have not reached the fixed point (`centreline_field.rounds`: the rounds the last call launched).  The field does not
+    depend on the order in which anything lands."""
+    lib = _lib.load()
+    who = "centreline_field"
+    n, h, w, radius, steps = _centreline_cost(who, clear, pen, steps, radius)
+    v = n * h * w
+    if isinstance(start, bool) or int(start) != start or not -2 ** 62 <= int(start) < 2 ** 62:
+        raise RuntimeError("%s: start: a linear voxel index expected, got %r" % (who, start))
+    rounds_per_call = _components_int(who, "rounds_per_call", rounds_per_call, 1, CENTRELINE_MAX_ROUNDS)
+    max_rounds = _components_int(who, "max_rounds", max_rounds, 1, CENTRELINE_MAX_ROUNDS)
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("%s: runs outside a captured graph (it reads the rounds' marks on the host)" % who)
+    tz, ty, tx = CENTRELINE_TILE
+    tiles = -(-n // tz) * -(-h // ty) * -(-w // tx)
+    dev = clear.device
+    with torch.cuda.device(dev):
+        dist = torch.empty((n, h, w), dtype=torch.uint32, device=dev) if dist is None else \
+            _components_array(who, "dist", dist, torch.uint32, v, clear)
+        active = torch.empty(2 * tiles, dtype=torch.int32, device=dev)
+        marks = torch.empty(max_rounds, dtype=torch.int32, device=dev)
+        stats = torch.empty(8, dtype=torch.int32, device=dev)
+        _lib.check(lib.ctg_centreline_seed(_p(clear), n, h, w, int(start), _p(dist), _p(active), _p(marks), max_rounds, _p(stats),
+                                           _stream()), "ctg_centreline_seed")
+        done, converged = 0, False
+        while done < max_rounds and not converged:
+            k = min(rounds_per_call, max_rounds - done)
+            _lib.check(lib.ctg_centreline_relax(_p(clear), n, h, w, _p(pen), radius, *steps, _p(dist), _p(active), _p(marks), max_rounds,
+                                                done, k, _p(stats), _stream()), "ctg_centreline_relax")
+            done += k
+            converged = int(marks[done - 1].item()) == 0      # the one synchronisation of the batch
+        centreline_field.rounds = done
+        if not converged:
+            raise RuntimeError("%s: %d rounds have not reached the fixed point (max_rounds)" % (who, max_rounds))
+        _lib.check(lib.ctg_centreline_saturated(_p(dist), v, _p(stats), _stream()), "ctg_centreline_saturated")
+    return dist, stats
+
+
+centreline_field.rounds = 0      # the rounds the last call launched (scripts/centreline_bench.py)
+
+
+def centreline_trace(clear, pen, steps, dist, ends, radius, max_points, stats=None):
+    """The paths from each of `ends` (an int32 device tensor [E] of linear indices, E in 1 .. 64) back to the start of
+    `centreline_field`'s dist -> (paths int32 [E, max_points], counts int32 [E]); `stats` (that call's; a fresh one if None) gains
+    entries 1, 2, 4 and, for a field that explains itself nowhere, the error flag [6].  A path runs end first, start last, -1
+    beyond its count; from v the next voxel is the smallest linear index among the neighbours that explain dist[v].  counts: the
+    voxels of the path; 0: the end is outside the volume, on background or unreached; -1: longer than max_points; -2: stuck."""
+    lib = _lib.load()
+    who = "centreline_trace"
+    n, h, w, radius, steps = _centreline_cost(who, clear, pen, steps, radius)
+    _components_array(who, "dist", dist, torch.uint32, n * h * w, clear)
+    e = _components_array(who, "ends", ends, torch.int32, None, clear).numel()
+    if not 1 <= e <= CENTRELINE_MAX_ENDS:
+        raise RuntimeError("%s: 1 .. %d ends expected, got %d" % (who, CENTRELINE_MAX_ENDS, e))
+    max_points = _components_int(who, "max_points", max_points, 1, CENTRELINE_MAX_POINTS)
+    with torch.cuda.device(clear.device):
+        stats = torch.zeros(8, dtype=torch.int32, device=clear.device) if stats is None else \
+            _components_array(who, "stats", stats, torch.int32, 8, clear)
+        paths = torch.empty((e, max_points), dtype=torch.int32, device=clear.device)
+        counts = torch.empty(e, dtype=torch.int32, device=clear.device)
+        _lib.check(lib.ctg_centreline_trace(_p(clear), n, h, w, _p(pen), radius, *steps, _p(dist), _p(ends), e, max_points, _p(paths),
+                                            _p(counts), _p(stats), _stream()), "ctg_centreline_trace")
+    return paths, counts

@@ -686,6 +686,56 @@ int ctg_components_select(const int* labels, long V, int min_voxels, const int* 
 int ctg_components_apply(const short* vol, const int* labels, const unsigned char* keep, long V, int background, int fill, float wc,
                          float ww, int hu, short* out, unsigned char* level, void* stream);
 
+/* ---- series inference, the vessel centreline between clicked voxels (added under ABI 15: purely additive, no existing signature or
+ * meaning moves, so the version stays 15): the minimal-cost path through the lumen from a start voxel to up to 64 end voxels, the
+ * line a curved reformat is laid along.  cta_gan_amd/infer.py: VolumeCentreline, centreline_volume, SeriesTranslator(centreline=...);
+ * ops.centreline_clearance, centreline_field, centreline_trace.  The reference has no counterpart.
+ * Definitions.  vol, N, H, W, V, the linear index i = (z H + y) W + x and the foreground lo <= vol[i] <= hi as for the components.
+ *   q(d) = (d d zq + 128) >> 8 with zq = aspect^2 in 8.8 fixed point (16 .. 65535; 256 = isotropic).  R = 1 .. 32.
+ * ctg_centreline_clearance: clear uint16 [V] = 0 on background, on a foreground voxel min(R^2, min over the background voxels b inside
+ *   the volume of dx^2 + dy^2 + q(|dz|)); voxels outside the volume are not background.  (With zq < 128, q(1) = 0: a foreground voxel
+ *   above or below background then reads 0 and counts as background from here on.)  scratch uint16 [V], the caller's, not `clear`.
+ *   Three launches.
+ * The cost field.  steps s0 .. s4, each 1 .. 255: the length of a move to a 26-neighbour by kind -- in-plane face, in-plane edge,
+ *   z alone, z + one in-plane axis, z + two.  pen uint16 [R^2 + 1], indexed by clear (a clear above R^2 reads pen[R^2]); what is read
+ *   is clamped into 1 .. 4095; pen[0] is never read.  step(u -> v) = steps[kind(v - u)] pen[clear[v]].  A voxel is foreground when
+ *   clear > 0.  dist uint32 [V]: 0xFFFFFFFF = unreached, SAT = 0xFFFFFFFE; dist[start] = 0 when start is foreground, otherwise
+ *   dist[v] = the cheapest path from start to v through foreground voxels, every partial sum passed through min(., SAT): the least
+ *   fixed point, the same bits in whatever order anything lands.
+ * ctg_centreline_seed: dist = 0xFFFFFFFF but 0 at start; active int32 [2][tiles], marks int32 [max_rounds] and stats int32 [8] zeroed;
+ *   the tile of start marked in active[0].  tiles = ceil(N / 8) ceil(H / 16) ceil(W / 32).  A start outside 0 .. V - 1 or on
+ *   background marks nothing and sets stats[0] = 1.
+ * ctg_centreline_relax: rounds first_round .. first_round + rounds - 1, one launch each.  In round r a workgroup per tile leaves at
+ *   once unless active[r & 1][tile] is set; otherwise it clears that entry, relaxes the tile in LDS until nothing changes (or a fixed
+ *   number of sweeps is reached: it then marks itself), writes every lowered voxel back by atomicMin, marks in active[(r + 1) & 1]
+ *   every neighbouring tile whose face, edge or corner it lowered and adds the number of its marks to marks[r].  marks[r] == 0 after
+ *   rounds 0 .. r: the field has reached its fixed point and later rounds do nothing.  stats is not touched.
+ * ctg_centreline_saturated: stats[3] = 1 when a voxel of dist reads SAT (left alone otherwise); for the finished field.
+ * ctg_centreline_trace: for each of E ends (int32 linear indices, 1 .. 64) paths int32 [E][max_points]: path[0] = end; from v with
+ *   dist[v] > 0 the next voxel is the smallest linear index u among the foreground neighbours with dist[u] reached, dist[u] <
+ *   dist[v] and min(dist[u] + step(u -> v), SAT) == dist[v]; the walk ends at dist == 0.  counts int32 [E] = the voxels written (end
+ *   first, start last); 0 for an end outside the volume, on background or unreached (stats[1] counts them, the row is all -1); -1
+ *   when max_points would be exceeded (stats[2]; the row holds the first max_points voxels); -2 when no such u exists (stats[4], and
+ *   the internal-error flag stats[6] = 1, which must read 0: a saturated or foreign field; the row holds the voxels up to there).
+ *   Entries beyond the voxels written hold -1.  stats [1], [2], [4] are zeroed by the call, [6] is only ever set.
+ * Nothing allocates or synchronises; no workgroup waits for another; every loop that depends on memory has a bound that does not;
+ *   exact integer arithmetic, the same bits as numpy (tests/centreline_np.py).
+ * CTG_EINVAL, nothing launched: a null pointer; scratch == clear; N, H or W outside 1 .. 4096 or V above 2^31 - 1; lo > hi or either
+ *   outside int16; R outside 1 .. 32; zq outside 16 .. 65535; a step outside 1 .. 255; max_rounds outside 1 .. 2^20; first_round < 0,
+ *   rounds < 0 or first_round + rounds > max_rounds; E outside 1 .. 64; max_points outside 1 .. 2^24; a 16-bit array not 2-byte
+ *   aligned, a 32-bit array not 4-byte aligned. ---- */
+int ctg_centreline_clearance(const short* vol, int N, int H, int W, int lo, int hi, int R, int zq, unsigned short* scratch,
+                             unsigned short* clear, void* stream);
+int ctg_centreline_seed(const unsigned short* clear, int N, int H, int W, long start, unsigned* dist, int* active, int* marks,
+                        int max_rounds, int* stats, void* stream);
+int ctg_centreline_relax(const unsigned short* clear, int N, int H, int W, const unsigned short* pen, int R, int s0, int s1, int s2,
+                         int s3, int s4, unsigned* dist, int* active, int* marks, int max_rounds, int first_round, int rounds,
+                         int* stats, void* stream);
+int ctg_centreline_saturated(const unsigned* dist, long V, int* stats, void* stream);
+int ctg_centreline_trace(const unsigned short* clear, int N, int H, int W, const unsigned short* pen, int R, int s0, int s1, int s2,
+                         int s3, int s4, const unsigned* dist, const int* ends, int E, int max_points, int* paths, int* counts,
+                         int* stats, void* stream);
+
 /* ---- LPIPS (AlexNet, lpips 0.1) of the test() loops (ABI 14): `loss_fn_alex = lpips.LPIPS(net='alex')` (trainer/HdTrainer.py:26-28)
  * and its calls `loss_fn_alex.forward(torch.tensor(c), torch.tensor(b))` on the windowed and on the raw masked pair of every slice
  * (HdTrainer.py:504-513, 531-536, 1029-1031, 1054-1056; the twins in CycTrainer.py, p2pTrainer.py, RegTrainer.py).  The five

@@ -18,6 +18,7 @@
                       [--mpr-dir DIR --mpr-normal X,Y,Z [--mpr-count P] [--mpr-pitch D] [--mpr-thick T]]
                       [--tumble-dir DIR [--tumble-angles 36] [--tumble-axis x|y|z]]
                       [--cpr-dir DIR --cpr-centreline pts.npy [--cpr-angles A] [--cpr-width U] [--cpr-thick T]]
+                      [--cl-start Z,Y,X --cl-end Z,Y,X [--cl-end ...] --cl-threshold LO[,HI] [--cl-radius R] [--cl-output pts.npy]]
                       [--reformat-sampling nearest|trilinear]
                       [--cc-output vessels.npy --cc-threshold LO[,HI] [--cc-level-dir DIR] [--cc-connectivity 6|18|26]
                        [--cc-min-voxels M] [--cc-largest K] [--cc-seed Z,Y,X ...] [--cc-despeckle] [--cc-source cta|sub]
@@ -94,6 +95,14 @@ keeps its values and only the dropped components are erased.  --cc-level-dir: on
 (int32 [8]) and roots_zyx (the voxel of every root in top, -1 where there is none), and one line reports the components found,
 kept and the voxels kept.  --mip-source vessels makes --mip-dir, --rot-dir, --sts-dir, --vr-dir and the reformats show that
 cleaned volume, in the window of its source.
+--cl-start Z,Y,X with one or more --cl-end Z,Y,X: the vessel centreline from the start voxel to every end voxel (the voxels clicks
+on a MIP or a rendered view map to; they must lie on foreground), traced on the device after the last chunk through the same
+source as the other displays (cta_gan_amd/infer.py: VolumeCentreline): the cheapest path through the voxels with --cl-threshold
+LO <= value <= HI (default HI: 32767) when a step costs more the closer it runs to the vessel wall, the distance to the wall
+capped at --cl-radius R pixels (default 8); --aspect R scales z.  --cl-output pts.npy receives the smoothed points (float64
+[M, 3], (z, y, x), start to end) of the first end -- what --cpr-centreline reads -- and centreline.npz next to it (next to
+--output without it) paths, counts, stats and points_0, points_1, ... of every end; one line reports the lengths.  --cpr-dir
+without --cpr-centreline then makes the curved reformat along the traced line of the first end in the same run.
 DICOM reading and writing are not part of this build.
 """
 import argparse
@@ -180,6 +189,11 @@ def build_parser():
     parser.add_argument("--cc-despeckle", action="store_true", help="keep the background, erase only the dropped components")
     parser.add_argument("--cc-source", choices=["cta", "sub"], default=None, help="the volume the components are taken from")
     parser.add_argument("--cc-labels", type=str, default=None, help="also write the int32 label volume here (with --cc-output)")
+    parser.add_argument("--cl-start", type=str, default=None, help="Z,Y,X: the voxel the vessel centreline starts at (with --cl-end)")
+    parser.add_argument("--cl-end", type=str, action="append", default=None, help="Z,Y,X: a voxel a centreline is traced to (repeatable)")
+    parser.add_argument("--cl-threshold", type=str, default=None, help="LO or LO,HI: the vessel's band (with --cl-start; as --cc-threshold)")
+    parser.add_argument("--cl-radius", type=int, default=8, help="the clearance is capped at this many pixels, 1 .. 32 (with --cl-start)")
+    parser.add_argument("--cl-output", type=str, default=None, help="write the smoothed centreline of the first end here (.npy, [M, 3])")
     parser.add_argument("--dtype", choices=DTYPES, default=None, help="compute mode (default %s, as train.py)" % DEFAULT_DTYPE)
     return parser
 
@@ -251,11 +265,37 @@ def cc_options(parser, opts):
             "labels": opts.cc_labels is not None, "top": 8}
 
 
+def cl_options(parser, opts):
+    """The `SeriesTranslator(centreline=...)` dict of --cl-start / --cl-end (None without them); bad values end in parser.error."""
+    if opts.cl_start is None and opts.cl_end is None:
+        if opts.cl_threshold is not None or opts.cl_output is not None:
+            parser.error("--cl-threshold and --cl-output need --cl-start and --cl-end")
+        return None
+    if opts.cl_start is None or opts.cl_end is None or opts.cl_threshold is None:
+        parser.error("--cl-start, --cl-end and --cl-threshold need each other")
+    try:
+        band = [int(v) for v in opts.cl_threshold.split(",")]
+        points = [tuple(int(v) for v in text.split(",")) for text in [opts.cl_start] + opts.cl_end]
+    except ValueError:
+        parser.error("--cl-threshold: whole numbers LO or LO,HI, --cl-start / --cl-end: whole numbers Z,Y,X expected")
+    band = band + [32767] if len(band) == 1 else band
+    if len(band) != 2 or not -32768 <= band[0] <= band[1] <= 32767:
+        parser.error("--cl-threshold: -32768 <= LO <= HI <= 32767 expected, got %r" % opts.cl_threshold)
+    if any(len(p) != 3 or min(p) < 0 for p in points) or len(points) > 65:
+        parser.error("--cl-start / --cl-end: three whole numbers Z,Y,X >= 0 each, at most 64 ends, expected")
+    if not 1 <= opts.cl_radius <= 32:
+        parser.error("--cl-radius: 1 .. 32 expected")
+    if not 0.25 <= opts.aspect < 16.0:
+        parser.error("--aspect: 0.25 .. 16 expected with --cl-start")
+    return {"threshold": tuple(band), "start": points[0], "ends": points[1:], "radius": opts.cl_radius, "aspect": opts.aspect}
+
+
 def parse_args(argv=None):
     parser = build_parser()
     opts = parser.parse_args(argv)
     opts.sts = sts_options(parser, opts)
     opts.cc = cc_options(parser, opts)
+    opts.cl = cl_options(parser, opts)
     if opts.sub_output is None and (opts.mip_source == "sub" or opts.sub_level_dir is not None):
         parser.error("--mip-source sub and --sub-level-dir need --sub-output")
     if opts.sub_ct_min is not None and opts.sub_ct_max is not None and opts.sub_ct_min > opts.sub_ct_max:
@@ -296,10 +336,15 @@ def parse_args(argv=None):
         parser.error("--mpr-count and --mpr-thick: at least 1, --mpr-pitch: above 0 expected")
     if opts.tumble_angles < 1:
         parser.error("--tumble-angles: at least one view angle expected")
-    if (opts.cpr_dir is None) != (opts.cpr_centreline is None):
-        parser.error("--cpr-dir and --cpr-centreline need each other")
+    opts.cpr_traced = opts.cpr_dir is not None and opts.cpr_centreline is None and opts.cl is not None
+    if (opts.cpr_dir is None) != (opts.cpr_centreline is None) and not opts.cpr_traced:
+        parser.error("--cpr-dir and --cpr-centreline need each other (or --cpr-dir with --cl-start / --cl-end: the traced centreline)")
     if opts.cpr_angles < 1 or opts.cpr_width < 1 or opts.cpr_thick < 1:
         parser.error("--cpr-angles, --cpr-width and --cpr-thick: at least 1 expected")
+    if opts.cpr_traced:      # the curved reformat along the traced path of every end, made by the centreline view itself
+        from cta_gan_amd.infer import view_angles
+        opts.cl["cpr"] = {"angles": view_angles(opts.cpr_angles, 180.0), "cols": opts.cpr_width, "depth": opts.cpr_thick,
+                          "sampling": opts.reformat_sampling, "mode": opts.mip_mode}
     return opts
 
 
@@ -315,7 +360,7 @@ def reformat_tables(opts):
     if opts.tumble_dir is not None:
         angles["tumble"] = view_angles(opts.tumble_angles)
         tables["tumble"] = lambda n, h, w: orbit_lines(n, h, w, angles["tumble"], axis=opts.tumble_axis, aspect=opts.aspect)
-    if opts.cpr_dir is not None:
+    if opts.cpr_dir is not None and not opts.cpr_traced:
         centreline = np.load(opts.cpr_centreline)
         angles["cpr"] = view_angles(opts.cpr_angles, 180.0)
         tables["cpr"] = lambda n, h, w: curved_lines(n, h, w, centreline, angles=angles["cpr"], cols=opts.cpr_width,
@@ -382,7 +427,7 @@ def main(argv=None):
                                  render_options=vr_options, reformat=reformat,
                                  reformat_options={"mode": opts.mip_mode, "sampling": opts.reformat_sampling} if reformat else None,
                                  render3d=None if vr3d is None else {"vr3d": vr3d}, render3d_options=vr3d_options,
-                                 components=opts.cc, components_source=opts.cc_source)
+                                 components=opts.cc, components_source=opts.cc_source, centreline=opts.cl)
     shown = "cued" if opts.depth_cue > 0 else "level"      # the plane the PNGs of the projections are written from
     out = translate(volume)
     np.save(opts.output, out["pix"])
@@ -473,7 +518,25 @@ os.path.join(opts.vr_dir, "vr_%03d.png" % i))
                  light=vr3d_light)
         print("wrote %d %s volume-rendered views (%s, %s sampling) to %s"
               % (len(ren["rgb"]), "shaded" if opts.vr3d_shade else "flat", opts.vr_preset, opts.vr3d_sampling, opts.vr3d_dir), flush=True)
-    for kind, where in (("mpr", opts.mpr_dir), ("tumble", opts.tumble_dir), ("cpr", opts.cpr_dir)):
+    if opts.cl is not None:
+        line = out["centreline"]
+        if opts.cl_output is not None:
+            np.save(opts.cl_output, line["points"][0])
+        np.savez(os.path.join(os.path.dirname(os.path.abspath(opts.cl_output or opts.output)), "centreline.npz"), paths=line["paths"],
+                 counts=line["counts"], stats=line["stats"], **{"points_%d" % e: p for e, p in enumerate(line["points"])})
+        print("centreline: %d path(s) of %s voxels from %s%s" % (len(line["counts"]), ", ".join(str(int(c)) for c in line["counts"]),
+              opts.cl_start, "" if opts.cl_output is None else " (wrote %s)" % opts.cl_output), flush=True)
+        if opts.cpr_traced:
+            from PIL import Image
+            os.makedirs(opts.cpr_dir, exist_ok=True)
+            planes = line["cpr"][0]      # (of the first end; centreline.npz has every path)
+            for i, plane in enumerate(planes["level"]):
+                Image.fromarray(np.ascontiguousarray(plane)).save(os.path.join(opts.cpr_dir, "cpr_%03d.png" % i))
+            np.savez(os.path.join(opts.cpr_dir, "reformat.npz"), values=planes["values"], level=planes["level"],
+                     angles=np.array(opts.cl["cpr"]["angles"], dtype=np.float64))
+            print("wrote %d cpr reformat(s) along the traced centreline, %s sampling, to %s"
+                  % (len(planes["level"]), opts.reformat_sampling, opts.cpr_dir), flush=True)
+    for kind, where in (("mpr", opts.mpr_dir), ("tumble", opts.tumble_dir), ("cpr", None if opts.cpr_traced else opts.cpr_dir)):
         if where is None:
             continue
         from PIL import Image

@@ -52,26 +52,33 @@ voxels inside the table (`aspect`), one launch per table after the last chunk.
 Shaded rendering along lines (`VolumeRenderer`, `render_lines_volume`, `SeriesTranslator(render3d=...)`): the volume-rendered view on
 the same line tables -- rays in any direction, trilinear sampling, anisotropic voxels inside the geometry -- with every sample's
 colour shaded by the local gradient (`ops.render_lines`: the compositing chain of `ops.project_render`, central differences at the
-sample's voxel, a light per line from `headlight` or one fixed vector, all in exact integers).  It keeps the volume on the device
-as the reformats do (`_ResidentVolume` holds what the two share); `line_voxel` maps a depth back to its voxel.
+sample's voxel, a light per line from `headlight` or one fixed vector, all in exact integers).  It reads the volume on the device
+as the reformats do; `line_voxel` maps a depth back to its voxel.
 
 Connected components (`VolumeComponents`, `components_volume`, `SeriesTranslator(components=..., project_source="vessels")`): the
 volume with only the wanted connected components of a threshold band left -- islands below a size dropped, the K largest kept, or
 the component a seed voxel (`ray_voxel`, `line_voxel`) lies in -- labelled on the device after the last chunk (`ops.components_label`
 / `components_select` / `components_apply`: a block union-find whose labels are the smallest linear index of a component, so the
-result does not depend on the order of the kernels' atomics).  A third `_ResidentVolume`; `root_voxel` maps a root to its voxel.
+result does not depend on the order of the kernels' atomics).  `root_voxel` maps a root to its voxel.  The centreline
+(`VolumeCentreline`, `centreline_volume`, `SeriesTranslator(centreline=...)`) is the cheapest path through such a band between clicks.
 
-The view protocol.  The seven display classes above are views (`_SeriesView` holds what they share), and `SeriesTranslator` and
+The resident volume.  The four `Volume*` views read the whole int16 volume on the device.  It is an object of its own,
+`ResidentVolume`: a view makes one for itself, or reads the one it is given (`source=`), so `SeriesTranslator` keeps one per source
+("cta", "sub", the cleaned "vessels") however many views read it and feeds it once per chunk; a volume that is already a contiguous
+device tensor -- the cleaned one, the input of a `*_volume` function -- is adopted as it is, without a copy.
+
+The view protocol.  The display classes above are views (`_SeriesView` holds what they share), and `SeriesTranslator` and
 the `*_volume` functions drive every one of them the same way.  A view is made for one volume shape and has `.n`, `.h`, `.w` and
 `.device`; `update(pix_chunk, n0)` takes a device chunk of slices n0 .. n0+K-1 on the current stream, in any order, every slice
 once; `result()` returns a tree on the device -- a dict of tensors, Nones and nested dicts -- once they have all arrived;
 `reset()` makes the view ready for the next volume of the same shape.  A view whose result has one plane per view angle keeps the
 angles as the host list `.angles`.  Where the classes differ: `SeriesProjector.update` forwards an empty chunk to ops (the others
-return early) and its `result` takes the window (the others take it at construction); `VolumeReformatter` and `VolumeRenderer` also
-bound the sides by `ops.REFORMAT_MAX_DIM`, check the chunk's dtype and resolve device=None at the first chunk only.
+return early) and its `result` takes the window (the others take it at construction); the `Volume*` views also bound the sides by
+`ops.REFORMAT_MAX_DIM`, check the chunk's dtype, resolve device=None at the first chunk only and, given a `source=`, take no chunks.
 """
 from __future__ import annotations
 
+import collections
 import math
 import time
 
@@ -132,10 +139,43 @@ def aspect_rows(n, aspect):
     return np.minimum(np.floor(np.arange(rows, dtype=np.float32) * scale).astype(np.int64), int(n) - 1)
 
 
+def _one_of(who, name, value, choices):
+    if value not in choices:
+        raise ValueError("%s: %s %r is not one of %s" % (who, name, value, choices))
+
+
+def _int_in(who, name, v, lo, hi=None):
+    """-> int(v) of an option that must be an integer (no bool, no float) in lo .. hi, or >= lo without a hi."""
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < lo or (hi is not None and v > hi):
+        raise ValueError("%s: %s: an integer %s expected, got %r" % (who, name, ">= %d" % lo if hi is None else "in %d .. %d" % (lo, hi), v))
+    return int(v)
+
+
+def _band(who, threshold):
+    """-> (lo, hi) of a threshold band: an integer lo (hi = 32767) or a pair of them, -32768 <= lo <= hi <= 32767."""
+    band = tuple(threshold) if isinstance(threshold, (tuple, list)) else (threshold, 32767)
+    if len(band) != 2 or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in band):
+        raise ValueError("%s: threshold: an integer lo or a pair (lo, hi) expected, got %r" % (who, threshold))
+    if not -32768 <= band[0] <= band[1] <= 32767:
+        raise ValueError("%s: threshold: -32768 <= lo <= hi <= 32767 expected, got %r" % (who, threshold))
+    return int(band[0]), int(band[1])
+
+
+def _voxel_indices(who, what, points, n, h, w, least=1, most=None):
+    """-> int64 [P], the linear indices (z h + y) w + x of `least` .. `most` integer points (z, y, x) that lie in the volume."""
+    pts = np.asarray(list(points))
+    if pts.ndim != 2 or pts.shape[1] != 3 or pts.dtype.kind not in "iu" or len(pts) < least or (most is not None and len(pts) > most):
+        raise ValueError("%s: %s: %s integer (z, y, x) expected, got %r"
+                         % (who, what, "at least %d" % least if most is None else "%d .. %d" % (least, most), points))
+    pts = pts.astype(np.int64)
+    if (pts < 0).any() or (pts >= np.array([n, h, w])).any():
+        raise ValueError("%s: %s: a point lies outside the volume (%d, %d, %d)" % (who, what, n, h, w))
+    return (pts[:, 0] * h + pts[:, 1]) * w + pts[:, 2]
+
+
 def _check_depth(who, depth, cue, mode):
     """-> (depth, cue) of the depth planes: cue an integer in 0 .. 256; a depth exists for "max" and "min" only."""
-    if isinstance(cue, bool) or not isinstance(cue, (int, np.integer)) or not 0 <= cue <= 256:
-        raise ValueError("%s: cue: an integer in 0 .. 256 expected, got %r" % (who, cue))
+    cue = _int_in(who, "cue", cue, 0, 256)
     if depth and mode not in ("max", "min"):
         raise ValueError("%s: depth=True needs mode 'max' or 'min' (a mean has no depth), got %r" % (who, mode))
     if cue and not depth:
@@ -161,10 +201,12 @@ def _tree_leaves(tree, path=()):
     return [] if tree is None else [(path, tree)]
 
 
-def _view_of_volume(who, volume, batch, device, make, result=lambda view: view.result(), upload=True):
+def _view_of_volume(who, volume, batch, device, make, result=lambda view: view.result(), whole=False):
     """What the `*_volume` functions share: the view `make(n, h, w, device)` fed with a volume that already exists -- int16
-    [N, H, W], a host array / CPU tensor in chunks of `batch` slices (uploaded one after another, or handed over as they are with
-    upload=False) or a device tensor -- and its `result`, converted to the input's kind."""
+    [N, H, W], a host array / CPU tensor in chunks of `batch` slices or a device tensor -- and its `result`, converted to the
+    input's kind.  The device is the tensor's, else `device`, else the current one.  whole=True, for the views on the whole
+    volume: host chunks go to `update` as they are (it copies them into the resident volume, the only time they cross PCIe), and
+    a contiguous device tensor is adopted as the resident volume instead of being copied into a second one."""
     is_np = isinstance(volume, np.ndarray)
     vol = torch.from_numpy(np.ascontiguousarray(volume)) if is_np else volume
     if not torch.is_tensor(vol) or vol.dtype != torch.int16 or vol.dim() != 3:
@@ -173,10 +215,13 @@ def _view_of_volume(who, volume, batch, device, make, result=lambda view: view.r
         raise ValueError("%s: batch >= 1 expected" % who)
     on_host = not vol.is_cuda
     n, h, w = vol.shape
-    view = make(n, h, w, device if on_host else vol.device)
+    view = make(n, h, w, vol.device if vol.is_cuda else torch.device("cuda", torch.cuda.current_device()) if device is None else device)
     with torch.cuda.device(view.device):
-        for s, e, _ in plan_chunks(n, batch):
-            view.update(vol[s:e].to(view.device) if on_host and upload else vol[s:e], s)
+        if whole and not on_host and vol.is_contiguous():
+            view.source.adopt(vol)
+        else:
+            for s, e, _ in plan_chunks(n, batch):
+                view.update(vol[s:e] if whole or not on_host else vol[s:e].to(view.device), s)
         out = result(view)
     if not on_host:
         return out
@@ -184,8 +229,9 @@ def _view_of_volume(who, volume, batch, device, make, result=lambda view: view.r
 
 
 class _SeriesView:
-    """What the six views share: the volume check, the device check, the check that a chunk lies in the volume, and a `reset()`
-    that does nothing.  A view takes `update(pix_chunk, n0)` for every chunk and gives `result()` once they have all arrived."""
+    """What the views and `ResidentVolume` share: the volume check, the device check, the check that a chunk lies in the volume,
+    and a `reset()` that does nothing.  A view takes `update(pix_chunk, n0)` for every chunk and gives `result()` once they have
+    all arrived.  An error names the class, or `who` where one speaks for another."""
 
     def _volume(self, n, h, w):
         self.n, self.h, self.w = int(n), int(h), int(w)
@@ -199,13 +245,30 @@ class _SeriesView:
             raise RuntimeError("%s: a GPU device is required (no CPU fallback)" % type(self).__name__)
         return device
 
-    def _chunk(self, pix_chunk, n0, dtype=None):
+    def _chunk(self, pix_chunk, n0, dtype=None, who=None):
         """-> K, the slices of a chunk that lies in the volume (and, where the view asks for it, is of `dtype`)."""
         k, n0 = pix_chunk.shape[0], int(n0)
         if tuple(pix_chunk.shape[1:]) != (self.h, self.w) or n0 < 0 or n0 + k > self.n or (dtype is not None and pix_chunk.dtype != dtype):
             raise RuntimeError("%s: %schunk %s at slice %d does not lie in the volume (%d, %d, %d)"
-                               % (type(self).__name__, "" if dtype is None else "int16 ", tuple(pix_chunk.shape), n0, self.n, self.h, self.w))
+                               % (who or type(self).__name__, "" if dtype is None else "int16 ", tuple(pix_chunk.shape), n0, self.n,
+                                  self.h, self.w))
         return k
+
+    def _rays(self, n, h, w, angles, detector, sampling, oversample, device):
+        """What the rotating views share: the volume, `.angles`, the detector `.u` x `.t` (None: `default_detector` for both), `.steps`
+        = t * oversample, the device and the coefficient table of the angles on it."""
+        _check_sampling(type(self).__name__, sampling, oversample)
+        self.sampling, self.oversample = sampling, int(oversample)
+        self._volume(n, h, w)
+        self.angles = [float(a) for a in angles]
+        if not 1 <= len(self.angles) <= ops.ROTATE_MAX_DIM:
+            raise ValueError("%s: 1 .. %d view angles expected, got %d" % (type(self).__name__, ops.ROTATE_MAX_DIM, len(self.angles)))
+        d = default_detector(self.h, self.w)
+        self.u, self.t = (d, d) if detector is None else _pair(detector)
+        self.steps = self.t * self.oversample
+        self.device = self._gpu(device)
+        self.table = ops.RotateTable([rotation_coefficients(a, self.h, self.w, self.u, self.t, self.oversample)
+                                      for a in self.angles], self.device)
 
     def reset(self):
         """For the next volume of the same shape: nothing to refill unless the view keeps accumulators."""
@@ -225,8 +288,7 @@ class SeriesProjector(_SeriesView):
     the level attenuated by the depth inside the ray, (level w + 128) >> 8 with w = 256 - (cue d) / E, `cue` in 0 .. 256."""
 
     def __init__(self, n, h, w, mode="max", slab=None, axes=AXES, device=None, depth=False, cue=0):
-        if mode not in PROJECTIONS:
-            raise ValueError("SeriesProjector: mode %r is not one of %s" % (mode, PROJECTIONS))
+        _one_of("SeriesProjector", "mode", mode, PROJECTIONS)
         self.depth, self.cue = _check_depth("SeriesProjector", depth, cue, mode)
         axes = tuple(axes)
         if not axes or any(a not in AXES for a in axes):
@@ -311,8 +373,7 @@ class SeriesSlabs(_SeriesView):
     numpy bit for bit."""
 
     def __init__(self, n, h, w, thick, step=None, mode="max", axes=AXES, wc=50.0, ww=400.0, hu=False, level=True, device=None):
-        if mode not in PROJECTIONS:
-            raise ValueError("SeriesSlabs: mode %r is not one of %s" % (mode, PROJECTIONS))
+        _one_of("SeriesSlabs", "mode", mode, PROJECTIONS)
         axes = tuple(axes)
         if not axes or any(a not in AXES for a in axes):
             raise ValueError("SeriesSlabs: axes %r, a non-empty choice of %s expected" % (axes, AXES))
@@ -433,10 +494,8 @@ def ray_voxel(coef_row, u, t):
 
 
 def _check_sampling(who, sampling, oversample):
-    if sampling not in ops.ROTATE_SAMPLINGS:
-        raise ValueError("%s: sampling %r is not one of %s" % (who, sampling, tuple(ops.ROTATE_SAMPLINGS)))
-    if isinstance(oversample, bool) or not isinstance(oversample, (int, np.integer)) or oversample < 1:
-        raise ValueError("%s: oversample: an integer >= 1 expected, got %r" % (who, oversample))
+    _one_of(who, "sampling", sampling, tuple(ops.ROTATE_SAMPLINGS))
+    _int_in(who, "oversample", oversample, 1)
 
 
 class SeriesRotator(_SeriesView):
@@ -454,24 +513,12 @@ class SeriesRotator(_SeriesView):
 
     def __init__(self, n, h, w, angles, mode="max", detector=None, fill=None, wc=50.0, ww=400.0, hu=False, level=True, device=None,
                  sampling="nearest", oversample=1, depth=False, cue=0):
-        if mode not in PROJECTIONS:
-            raise ValueError("SeriesRotator: mode %r is not one of %s" % (mode, PROJECTIONS))
+        _one_of("SeriesRotator", "mode", mode, PROJECTIONS)
         self.depth, self.cue = _check_depth("SeriesRotator", depth, cue, mode)
-        _check_sampling("SeriesRotator", sampling, oversample)
-        self.sampling, self.oversample = sampling, int(oversample)
-        self._volume(n, h, w)
-        self.angles = [float(a) for a in angles]
-        if not 1 <= len(self.angles) <= ops.ROTATE_MAX_DIM:
-            raise ValueError("SeriesRotator: 1 .. %d view angles expected, got %d" % (ops.ROTATE_MAX_DIM, len(self.angles)))
-        d = default_detector(self.h, self.w)
-        self.u, self.t = (d, d) if detector is None else _pair(detector)
-        self.steps = self.t * self.oversample
         self.mode, self.code = mode, ops.PROJECT_MODES[mode]
         self.hu, self.window = bool(hu), (float(wc), float(ww))
         self.fill = (-1024 if self.hu else 0) if fill is None else int(fill)
-        self.device = self._gpu(device)
-        self.table = ops.RotateTable([rotation_coefficients(a, self.h, self.w, self.u, self.t, self.oversample)
-                                      for a in self.angles], self.device)
+        self._rays(n, h, w, angles, detector, sampling, oversample, device)
         shape = (len(self.angles), self.n, self.u)
         self.values = torch.empty(shape, dtype=torch.int16, device=self.device)
         self.level = torch.empty(shape, dtype=torch.uint8, device=self.device) if level else None
@@ -519,8 +566,7 @@ def transfer_function(points, oversample=1):
     floor(x + 0.5).  oversample = s: a ray that takes s steps per voxel meets s samples where it met one, so the opacity is
     corrected per step, a_s = 1 - (1 - a) ** (1 / s) (s = 1 changes nothing), and alpha = floor(a_s * 32768 + 0.5), 32768 = opaque.
     Returns uint16 [256, 4]: R, G, B, alpha."""
-    if isinstance(oversample, bool) or not isinstance(oversample, (int, np.integer)) or oversample < 1:
-        raise ValueError("transfer_function: oversample: an integer >= 1 expected, got %r" % (oversample,))
+    _int_in("transfer_function", "oversample", oversample, 1)
     try:
         pts = np.array([[float(v) for v in p] for p in points], dtype=np.float64)
     except (TypeError, ValueError):
@@ -561,8 +607,7 @@ def _transfer_table(who, transfer, oversample):
     """`transfer` of SeriesRenderer -> uint16 [256, 4]: a preset name, a point list (both through `transfer_function` with the
     renderer's oversample) or a ready table (taken as it is: whoever made it corrected it)."""
     if isinstance(transfer, str):
-        if transfer not in TRANSFER_PRESETS:
-            raise ValueError("%s: transfer %r is not one of %s" % (who, transfer, tuple(TRANSFER_PRESETS)))
+        _one_of(who, "transfer", transfer, tuple(TRANSFER_PRESETS))
         return transfer_function(TRANSFER_PRESETS[transfer], oversample)
     table = transfer.cpu().numpy() if torch.is_tensor(transfer) else transfer
     if isinstance(table, np.ndarray) and table.shape == (256, 4):
@@ -585,20 +630,10 @@ class SeriesRenderer(_SeriesView):
     def __init__(self, n, h, w, angles, transfer="vessels", detector=None, wc=300.0, ww=1500.0, hu=False, sampling="nearest",
                  oversample=1, background=(0, 0, 0), stop=128, surface=16384, depth=True, device=None):
         _check_sampling("SeriesRenderer", sampling, oversample)
-        self.sampling, self.oversample = sampling, int(oversample)
-        self._volume(n, h, w)
-        self.angles = [float(a) for a in angles]
-        if not 1 <= len(self.angles) <= ops.ROTATE_MAX_DIM:
-            raise ValueError("SeriesRenderer: 1 .. %d view angles expected, got %d" % (ops.ROTATE_MAX_DIM, len(self.angles)))
         self.background, self.stop, self.surface = _check_compositing("SeriesRenderer", background, stop, surface)
-        d = default_detector(self.h, self.w)
-        self.u, self.t = (d, d) if detector is None else _pair(detector)
-        self.steps = self.t * self.oversample
         self.hu, self.window = bool(hu), (float(wc), float(ww))
-        lut = _transfer_table("SeriesRenderer", transfer, self.oversample)
-        self.device = self._gpu(device)
-        self.table = ops.RotateTable([rotation_coefficients(a, self.h, self.w, self.u, self.t, self.oversample)
-                                      for a in self.angles], self.device)
+        lut = _transfer_table("SeriesRenderer", transfer, int(oversample))
+        self._rays(n, h, w, angles, detector, sampling, oversample, device)
         self.lut = ops.TransferTable(lut, self.device)
         shape = (len(self.angles), self.n, self.u)
         self.rgb = torch.empty(shape + (3,), dtype=torch.uint8, device=self.device)
@@ -675,8 +710,7 @@ def _unit(who, name, v):
 
 def _line_geometry(who, n, h, w, rows, cols, depth, oversample, aspect):
     n, h, w, rows, cols, depth = int(n), int(h), int(w), int(rows), int(cols), int(depth)
-    if isinstance(oversample, bool) or not isinstance(oversample, (int, np.integer)) or oversample < 1:
-        raise ValueError("%s: oversample: an integer >= 1 expected, got %r" % (who, oversample))
+    _int_in(who, "oversample", oversample, 1)
     s, aspect = int(oversample), float(aspect)
     if min(n, h, w) < 1 or max(n, h, w) > ops.REFORMAT_MAX_DIM:
         raise ValueError("%s: n, h, w in 1 .. %d expected, got %d %d %d" % (who, ops.REFORMAT_MAX_DIM, n, h, w))
@@ -838,21 +872,87 @@ def curved_lines(n, h, w, centreline, angles=(0.0,), cols=65, depth=1, pitch=1.0
     return LineSet(np.stack(tables), depth * s, cols)
 
 
-class _ResidentVolume(_SeriesView):
-    """What the views on the whole volume share (`VolumeReformatter`, `VolumeRenderer`): the int16 volume kept on the device, the
-    copy-in of a chunk in any order, the count of how often every slice has arrived and the refusal of a result unless that is
-    exactly once, the device resolved at the first chunk only, and `reset()`.  A subclass calls `_resident` from its constructor,
-    uploads its tables in `_upload` (run once, at the first chunk, on `self.device`) and `_whole` before it launches."""
+class ResidentVolume(_SeriesView):
+    """An int16 volume [n, h, w] kept on the device for the views that read all of it (`VolumeReformatter`, `VolumeRenderer`,
+    `VolumeComponents`, `VolumeCentreline`): any number of them read one `ResidentVolume` (their `source=`).  `.volume`: the
+    tensor, None until the first chunk; `.device`: None means the current device at the first chunk; `.seen`: how often every slice
+    has arrived; `.nbytes` = 2 n h w.  `update(pix_chunk, n0)` copies a chunk in, in any order; `whole(who)` raises unless every
+    slice has arrived exactly once since the last `reset()`, which forgets the arrivals and keeps the memory.  `adopt(tensor)`
+    takes a finished volume -- a contiguous int16 [n, h, w] tensor on the device -- as it is, without a copy: every slice has then
+    arrived once, and `reset()` lets go of it."""
 
-    def _sides(self, who, n, h, w):
+    def __init__(self, n, h, w, device=None):
+        self._volume(n, h, w)
+        self.device = None if device is None else self._gpu(device)
+        self.seen = np.zeros(self.n, dtype=np.int64)
+        self.volume, self._adopted = None, False      # on the device from the first chunk on
+        self.nbytes = 2 * self.n * self.h * self.w
+
+    def reset(self):
+        self.seen[:] = 0
+        if self._adopted:
+            self.volume, self._adopted = None, False
+
+    def update(self, pix_chunk, n0, who=None):
+        k, n0 = self._chunk(pix_chunk, n0, dtype=torch.int16, who=who), int(n0)      # (the copy below would convert another dtype)
+        if k < 1:
+            return
+        if self.volume is None or self._adopted:      # (an adopted tensor is somebody's result: never written to)
+            self.device = self._gpu(None) if self.device is None else self.device
+            self.volume, self._adopted = torch.empty((self.n, self.h, self.w), dtype=torch.int16, device=self.device), False
+        self.volume[n0:n0 + k].copy_(pix_chunk, non_blocking=True)
+        self.seen[n0:n0 + k] += 1
+
+    def adopt(self, tensor):
+        if (not torch.is_tensor(tensor) or tensor.dtype != torch.int16 or tuple(tensor.shape) != (self.n, self.h, self.w)
+                or not tensor.is_cuda or not tensor.is_contiguous() or self.device not in (None, torch.device("cuda"), tensor.device)):
+            got = (tensor.dtype, tuple(tensor.shape), tensor.device, tensor.is_contiguous()) if torch.is_tensor(tensor) else tensor
+            raise RuntimeError("ResidentVolume: adopt: a contiguous int16 tensor (%d, %d, %d) on %s expected, got %r"
+                               % (self.n, self.h, self.w, self.device or "a GPU", got))
+        self.volume, self.device, self._adopted = tensor, tensor.device, True
+        self.seen[:] = 1
+
+    def whole(self, who):
+        if (self.seen != 1).any():
+            missing, twice = int((self.seen == 0).sum()), int((self.seen > 1).sum())
+            raise RuntimeError("%s: every slice must have arrived exactly once: %d of %d missing, %d more than once"
+                               % (who, missing, self.n, twice))
+
+
+class _VolumeView(_SeriesView):
+    """What the views on the whole volume share: they read a `ResidentVolume`, `.source`.  source=None: the view makes its own
+    and `update` feeds it; source= a `ResidentVolume` of the same (n, h, w): the view reads that one, whoever owns it feeds it,
+    and `nbytes` leaves the volume out.  `.volume` and `.device` are the source's.  A subclass checks its sides with `_sides`, ends
+    its constructor with `_reads`, uploads its tables in `_upload` (run once on `self.device`: at the first chunk of its own
+    volume, else before the first launch) and calls `_whole` before it launches."""
+
+    volume = property(lambda self: self.source.volume)
+    device = property(lambda self: self.source.device)
+
+    def _sides(self, who, n, h, w, linear=False):
         self._volume(n, h, w)
         if max(self.n, self.h, self.w) > ops.REFORMAT_MAX_DIM:      # the line tables address the sides in 16.16 fixed point
             raise ValueError("%s: n, h, w in 1 .. %d expected, got %d %d %d" % (who, ops.REFORMAT_MAX_DIM, self.n, self.h, self.w))
+        if linear and self.n * self.h * self.w > 2 ** 31 - 1:      # the kernels address a voxel by an int32 linear index
+            raise ValueError("%s: at most 2^31 - 1 voxels expected, got %d x %d x %d" % (who, self.n, self.h, self.w))
 
-    def _resident(self, device):
-        self._seen = np.zeros(self.n, dtype=np.int64)
-        self.device = None if device is None else self._gpu(device)      # None: the current device at the first chunk
-        self.volume = None      # on the device from the first chunk on
+    def _shown(self, wc, ww, hu, level, fill):
+        """The window of the 8-bit level, whether it is wanted, and what lies outside the volume: air by default, 0 or -1024 with `hu`."""
+        self.hu, self.window, self.want_level = bool(hu), (float(wc), float(ww)), bool(level)
+        self.fill = (-1024 if self.hu else 0) if fill is None else int(fill)
+
+    def _reads(self, device, source):
+        """The last step of a constructor (`self.nbytes` counts a volume of the view's own by then)."""
+        self.owns, self._uploaded = source is None, False
+        if self.owns:
+            source = ResidentVolume(self.n, self.h, self.w, None if device is None else self._gpu(device))
+        elif not isinstance(source, ResidentVolume) or (source.n, source.h, source.w) != (self.n, self.h, self.w):
+            raise ValueError("%s: source: a ResidentVolume of (%d, %d, %d) expected, got %r"
+                             % (type(self).__name__, self.n, self.h, self.w,
+                                (source.n, source.h, source.w) if isinstance(source, ResidentVolume) else source))
+        else:
+            self.nbytes -= source.nbytes
+        self.source = source
 
     def _line_tables(self, who, tables, cols):
         """`tables` of the constructor -> {name: (host table, U, T)}, checked on the host."""
@@ -868,83 +968,74 @@ class _ResidentVolume(_SeriesView):
         return lines
 
     def _upload(self):
-        """The view's tables onto `self.device`: once, at the first chunk."""
+        """The view's tables onto `self.device`."""
+
+    def _uploaded_once(self):
+        if not self._uploaded and self.device is not None:
+            self._upload()
+            self._uploaded = True
 
     def reset(self):
-        """Forget which slices have arrived (the volume's memory is kept and overwritten)."""
-        self._seen[:] = 0
+        if self.owns:
+            self.source.reset()
 
     def update(self, pix_chunk, n0):
-        k, n0 = self._chunk(pix_chunk, n0, dtype=torch.int16), int(n0)      # (the copy below would convert another dtype)
-        if k < 1:
-            return
-        if self.volume is None:
-            if self.device is None:
-                self.device = self._gpu(None)
-            self._upload()
-            self.volume = torch.empty((self.n, self.h, self.w), dtype=torch.int16, device=self.device)
-        self.volume[n0:n0 + k].copy_(pix_chunk, non_blocking=True)
-        self._seen[n0:n0 + k] += 1
+        if not self.owns:
+            raise RuntimeError("%s: update: the volume is fed through its source" % type(self).__name__)
+        self.source.update(pix_chunk, n0, who=type(self).__name__)
+        self._uploaded_once()
 
     def _whole(self):
-        if (self._seen != 1).any():
-            missing, twice = int((self._seen == 0).sum()), int((self._seen > 1).sum())
-            raise RuntimeError("%s: every slice must have arrived exactly once: %d of %d missing, %d more than once"
-                               % (type(self).__name__, missing, self.n, twice))
+        self.source.whole(type(self).__name__)
+        self._uploaded_once()
+
+    def _reformat(self, table, mode, sampling):
+        """One `ops.reformat_lines` launch on the volume, in the view's window."""
+        values, level = ops.reformat_lines(self.volume, table, table.u, table.t, mode, fill=self.fill, wc=self.window[0], ww=self.window[1],
+                                           hu=self.hu, sampling=sampling, want_level=self.want_level)
+        return {"values": values, "level": level}
 
 
-class VolumeReformatter(_ResidentVolume):
-    """Reformats of an int16 volume [n, h, w] that arrives in chunks and stays on the device: oblique planes, tumbling views,
-    curved reformats -- every display whose rows cross slices (`ops.reformat_lines`, csrc/reformat.hip).  tables: {name: a
-    `LineSet`, a pair (table [..., 9], T) with `cols` given here, or a callable (n, h, w) -> either}; mode "max" / "min" / "mean"
-    along the rays of T steps, sampling "trilinear" or "nearest", `fill` where a ray misses the volume (default: air, 0 or -1024
-    with `hu`), level=False skips the 8-bit planes of the window (wc, ww).  `update(pix_chunk, n0)` copies a chunk in, in any
-    order; `result()` raises unless every slice has arrived exactly once since the last `reset()`, then makes one launch per
-    table -> {name: {"values": int16 [..., U], "level": uint8 or None}} on the device.  `.nbytes`: the device memory held (the
-    volume and the tables) plus that of one result, known before the first chunk.  Exact integer arithmetic on the current
-    stream: equal to numpy bit for bit."""
+class VolumeReformatter(_VolumeView):
+    """Reformats of an int16 volume [n, h, w] that arrives in chunks and stays on the device: oblique planes, tumbling views, curved
+    reformats -- every display whose rows cross slices (`ops.reformat_lines`, csrc/reformat.hip).  tables: {name: a `LineSet`, a
+    pair (table [..., 9], T) with `cols` given here, or a callable (n, h, w) -> either}; mode "max" / "min" / "mean" along the rays
+    of T steps, sampling "trilinear" or "nearest", `fill` where a ray misses the volume (default: air, 0 or -1024 with `hu`),
+    level=False skips the 8-bit planes of the window (wc, ww).  The volume, `source=`, `update` and `reset` as `_VolumeView` has
+    them; `result()` makes one launch per table -> {name: {"values": int16 [..., U], "level": uint8 or None}} on the
+    device.  `.nbytes`: the device memory held (the volume, unless it is a source's, and the tables) plus that of one result, known
+    before the first chunk.  Exact integer arithmetic on the current stream: equal to numpy bit for bit."""
 
     def __init__(self, n, h, w, tables, mode="max", sampling="trilinear", fill=None, wc=50.0, ww=400.0, hu=False, level=True,
-                 device=None, cols=None):
+                 device=None, cols=None, source=None):
         who = "VolumeReformatter"
-        if mode not in PROJECTIONS:
-            raise ValueError("%s: mode %r is not one of %s" % (who, mode, PROJECTIONS))
-        if sampling not in REFORMAT_SAMPLINGS:
-            raise ValueError("%s: sampling %r is not one of %s" % (who, sampling, REFORMAT_SAMPLINGS))
+        _one_of(who, "mode", mode, PROJECTIONS)
+        _one_of(who, "sampling", sampling, REFORMAT_SAMPLINGS)
         self._sides(who, n, h, w)
         self.lines = self._line_tables(who, tables, cols)      # name -> (host table, U, T), checked
         self.mode, self.sampling = mode, sampling
-        self.hu, self.window, self.want_level = bool(hu), (float(wc), float(ww)), bool(level)
-        self.fill = (-1024 if self.hu else 0) if fill is None else int(fill)
+        self._shown(wc, ww, hu, level, fill)
         per = 2 + (1 if self.want_level else 0)
         self.nbytes = 2 * self.n * self.h * self.w + sum(t.nbytes + per * (t.size // 9) * u for t, u, _ in self.lines.values())
-        self._resident(device)
-        self.tables = None      # on the device from the first chunk on
+        self.tables = None      # on the device from `_upload` on
+        self._reads(device, source)
 
     def _upload(self):
         self.tables = {name: ops.LineTable(t, u, steps, self.device) for name, (t, u, steps) in self.lines.items()}
 
     def result(self):
         self._whole()
-        out = {}
-        for name, table in self.tables.items():
-            values, level = ops.reformat_lines(self.volume, table, table.u, table.t, self.mode, fill=self.fill, wc=self.window[0],
-                                               ww=self.window[1], hu=self.hu, sampling=self.sampling, want_level=self.want_level)
-            out[name] = {"values": values, "level": level}
-        return out
+        return {name: self._reformat(table, self.mode, self.sampling) for name, table in self.tables.items()}
 
 
 def reformat_volume(volume, tables, mode="max", sampling="trilinear", fill=None, wc=50.0, ww=400.0, hu=False, level=True, batch=64,
                     device=None, cols=None):
     """The reformats of a volume that already exists, the twin of `rotate_volume`: int16 [N, H, W], a host array / CPU tensor
-    (chunks of `batch` slices cross PCIe one after another) or a device tensor; tables and the options as `VolumeReformatter`.
-    Returns what `VolumeReformatter.result` returns, of the input's kind."""
-    def make(n, h, w, dev):      # (the device is resolved here: the chunk loop runs under it)
-        return VolumeReformatter(n, h, w, tables, mode=mode, sampling=sampling, fill=fill, wc=wc, ww=ww, hu=hu, level=level,
-                                 device=torch.device("cuda", torch.cuda.current_device()) if dev is None else dev, cols=cols)
-
-    # host chunks go to `update` as they are: it copies them into the resident volume, the only time they cross PCIe
-    return _view_of_volume("reformat_volume", volume, batch, device, make, upload=False)
+    (chunks of `batch` slices cross PCIe one after another) or a device tensor (read where it is when it is contiguous); tables and
+    the options as `VolumeReformatter`.  Returns what `VolumeReformatter.result` returns, of the input's kind."""
+    return _view_of_volume("reformat_volume", volume, batch, device, whole=True,
+                           make=lambda n, h, w, dev: VolumeReformatter(n, h, w, tables, mode=mode, sampling=sampling, fill=fill, wc=wc,
+                                                                       ww=ww, hu=hu, level=level, device=dev, cols=cols))
 
 
 def _ray_table(who, lines):
@@ -1003,35 +1094,32 @@ def _check_compositing(who, background, stop, surface):
     bg = tuple(background)
     if len(bg) != 3 or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v <= 255 for v in bg):
         raise ValueError("%s: background: three integers in 0 .. 255 expected, got %r" % (who, background))
-    for name, v, lo in (("stop", stop, 0), ("surface", surface, 1)):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= lo + ops.RENDER_OPAQUE - 1:
-            raise ValueError("%s: %s: an integer in %d .. %d expected, got %r" % (who, name, lo, lo + ops.RENDER_OPAQUE - 1, v))
-    return tuple(int(v) for v in bg), int(stop), int(surface)
+    return (tuple(int(v) for v in bg), _int_in(who, "stop", stop, 0, ops.RENDER_OPAQUE - 1),
+            _int_in(who, "surface", surface, 1, ops.RENDER_OPAQUE))
 
 
-class VolumeRenderer(_ResidentVolume):
+class VolumeRenderer(_VolumeView):
     """Shaded volume-rendered views of an int16 volume [n, h, w] that arrives in chunks and stays on the device, along rays in any
     direction (`ops.render_lines`, csrc/render_lines.hip): the compositing of `SeriesRenderer` on the line tables of
     `VolumeReformatter` -- tumbling and oblique views, trilinear sampling, anisotropic voxels inside the geometry -- with every
     sample's colour shaded by the local gradient.  tables: {name: a `LineSet`, a pair (table, T) with `cols` given here, or a
-    callable (n, h, w) -> either}; transfer, (wc, ww), hu, background, stop, surface and depth as `SeriesRenderer` (a preset name
-    or a point list is made for one step per voxel: for oversampled tables pass `transfer_function(points, oversample)`);
-    sampling "trilinear" or "nearest".  shading: None (flat class colours) or a dict with any of "ambient" (0 .. 1, default 0.3:
-    the share of the colour a wall edge-on to the light keeps), "gmin" (default 40, in stored units per two voxels: a sample
-    whose gradient is shorter keeps its colour, so that noise in soft tissue is not shaded) and "light" ("head", default: along
-    every line's own ray, `headlight`; or one vector (x, y, z) in pixel units for all).  aspect (slice spacing / pixel spacing,
-    the one the tables were made with) scales the gradient's z component, zscale = floor(256 / aspect + 0.5) in 1 .. 4096, and
-    the headlight.  `update(pix_chunk, n0)` copies a chunk in, in any order; `result()` raises unless every slice has arrived
-    exactly once since the last `reset()`, then makes one launch per table -> {name: {"rgb": uint8 [..., U, 3], "opacity": uint8
-    [..., U], "depth": int16 [..., U] or None (-1 where the ray never reaches `surface`; `line_voxel` maps a hit back to the
-    voxel)}} on the device.  `.nbytes`: the device memory held (the volume and the tables) plus that of one result, known before
-    the first chunk.  Exact integer arithmetic on the current stream: equal to numpy bit for bit."""
+    callable (n, h, w) -> either}; transfer, (wc, ww), hu, background, stop, surface and depth as `SeriesRenderer` (a preset name or
+    a point list is made for one step per voxel: for oversampled tables pass `transfer_function(points, oversample)`); sampling
+    "trilinear" or "nearest".  shading: None (flat class colours) or a dict with any of "ambient" (0 .. 1, default 0.3: the share of
+    the colour a wall edge-on to the light keeps), "gmin" (default 40, in stored units per two voxels: a sample whose gradient is
+    shorter keeps its colour, so that noise in soft tissue is not shaded) and "light" ("head", default: along every line's own ray,
+    `headlight`; or one vector (x, y, z) in pixel units for all).  aspect (slice spacing / pixel spacing, the one the tables were
+    made with) scales the gradient's z component, zscale = floor(256 / aspect + 0.5) in 1 .. 4096, and the headlight.  The volume,
+    `source=`, `update` and `reset` as `_VolumeView` has them; `result()` makes one launch per table -> {name: {"rgb": uint8 [...,
+    U, 3], "opacity": uint8 [..., U], "depth": int16 [..., U] or None (-1 where the ray never reaches `surface`; `line_voxel` maps a
+    hit back to the voxel)}} on the device.  `.nbytes`: the device memory held (the volume, unless it is a source's, and the tables)
+    plus that of one result, known before the first chunk.  Exact integer arithmetic on the current stream: equal to numpy bit for
+    bit."""
 
     def __init__(self, n, h, w, tables, transfer="vessels", wc=300.0, ww=1500.0, hu=False, sampling="trilinear", shading=None,
-                 aspect=1.0, background=(0, 0, 0), stop=128, surface=16384, depth=True, device=None, cols=None):
+                 aspect=1.0, background=(0, 0, 0), stop=128, surface=16384, depth=True, device=None, cols=None, source=None):
         who = "VolumeRenderer"
-        if sampling not in REFORMAT_SAMPLINGS:
-            raise ValueError("%s: sampling %r is not one of %s" % (who, sampling, REFORMAT_SAMPLINGS))
+        _one_of(who, "sampling", sampling, REFORMAT_SAMPLINGS)
         self._sides(who, n, h, w)
         self.lines = self._line_tables(who, tables, cols)      # name -> (host table, U, T), checked
         self.sampling, self.hu, self.window, self.want_depth = sampling, bool(hu), (float(wc), float(ww)), bool(depth)
@@ -1066,8 +1154,8 @@ class VolumeRenderer(_ResidentVolume):
         per = 3 + 1 + (2 if self.want_depth else 0)
         self.nbytes = 2 * self.n * self.h * self.w + 2 * 4 * 256 + sum(
             t.nbytes + (12 * (t.size // 9) if self.lights is not None else 0) + per * (t.size // 9) * u for t, u, _ in self.lines.values())
-        self._resident(device)
-        self.tables = self.lamps = self.lut = None      # on the device from the first chunk on
+        self.tables = self.lamps = self.lut = None      # on the device from `_upload` on
+        self._reads(device, source)
 
     def _upload(self):
         self.tables = {name: ops.LineTable(t, u, steps, self.device) for name, (t, u, steps) in self.lines.items()}
@@ -1089,14 +1177,10 @@ class VolumeRenderer(_ResidentVolume):
 
 def render_lines_volume(volume, tables, batch=64, device=None, **options):
     """The shaded renderings of a volume that already exists, the twin of `reformat_volume`: int16 [N, H, W], a host array / CPU
-    tensor (chunks of `batch` slices cross PCIe one after another) or a device tensor; tables and the options as
-    `VolumeRenderer`.  Returns what `VolumeRenderer.result` returns, of the input's kind."""
-    def make(n, h, w, dev):      # (the device is resolved here: the chunk loop runs under it)
-        return VolumeRenderer(n, h, w, tables, device=torch.device("cuda", torch.cuda.current_device()) if dev is None else dev,
-                              **options)
-
-    # host chunks go to `update` as they are: it copies them into the resident volume, the only time they cross PCIe
-    return _view_of_volume("render_lines_volume", volume, batch, device, make, upload=False)
+    tensor (chunks of `batch` slices cross PCIe one after another) or a device tensor (read where it is when it is contiguous);
+    tables and the options as `VolumeRenderer`.  Returns what `VolumeRenderer.result` returns, of the input's kind."""
+    return _view_of_volume("render_lines_volume", volume, batch, device, whole=True,
+                           make=lambda n, h, w, dev: VolumeRenderer(n, h, w, tables, device=dev, **options))
 
 
 COMPONENTS_OPTIONS = ("threshold", "connectivity", "min_voxels", "largest", "seeds", "background", "fill", "wc", "ww", "hu", "level",
@@ -1117,63 +1201,43 @@ def root_voxel(root, h, w):
     return (int(z), int(y), int(x)) if r.ndim == 0 else (z, y, x)
 
 
-class VolumeComponents(_ResidentVolume):
+class VolumeComponents(_VolumeView):
     """The connected components of an int16 volume [n, h, w] that arrives in chunks and stays on the device, and the volume with
     only the wanted ones left (`ops.components_label` / `components_select` / `components_apply`, csrc/components.hip): despeckle,
     the K largest vessels, the vessel tree a click lies in.  threshold: lo, or (lo, hi) with hi = 32767 by default -- a voxel is
     foreground when lo <= value <= hi (stored values: HU differences for the subtraction volume); connectivity 6 / 18 / 26 in index
     space.  Kept are the components of at least `min_voxels` voxels that, where `seeds` (a sequence of (z, y, x), e.g. from
     `ray_voxel` / `line_voxel`) is given, hold a seed; of those the `largest` = K biggest (0: all; ties: the smaller root first).
-    background=False masks: everything but the kept components becomes `fill` (default: air, 0 or -1024 with `hu`);
-    background=True despeckles: only the dropped components do.  `update(pix_chunk, n0)` copies a chunk in, in any order;
-    `result()` raises unless every slice has arrived exactly once since the last `reset()` -> {"values": int16 [n, h, w],
-    "level": uint8 in the window (wc, ww) or None, "labels": int32 [n, h, w] (-1 on background, otherwise the component's root:
-    its smallest linear index, `root_voxel`) or None, "top": int32 [top, 2] = (root, size) of the biggest kept components in
-    order, (-1, 0) beyond them, "stats": int32 [8] = foreground voxels, components, candidates, kept components, kept voxels,
-    seeds that selected nothing, the internal-error flag (whoever reads stats on the host raises unless it is 0:
-    `check_components_stats`), 0} on the device.  `.nbytes`: the device memory held (the volume, labels, sizes, marks: 11 bytes
-    per voxel) plus that of one result (2, or 3 with level, per voxel), known before the first chunk.  It holds its own copy of
-    the volume.  Exact integer arithmetic on the current stream: equal to numpy bit for bit, whatever order the atomics land in."""
+    background=False masks: everything but the kept components becomes `fill` (default: air, 0 or -1024 with `hu`); background=True
+    despeckles: only the dropped components do.  The volume, `source=`, `update` and `reset` as `_VolumeView` has them; `result()`
+    -> {"values": int16 [n, h, w], "level": uint8 in the window (wc, ww) or None, "labels": int32 [n, h, w] (-1 on background,
+    otherwise the component's root: its smallest linear index, `root_voxel`) or None, "top": int32 [top, 2] = (root, size) of the
+    biggest kept components in order, (-1, 0) beyond them, "stats": int32 [8] = foreground voxels, components, candidates, kept
+    components, kept voxels, seeds that selected nothing, the internal-error flag (whoever reads stats on the host raises unless it
+    is 0: `check_components_stats`), 0} on the device.  `.nbytes`: the device memory held (the volume, unless it is a source's,
+    labels, sizes, marks: 2 + 9 bytes per voxel) plus that of one result (2, or 3 with level, per voxel), known before the first
+    chunk.  It never writes to the volume: "values" is a fresh tensor per result.  Exact integer arithmetic on the current stream:
+    equal to numpy bit for bit, whatever order the atomics land in."""
 
     def __init__(self, n, h, w, threshold, connectivity=26, min_voxels=1, largest=0, seeds=None, background=False, fill=None,
-                 wc=50.0, ww=400.0, hu=False, level=True, labels=False, top=8, device=None):
+                 wc=50.0, ww=400.0, hu=False, level=True, labels=False, top=8, device=None, source=None):
         who = "VolumeComponents"
-        self._sides(who, n, h, w)
-        if self.n * self.h * self.w > 2 ** 31 - 1:
-            raise ValueError("%s: at most 2^31 - 1 voxels expected, got %d x %d x %d" % (who, self.n, self.h, self.w))
-        band = tuple(threshold) if isinstance(threshold, (tuple, list)) else (threshold, 32767)
-        if len(band) != 2 or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in band):
-            raise ValueError("%s: threshold: an integer lo or a pair (lo, hi) expected, got %r" % (who, threshold))
-        self.lo, self.hi = int(band[0]), int(band[1])
-        if not -32768 <= self.lo <= self.hi <= 32767:
-            raise ValueError("%s: threshold: -32768 <= lo <= hi <= 32767 expected, got %r" % (who, threshold))
-        if connectivity not in ops.COMPONENTS_CONNECTIVITY:
-            raise ValueError("%s: connectivity %r is not one of %s" % (who, connectivity, ops.COMPONENTS_CONNECTIVITY))
+        self._sides(who, n, h, w, linear=True)
+        self.lo, self.hi = _band(who, threshold)
+        _one_of(who, "connectivity", connectivity, ops.COMPONENTS_CONNECTIVITY)
         self.connectivity = int(connectivity)
-        for name, v, lo, hi in (("min_voxels", min_voxels, 1, 2 ** 31 - 1), ("largest", largest, 0, ops.COMPONENTS_MAX_TOP),
-                                ("top", top, 0, ops.COMPONENTS_MAX_TOP)):
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
-                raise ValueError("%s: %s: an integer in %d .. %d expected, got %r" % (who, name, lo, hi, v))
-        self.min_voxels, self.largest, self.top = int(min_voxels), int(largest), int(top)
-        self.seeds_host = None
-        if seeds is not None:
-            pts = np.asarray(list(seeds))
-            if pts.size == 0 or pts.ndim != 2 or pts.shape[1] != 3 or pts.dtype.kind not in "iu":
-                raise ValueError("%s: seeds: a sequence of integer (z, y, x), at least one, expected, got %r" % (who, seeds))
-            pts = pts.astype(np.int64)
-            if (pts < 0).any() or (pts >= np.array([self.n, self.h, self.w])).any():
-                raise ValueError("%s: a seed lies outside the volume (%d, %d, %d)" % (who, self.n, self.h, self.w))
-            self.seeds_host = ((pts[:, 0] * self.h + pts[:, 1]) * self.w + pts[:, 2]).astype(np.int32)
-        self.background, self.hu, self.window = bool(background), bool(hu), (float(wc), float(ww))
-        self.want_level, self.want_labels = bool(level), bool(labels)
-        self.fill = (-1024 if self.hu else 0) if fill is None else int(fill)
+        self.min_voxels = _int_in(who, "min_voxels", min_voxels, 1, 2 ** 31 - 1)
+        self.largest, self.top = (_int_in(who, name, v, 0, ops.COMPONENTS_MAX_TOP) for name, v in (("largest", largest), ("top", top)))
+        self.seeds_host = None if seeds is None else _voxel_indices(who, "seeds", seeds, self.n, self.h, self.w).astype(np.int32)
+        self._shown(wc, ww, hu, level, fill)
+        self.background, self.want_labels = bool(background), bool(labels)
         if not -32768 <= self.fill <= 32767:
             raise ValueError("%s: fill %d is not an int16 value" % (who, self.fill))
         v = self.n * self.h * self.w
         self.nbytes = (2 + 4 + 4 + 1) * v + (2 + (1 if self.want_level else 0)) * v + 4 * (8 + 2 * self.top) + \
             (0 if self.seeds_host is None else self.seeds_host.nbytes)
-        self._resident(device)
-        self.seeds = self._labels = self._sizes = self._keep = None      # on the device from the first chunk / result on
+        self.seeds = self._labels = self._sizes = self._keep = None      # on the device from `_upload` / the first result on
+        self._reads(device, source)
 
     def _upload(self):
         if self.seeds_host is not None:
@@ -1203,15 +1267,11 @@ def check_components_stats(stats):
 
 def components_volume(volume, threshold, batch=64, device=None, **options):
     """The components view of a volume that already exists, the twin of `reformat_volume`: int16 [N, H, W], a host array / CPU
-    tensor (chunks of `batch` slices cross PCIe one after another) or a device tensor; threshold and the options as
-    `VolumeComponents`.  Returns what `VolumeComponents.result` returns, of the input's kind; a result that comes back to the
-    host has had its error flag checked."""
-    def make(n, h, w, dev):      # (the device is resolved here: the chunk loop runs under it)
-        return VolumeComponents(n, h, w, threshold, device=torch.device("cuda", torch.cuda.current_device()) if dev is None else dev,
-                                **options)
-
-    # host chunks go to `update` as they are: it copies them into the resident volume, the only time they cross PCIe
-    out = _view_of_volume("components_volume", volume, batch, device, make, upload=False)
+    tensor (chunks of `batch` slices cross PCIe one after another) or a device tensor (read where it is when it is contiguous);
+    threshold and the options as `VolumeComponents`.  Returns what `VolumeComponents.result` returns, of the input's kind; a
+    result that comes back to the host has had its error flag checked."""
+    out = _view_of_volume("components_volume", volume, batch, device, whole=True,
+                          make=lambda n, h, w, dev: VolumeComponents(n, h, w, threshold, device=dev, **options))
     if not torch.is_tensor(out["stats"]) or not out["stats"].is_cuda:
         check_components_stats(out["stats"])
     return out
@@ -1230,9 +1290,7 @@ def centreline_penalty(radius, far=1, near=64):
     r = int(radius)
     if isinstance(radius, bool) or r != radius or not 1 <= r <= ops.CENTRELINE_MAX_RADIUS:
         raise ValueError("centreline_penalty: radius: an integer in 1 .. %d expected, got %r" % (ops.CENTRELINE_MAX_RADIUS, radius))
-    for name, v in (("far", far), ("near", near)):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= v <= 4095:
-            raise ValueError("centreline_penalty: %s: an integer in 1 .. 4095 expected, got %r" % (name, v))
+    far, near = _int_in("centreline_penalty", "far", far, 1, 4095), _int_in("centreline_penalty", "near", near, 1, 4095)
     c = np.arange(r * r + 1, dtype=np.float64)
     pen = np.floor(far + (near - far) * (1.0 - np.sqrt(c) / r) ** 2 + 0.5)
     pen[0] = near
@@ -1271,55 +1329,41 @@ def smooth_centreline(points, window=5):
     return (total[int(window):] - total[:-int(window)]) / float(window)
 
 
-class VolumeCentreline(_ResidentVolume):
+class VolumeCentreline(_VolumeView):
     """The vessel centreline from a start voxel to each of up to 64 end voxels of an int16 volume [n, h, w] that arrives in chunks
     and stays on the device (`ops.centreline_clearance` / `centreline_field` / `centreline_trace`, csrc/centreline.hip): the
-    cheapest 26-connected path through the foreground when a move into a voxel costs its length times a penalty that falls with
-    the voxel's distance from the vessel wall -- the path `curved_lines` wants.  threshold: lo, or (lo, hi), as `VolumeComponents`;
+    cheapest 26-connected path through the foreground when a move into a voxel costs its length times a penalty that falls with the
+    voxel's distance from the vessel wall -- the path `curved_lines` wants.  threshold: lo, or (lo, hi), as `VolumeComponents`;
     start and ends: (z, y, x) voxels, e.g. from `ray_voxel` / `line_voxel` (a click is not snapped to the vessel: it must lie on
     foreground); radius R in 1 .. 32 caps the clearance (in pixels); aspect = slice spacing / pixel spacing scales z in the
     clearance and the step lengths (`centreline_steps`); penalty: a uint16 table [R^2 + 1] (default `centreline_penalty(R)`);
     max_points: the longest path in voxels (default 4 (n + h + w)); smooth: the window of `smooth_centreline`.  cpr = a dict with
     any of angles, cols, depth, pitch (as `curved_lines`), sampling, mode (as `VolumeReformatter`) adds the curved reformat along
-    every end's smoothed path, one `ops.reformat_lines` launch per end on the resident volume, in the window (wc, ww) / `hu`.
-    `update(pix_chunk, n0)` copies a chunk in, in any order; `result()` raises unless every slice has arrived exactly once since
-    the last `reset()` -> {"paths": int32 [E, max_points] (linear indices, end first, -1 beyond the count), "counts": int32 [E],
-    "points": a list of float64 [M, 3] (z, y, x), start to end, smoothed, "clearance": uint16 [n, h, w] (clearance=True) or None,
-    "stats": int32 [8] (`ops.CENTRELINE_STATS`), and with cpr "cpr": [{"values": int16 [A, rows, cols], "level": uint8 or None}]} on
-    the device.  It reads the counts on the host (one synchronisation beyond those of the relaxation) and raises ValueError for a
-    start on background, an end on background or in another component, or a path longer than max_points, and RuntimeError when the
-    field saturated or the error flag is set.  `.nbytes`: the device memory held (the volume, the scratch and the clearance at 2
-    bytes per voxel, the field at 4, the tables) plus paths and counts, known before the first chunk; the cpr planes are not in
-    it (their rows follow the length of the path).  Exact integer arithmetic on the current stream up to the path; the smoothing
-    is float64 on the host."""
+    every end's smoothed path, one `ops.reformat_lines` launch per end on the resident volume, in the window (wc, ww) / `hu`. The
+    volume, `source=`, `update` and `reset` as `_VolumeView` has them; `result()` -> {"paths": int32 [E, max_points] (linear
+    indices, end first, -1 beyond the count), "counts": int32 [E], "points": a list of float64 [M, 3] (z, y, x), start to end,
+    smoothed, "clearance": uint16 [n, h, w] (clearance=True) or None, "stats": int32 [8] (`ops.CENTRELINE_STATS`), and with cpr
+    "cpr": [{"values": int16 [A, rows, cols], "level": uint8 or None}]} on the device.  It reads the counts on the host (one
+    synchronisation beyond those of the relaxation) and raises ValueError for a start on background, an end on background or in
+    another component, or a path longer than max_points, and RuntimeError when the field saturated or the error flag is
+    set.  `.nbytes`: the device memory held (the volume, unless it is a source's, the scratch and the clearance at 2 bytes per
+    voxel, the field at 4, the tables) plus paths and counts, known before the first chunk; the cpr planes are not in it (their rows
+    follow the length of the path).  Exact integer arithmetic on the current stream up to the path; the smoothing is float64 on the
+    host."""
 
     def __init__(self, n, h, w, threshold, start, ends, radius=8, aspect=1.0, penalty=None, max_points=None, smooth=5, cpr=None,
-                 clearance=False, rounds_per_call=16, max_rounds=4096, fill=None, wc=50.0, ww=400.0, hu=False, level=True, device=None):
+                 clearance=False, rounds_per_call=16, max_rounds=4096, fill=None, wc=50.0, ww=400.0, hu=False, level=True, device=None,
+                 source=None):
         who = "VolumeCentreline"
-        self._sides(who, n, h, w)
+        self._sides(who, n, h, w, linear=True)
         v = self.n * self.h * self.w
-        if v > 2 ** 31 - 1:
-            raise ValueError("%s: at most 2^31 - 1 voxels expected, got %d x %d x %d" % (who, self.n, self.h, self.w))
-        band = tuple(threshold) if isinstance(threshold, (tuple, list)) else (threshold, 32767)
-        if len(band) != 2 or any(isinstance(t, bool) or not isinstance(t, (int, np.integer)) for t in band):
-            raise ValueError("%s: threshold: an integer lo or a pair (lo, hi) expected, got %r" % (who, threshold))
-        self.lo, self.hi = int(band[0]), int(band[1])
-        if not -32768 <= self.lo <= self.hi <= 32767:
-            raise ValueError("%s: threshold: -32768 <= lo <= hi <= 32767 expected, got %r" % (who, threshold))
-        pts = np.asarray([tuple(start)] + [tuple(e) for e in ends])
-        if pts.ndim != 2 or pts.shape[1] != 3 or pts.dtype.kind not in "iu" or not 2 <= len(pts) <= 1 + ops.CENTRELINE_MAX_ENDS:
-            raise ValueError("%s: start: an integer (z, y, x), ends: 1 .. %d of them expected, got %r, %r"
-                             % (who, ops.CENTRELINE_MAX_ENDS, start, ends))
-        pts = pts.astype(np.int64)
-        if (pts < 0).any() or (pts >= np.array([self.n, self.h, self.w])).any():
-            raise ValueError("%s: the start or an end lies outside the volume (%d, %d, %d)" % (who, self.n, self.h, self.w))
-        index = (pts[:, 0] * self.h + pts[:, 1]) * self.w + pts[:, 2]
+        self.lo, self.hi = _band(who, threshold)
+        index = _voxel_indices(who, "start and ends", [tuple(start)] + [tuple(e) for e in ends], self.n, self.h, self.w, 2,
+                               1 + ops.CENTRELINE_MAX_ENDS)
         self.start, self.ends_host = int(index[0]), index[1:].astype(np.int32)
-        for name, t, lo_, hi_ in (("radius", radius, 1, ops.CENTRELINE_MAX_RADIUS), ("rounds_per_call", rounds_per_call, 1, ops.CENTRELINE_MAX_ROUNDS),
-                                  ("max_rounds", max_rounds, 1, ops.CENTRELINE_MAX_ROUNDS)):
-            if isinstance(t, bool) or not isinstance(t, (int, np.integer)) or not lo_ <= t <= hi_:
-                raise ValueError("%s: %s: an integer in %d .. %d expected, got %r" % (who, name, lo_, hi_, t))
-        self.radius, self.rounds_per_call, self.max_rounds = int(radius), int(rounds_per_call), int(max_rounds)
+        self.radius = _int_in(who, "radius", radius, 1, ops.CENTRELINE_MAX_RADIUS)
+        self.rounds_per_call = _int_in(who, "rounds_per_call", rounds_per_call, 1, ops.CENTRELINE_MAX_ROUNDS)
+        self.max_rounds = _int_in(who, "max_rounds", max_rounds, 1, ops.CENTRELINE_MAX_ROUNDS)
         self.aspect, self.zq = _centreline_aspect(who, aspect)
         self.steps = centreline_steps(self.aspect)
         pen = centreline_penalty(self.radius) if penalty is None else np.asarray(penalty)
@@ -1327,9 +1371,7 @@ class VolumeCentreline(_ResidentVolume):
             raise ValueError("%s: penalty: %d integers in 1 .. 4095 expected" % (who, self.radius ** 2 + 1))
         self.pen_host = np.clip(pen, 1, 4095).astype(np.uint16)
         max_points = min(v, 4 * (self.n + self.h + self.w), ops.CENTRELINE_MAX_POINTS) if max_points is None else max_points
-        if isinstance(max_points, bool) or not isinstance(max_points, (int, np.integer)) or not 1 <= max_points <= ops.CENTRELINE_MAX_POINTS:
-            raise ValueError("%s: max_points: an integer in 1 .. %d expected, got %r" % (who, ops.CENTRELINE_MAX_POINTS, max_points))
-        self.max_points = int(max_points)
+        self.max_points = _int_in(who, "max_points", max_points, 1, ops.CENTRELINE_MAX_POINTS)
         smooth_centreline(np.zeros((1, 3)), smooth)
         self.smooth = int(smooth)
         self.cpr = None
@@ -1342,14 +1384,13 @@ class VolumeCentreline(_ResidentVolume):
             curved_lines(self.n, self.h, self.w, np.array([[0.0, 0.0, 0.0], [0.0, 0.0, 1.0]]), aspect=self.aspect,
                          **{k: self.cpr[k] for k in ("angles", "cols", "depth", "pitch")})      # (the options, checked now)
         self.want_clearance = bool(clearance)
-        self.hu, self.window, self.want_level = bool(hu), (float(wc), float(ww)), bool(level)
-        self.fill = (-1024 if self.hu else 0) if fill is None else int(fill)
+        self._shown(wc, ww, hu, level, fill)
         tz, ty, tx = ops.CENTRELINE_TILE
         tiles = -(-self.n // tz) * -(-self.h // ty) * -(-self.w // tx)
         e = len(self.ends_host)
         self.nbytes = (2 + 2 + 2 + 4) * v + self.pen_host.nbytes + 4 * e + 8 * tiles + 4 * self.max_rounds + 4 * e * (self.max_points + 1) + 32
-        self._resident(device)
-        self.pen = self.ends = self._scratch = self._clear = self._dist = None      # on the device from the first chunk / result on
+        self.pen = self.ends = self._scratch = self._clear = self._dist = None      # on the device from `_upload` / the first result on
+        self._reads(device, source)
 
     def _upload(self):
         self.pen = torch.from_numpy(self.pen_host.view(np.int16)).to(self.device).view(torch.uint16)
@@ -1390,23 +1431,18 @@ class VolumeCentreline(_ResidentVolume):
                 if len(p) < 2:
                     raise ValueError("%s: cpr: an end is the start itself: there is no line to reformat along" % who)
                 lines = curved_lines(self.n, self.h, self.w, p, aspect=self.aspect, **{k: self.cpr[k] for k in ("angles", "cols", "depth", "pitch")})
-                table = ops.LineTable(lines[0], lines.cols, lines[1], self.device)
-                values, level = ops.reformat_lines(self.volume, table, table.u, table.t, self.cpr["mode"], fill=self.fill, wc=self.window[0],
-                                                   ww=self.window[1], hu=self.hu, sampling=self.cpr["sampling"], want_level=self.want_level)
-                out["cpr"].append({"values": values, "level": level})
+                out["cpr"].append(self._reformat(ops.LineTable(lines[0], lines.cols, lines[1], self.device), self.cpr["mode"],
+                                                 self.cpr["sampling"]))
         return out
 
 
 def centreline_volume(volume, threshold, start, ends, batch=64, device=None, **options):
     """The centreline view of a volume that already exists, the twin of `components_volume`: int16 [N, H, W], a host array / CPU
-    tensor (chunks of `batch` slices cross PCIe one after another) or a device tensor; threshold, start, ends and the options as
-    `VolumeCentreline`.  Returns what `VolumeCentreline.result` returns, of the input's kind."""
-    def make(n, h, w, dev):      # (the device is resolved here: the chunk loop runs under it)
-        return VolumeCentreline(n, h, w, threshold, start, ends, device=torch.device("cuda", torch.cuda.current_device()) if dev is None else dev,
-                                **options)
-
-    # host chunks go to `update` as they are: it copies them into the resident volume, the only time they cross PCIe
-    return _view_of_volume("centreline_volume", volume, batch, device, make, upload=False)
+    tensor (chunks of `batch` slices cross PCIe one after another) or a device tensor (read where it is when it is contiguous);
+    threshold, start, ends and the options as `VolumeCentreline`.  Returns what `VolumeCentreline.result` returns, of the input's
+    kind."""
+    return _view_of_volume("centreline_volume", volume, batch, device, whole=True,
+                           make=lambda n, h, w, dev: VolumeCentreline(n, h, w, threshold, start, ends, device=dev, **options))
 
 
 def subtract_volume(cta, ct_hu, cta_is_hu=False, median=True, floor=0, ct_range=(None, None), wc=150.0, ww=300.0, level=True,
@@ -1456,6 +1492,29 @@ RENDER_OPTIONS = ("transfer", "detector", "wc", "ww", "hu", "sampling", "oversam
 RENDER3D_OPTIONS = ("transfer", "wc", "ww", "hu", "sampling", "shading", "aspect", "background", "stop", "surface", "depth", "cols")
 
 
+def _option_dict(name, value, allowed, required=(), needs=None):
+    """A dict option of `SeriesTranslator`, checked -> a copy of it ({} for None): every key of `required` and none outside
+    `allowed`.  needs = (what the options go with, that thing, what it is made of): options without the thing are refused, and
+    so is a thing with nothing in it."""
+    opts = dict(value or {})
+    if needs is not None and needs[1] is None:
+        if opts:
+            raise ValueError("SeriesTranslator: %s need %s" % (name, needs[0]))
+    elif needs is not None and not needs[1]:
+        raise ValueError("SeriesTranslator: %s needs at least one %s" % (needs[0], needs[2]))
+    elif not set(required) <= set(opts) or set(opts) - set(allowed):
+        raise ValueError("SeriesTranslator: %s %r: a dict with %sany of %s expected"
+                         % (name, value, "".join("%r, " % key for key in required), tuple(allowed)))
+    return opts
+
+
+# What `SeriesTranslator` knows of a display that is on: make(n, h, w) -> its view; result(view) -> its tree; angles: the output
+# gains the view's "angles"; reads: None for a view fed chunk by chunk, else the source ("cta", "sub", "vessels") whose
+# `ResidentVolume` a view on the whole volume reads; first: its result is made before the others', and its "values" are the
+# source "vessels" where a display reads that; check: what the finished tree is put through once it is on the host.
+_Display = collections.namedtuple("_Display", "make result angles reads first check", defaults=(False, None, False, None))
+
+
 def _angle_list(rotate):
     """`rotate` of SeriesTranslator / `angles` of rotate_volume: an int count of views around the full circle, or degrees."""
     if isinstance(rotate, (int, np.integer)) and not isinstance(rotate, bool):
@@ -1464,56 +1523,52 @@ def _angle_list(rotate):
 
 
 class SeriesTranslator:
-    """`SeriesTranslator(generator)(volume)`: int16 HU volume [N, H, W] (numpy array or CPU tensor, SimpleITK convention) ->
-    {"pix": int16 [N, H, W], "level": uint8 [N, H, W] or None}, of the input's kind.  project = "max" / "min" / "mean" (slab:
-    slices per axial slab, None: the whole volume) adds "projections": {axis: {"values": int16, "level": uint8 or None}} of
-    the synthesized volume (`SeriesProjector`), in the translator's own window and `hu` (their level whatever `level` says).
+    """`SeriesTranslator(generator)(volume)`: int16 HU volume [N, H, W] (numpy array or CPU tensor, SimpleITK convention) -> {"pix":
+    int16 [N, H, W], "level": uint8 [N, H, W] or None}, of the input's kind.  project = "max" / "min" / "mean" (slab: slices per
+    axial slab, None: the whole volume) adds "projections": {axis: {"values": int16, "level": uint8 or None}} of the synthesized
+    volume (`SeriesProjector`), in the translator's own window and `hu` (their level whatever `level` says).
     rotate = an int count of views around the full circle, or a sequence of degrees (rotate_mode: "max" / "min" / "mean", default
     `project` or "max"; rotate_sampling "nearest" / "bilinear" and rotate_oversample = steps per voxel, as `SeriesRotator`) adds
     "rotation": {"values": int16 [A, N, D], "level": uint8, "angles": float64 [A]}.
     subtract=True adds "sub" (int16 [N, H, W]: synthesized minus input, `ops.subtract_slices` with sub_median, sub_floor,
     sub_ct_range) and "sub_level" (uint8 in sub_window = (wc, ww) of a HU difference, None with level=False).
     project_source="sub" (needs subtract=True) projects and rotates the subtraction volume instead of the synthesized one, its
-    levels in sub_window with hu=True: the bone-free MIP.  Without `subtract` nothing of this is allocated or launched.
-    slabs = a dict of `SeriesSlabs` keyword arguments (thick, and any of step, mode, axes) adds "slabs": {axis: {"values":
-    int16 [J, ...], "level": uint8}}, the sliding thin-slab projections of the same source in the same window, copied back once
-    after the last chunk; with slabs=None nothing of it is allocated or launched.
+    levels in sub_window with hu=True: the bone-free MIP.
+    slabs = a dict of `SeriesSlabs` keyword arguments (thick, and any of step, mode, axes) adds "slabs": {axis: {"values": int16 [J,
+    ...], "level": uint8}}, the sliding thin-slab projections of the same source in the same window, copied back once after the last
+    chunk.
     depth=True (depth_cue: 0 .. 256) applies to whichever of `project` / `rotate` is on, with mode "max" / "min": their dicts gain
-    "depth" (int16) and "cued" (uint8, the depth-cued level), as `SeriesProjector` / `SeriesRotator` give them, staged back with
-    the other planes; the slabs have no depth planes.  With depth=False nothing of it is allocated or launched.
+    "depth" (int16) and "cued" (uint8, the depth-cued level), as `SeriesProjector` / `SeriesRotator` give them, staged back with the
+    other planes; the slabs have no depth planes.
     render = an int count of views around the full circle, or a sequence of degrees (render_options: a dict of `SeriesRenderer`
     keyword arguments -- transfer, detector, wc, ww, hu (default: that of the source), sampling, oversample, background, stop,
     surface, depth) adds "render": {"rgb": uint8 [A, N, D, 3], "opacity": uint8, "depth": int16 (unless depth=False), "angles":
-    float64 [A]}, the volume-rendered views of the same source (`project_source`), copied back once after the last chunk.  With
-    render=None nothing of it is allocated or launched.
-    reformat = {name: a `LineSet`, a pair (table, T), or a callable (n, h, w) -> either} (reformat_options: a dict with any of
-    mode, sampling, fill, cols, as `VolumeReformatter`) adds "reformat": {name: {"values": int16 [..., U], "level": uint8}}:
-    oblique planes, tumbling views and curved reformats of the same source (`project_source`, so "sub" gives bone-free reformats
-    in sub_window).  Their rows cross slices, so the source volume is kept on the device (`VolumeReformatter.nbytes`), every table
-    is one launch after the last chunk, and the planes are copied back once.  With reformat=None nothing of it is allocated or
-    launched.
-    render3d = tables as `reformat` (render3d_options: a dict of `VolumeRenderer` keyword arguments -- transfer, wc, ww, hu (default:
-    that of the source), sampling, shading, aspect, background, stop, surface, depth, cols) adds "render3d": {name: {"rgb": uint8
-    [..., U, 3], "opacity": uint8, "depth": int16 or None}}: the shaded volume-rendered views of the same source
-    (`project_source`) along rays in any direction, one launch per table after the last chunk, copied back once.  It keeps the
-    source volume on the device (`VolumeRenderer.nbytes`); with `reformat` on as well the two hold a copy each (sharing one is not
-    built).  With render3d=None nothing of it is allocated or launched.
+    float64 [A]}, the volume-rendered views of the same source (`project_source`), copied back once after the last chunk.
+    reformat = {name: a `LineSet`, a pair (table, T), or a callable (n, h, w) -> either} (reformat_options: a dict with any of mode,
+    sampling, fill, cols, as `VolumeReformatter`) adds "reformat": {name: {"values": int16 [..., U], "level": uint8}}: oblique
+    planes, tumbling views and curved reformats of the same source (`project_source`, so "sub" gives bone-free reformats in
+    sub_window).  Their rows cross slices, so every table is one launch on the whole volume after the last chunk, and the planes are
+    copied back once.
+    render3d = tables as `reformat` (render3d_options: a dict of `VolumeRenderer` keyword arguments -- transfer, wc, ww, hu
+    (default: that of the source), sampling, shading, aspect, background, stop, surface, depth, cols) adds "render3d": {name:
+    {"rgb": uint8 [..., U, 3], "opacity": uint8, "depth": int16 or None}}: the shaded volume-rendered views of the same source
+    (`project_source`) along rays in any direction, one launch per table after the last chunk, copied back once.
     components = a dict of `VolumeComponents` keyword arguments (threshold, and any of connectivity, min_voxels, largest, seeds,
     background, fill, wc, ww, hu, level, labels, top) adds "vessels": {"values": int16 [N, H, W], "level": uint8 or None, "labels":
     int32 or None, "top": int32 [top, 2], "stats": int32 [8]}, the volume of components_source ("cta" or "sub", which needs
     subtract=True; default: what `project_source` shows, "cta" for "vessels") with only the wanted connected components left, in
-    that source's window and `hu`, labelled after the last chunk and copied back once; a stats[6] other than 0 raises.  It keeps
-    the source volume on the device (`VolumeComponents.nbytes`).  project_source="vessels" (needs components) makes every other
-    display show that cleaned volume: the chunk loop then feeds only the components view, and the cleaned volume is handed to the
-    other displays after the last chunk, device to device, in chunks of `batch` slices.  With components=None nothing of it is
-    allocated or launched.
+    that source's window and `hu`, labelled after the last chunk and copied back once; a stats[6] other than 0 raises.
+    project_source="vessels" (needs components) makes every other display show that cleaned volume: the chunk loop then feeds only
+    the components' source, and after the last chunk the views on the whole volume read the cleaned tensor where it is and the
+    others get its slices in chunks of `batch`.
     centreline = a dict of `VolumeCentreline` keyword arguments (threshold, start, ends, and any of radius, aspect, penalty,
     max_points, smooth, cpr, clearance, rounds_per_call, max_rounds, fill, wc, ww, hu, level) adds "centreline": {"paths", "counts",
-    "points": a list of float64 [M, 3], "clearance", "stats", and with cpr "cpr": [{"values", "level"}]}, the vessel centreline
-    from `start` to every end through the same source as the other displays (`project_source`; with "vessels" the cleaned volume,
-    handed over device to device), traced after the last chunk and copied back once.  It keeps the source volume on the device
-    (`VolumeCentreline.nbytes`) and waits for the relaxation on the host.  With centreline=None nothing of it is allocated or
-    launched.
+    "points": a list of float64 [M, 3], "clearance", "stats", and with cpr "cpr": [{"values", "level"}]}, the vessel centreline from
+    `start` to every end through the same source as the other displays (`project_source`), traced after the last chunk and copied
+    back once; it waits for the relaxation on the host.
+    reformat, render3d, components and centreline read the whole volume, which stays on the device: one `ResidentVolume` per source
+    that any of them reads (2 N H W bytes, fed once per chunk), beside what each view holds itself (its `.nbytes`).
+    A display that is off (None; depth=False, subtract=False) allocates and launches nothing.
 
     size: the side(s) the generator runs at (None: the volume's own); a volume of another size is resized (nearest) on the way
     in and comes back at its own size.  wc / ww: the window of the 8-bit level; hu: pixels minus 1024 (SimpleITK) instead of
@@ -1527,17 +1582,11 @@ class SeriesTranslator:
                  render3d_options=None, components=None, components_source=None, centreline=None):
         if int(batch) < 1:
             raise ValueError("SeriesTranslator: batch >= 1 expected")
-        self.centreline = None if centreline is None else dict(centreline)
-        if self.centreline is not None and (not {"threshold", "start", "ends"} <= set(self.centreline)
-                                            or set(self.centreline) - set(CENTRELINE_OPTIONS)):
-            raise ValueError("SeriesTranslator: centreline %r: a dict with 'threshold', 'start', 'ends' and any of %s expected"
-                             % (centreline, CENTRELINE_OPTIONS))
-        self.components = None if components is None else dict(components)
+        self.centreline = centreline if centreline is None else _option_dict("centreline", centreline, CENTRELINE_OPTIONS,
+                                                                             ("threshold", "start", "ends"))
+        self.components = components if components is None else _option_dict("components", components, COMPONENTS_OPTIONS, ("threshold",))
         if self.components is None and components_source is not None:
             raise ValueError("SeriesTranslator: components_source needs components")
-        if self.components is not None and ("threshold" not in self.components or set(self.components) - set(COMPONENTS_OPTIONS)):
-            raise ValueError("SeriesTranslator: components %r: a dict with 'threshold' and any of %s expected"
-                             % (components, COMPONENTS_OPTIONS))
         if project_source == "vessels" and self.components is None:
             raise ValueError("SeriesTranslator: project_source 'vessels' needs components")
         if components_source is None:
@@ -1547,26 +1596,11 @@ class SeriesTranslator:
                              % (components_source, COMPONENTS_SOURCES))
         self.components_source = components_source
         self.render3d = None if render3d is None else dict(render3d)
-        self.render3d_options = dict(render3d_options or {})
-        if self.render3d is None and self.render3d_options:
-            raise ValueError("SeriesTranslator: render3d_options need render3d")
-        if self.render3d is not None and (not self.render3d or set(self.render3d_options) - set(RENDER3D_OPTIONS)):
-            raise ValueError("SeriesTranslator: render3d needs at least one table, and render3d_options %r a dict with any of %s"
-                             % (render3d_options, RENDER3D_OPTIONS))
+        self.render3d_options = _option_dict("render3d_options", render3d_options, RENDER3D_OPTIONS, needs=("render3d", self.render3d, "table"))
         self.reformat = None if reformat is None else dict(reformat)
-        self.reformat_options = dict(reformat_options or {})
-        if self.reformat is None and self.reformat_options:
-            raise ValueError("SeriesTranslator: reformat_options need reformat")
-        if self.reformat is not None and (not self.reformat or set(self.reformat_options) - set(REFORMAT_OPTIONS)):
-            raise ValueError("SeriesTranslator: reformat needs at least one table, and reformat_options %r a dict with any of %s"
-                             % (reformat_options, REFORMAT_OPTIONS))
+        self.reformat_options = _option_dict("reformat_options", reformat_options, REFORMAT_OPTIONS, needs=("reformat", self.reformat, "table"))
         self.render = None if render is None else _angle_list(render)
-        self.render_options = dict(render_options or {})
-        if self.render is None and self.render_options:
-            raise ValueError("SeriesTranslator: render_options need render")
-        if self.render is not None and (not self.render or set(self.render_options) - set(RENDER_OPTIONS)):
-            raise ValueError("SeriesTranslator: render needs at least one angle, and render_options %r a dict with any of %s"
-                             % (render_options, RENDER_OPTIONS))
+        self.render_options = _option_dict("render_options", render_options, RENDER_OPTIONS, needs=("render", self.render, "angle"))
         if project_source not in PROJECT_SOURCES or (project_source == "sub" and not subtract):
             raise ValueError("SeriesTranslator: project_source %r: one of %s expected, and 'sub' needs subtract=True"
                              % (project_source, PROJECT_SOURCES))
@@ -1588,9 +1622,7 @@ class SeriesTranslator:
         for mode in ([project] if project is not None else []) + ([self.rotate_mode] if self.rotate is not None else []):
             _check_depth("SeriesTranslator", self.depth, self.depth_cue, mode)
         self.rotate_sampling, self.rotate_oversample = rotate_sampling, int(rotate_oversample)
-        self.slabs = None if slabs is None else dict(slabs)
-        if self.slabs is not None and ("thick" not in self.slabs or set(self.slabs) - {"thick", "step", "mode", "axes"}):
-            raise ValueError("SeriesTranslator: slabs %r: a dict with 'thick' and any of 'step', 'mode', 'axes' expected" % (slabs,))
+        self.slabs = slabs if slabs is None else _option_dict("slabs", slabs, ("thick", "step", "mode", "axes"), ("thick",))
         self.window = (float(wc), float(ww))
         self.generator = generator
         self.batch = int(batch)
@@ -1612,50 +1644,43 @@ class SeriesTranslator:
         self._planes = {"pix": torch.int16, "level": torch.uint8 if self.level else None}
         if self.subtract:
             self._planes.update(sub=torch.int16, sub_level=torch.uint8 if self.level else None)
-        # the displays that are on, by output key: (the view of an (n, h, w) volume, its result, whether the output gains "angles")
+        # the displays that are on, by output key (`_Display`); a view on the whole volume reads the resident volume of its source
+        dev, src, shown = self.device, self.project_source, self._shows(self.project_source)
         self._displays = {}
         if self.project is not None:
-            self._displays["projections"] = (
-                lambda n, h, w: SeriesProjector(n, h, w, mode=self.project, slab=self.slab, device=self.device, depth=self.depth,
-                                                cue=self.depth_cue),
-                lambda view: view.result(*self._view_window(), hu=self._view_hu()), False)
+            self._displays["projections"] = _Display(
+                lambda n, h, w: SeriesProjector(n, h, w, mode=self.project, slab=self.slab, device=dev, depth=self.depth, cue=self.depth_cue),
+                lambda view: view.result(shown["wc"], shown["ww"], hu=shown["hu"]))
         if self.rotate is not None:
-            self._displays["rotation"] = (
-                lambda n, h, w: SeriesRotator(n, h, w, self.rotate, mode=self.rotate_mode, **self._view_options(),
-                                              device=self.device, sampling=self.rotate_sampling, oversample=self.rotate_oversample,
-                                              depth=self.depth, cue=self.depth_cue),
-                SeriesRotator.result, True)
+            self._displays["rotation"] = _Display(
+                lambda n, h, w: SeriesRotator(n, h, w, self.rotate, mode=self.rotate_mode, **shown, device=dev, sampling=self.rotate_sampling,
+                                              oversample=self.rotate_oversample, depth=self.depth, cue=self.depth_cue),
+                SeriesRotator.result, angles=True)
         if self.slabs is not None:
-            self._displays["slabs"] = (
-                lambda n, h, w: SeriesSlabs(n, h, w, **self._view_options(), device=self.device, **self.slabs),
-                SeriesSlabs.result, False)
+            self._displays["slabs"] = _Display(lambda n, h, w: SeriesSlabs(n, h, w, **shown, device=dev, **self.slabs), SeriesSlabs.result)
         if self.render is not None:
-            self._displays["render"] = (
-                lambda n, h, w: SeriesRenderer(n, h, w, self.render, device=self.device, **{"hu": self._view_hu(), **self.render_options}),
-                SeriesRenderer.result, True)
+            self._displays["render"] = _Display(
+                lambda n, h, w: SeriesRenderer(n, h, w, self.render, device=dev, **{"hu": shown["hu"], **self.render_options}),
+                SeriesRenderer.result, angles=True)
         if self.reformat is not None:
-            self._displays["reformat"] = (
-                lambda n, h, w: VolumeReformatter(n, h, w, self.reformat, **self._view_options(), device=self.device,
-                                                  **self.reformat_options),
-                VolumeReformatter.result, False)
+            self._displays["reformat"] = _Display(
+                lambda n, h, w, **source: VolumeReformatter(n, h, w, self.reformat, **shown, **self.reformat_options, **source),
+                VolumeReformatter.result, reads=src)
         if self.render3d is not None:
-            self._displays["render3d"] = (
-                lambda n, h, w: VolumeRenderer(n, h, w, self.render3d, device=self.device,
-                                               **{"hu": self._view_hu(), **self.render3d_options}),
-                VolumeRenderer.result, False)
-        if self.components is not None:
-            # its window and `hu` are those of its own source, which is also what the other displays show with "vessels"
-            sub = self.components_source == "sub"
-            wc_, ww_ = self.sub_window if sub else self.window
-            self._displays["vessels"] = (
-                lambda n, h, w: VolumeComponents(n, h, w, device=self.device,
-                                                 **{"wc": wc_, "ww": ww_, "hu": True if sub else self.hu, **self.components}),
-                VolumeComponents.result, False)
+            self._displays["render3d"] = _Display(
+                lambda n, h, w, **source: VolumeRenderer(n, h, w, self.render3d, **{"hu": shown["hu"], **self.render3d_options}, **source),
+                VolumeRenderer.result, reads=src)
+        if self.components is not None:      # (in the window of its own source, which is what the others show with "vessels")
+            self._displays["vessels"] = _Display(
+                lambda n, h, w, **source: VolumeComponents(n, h, w, **{**self._shows(self.components_source), **self.components}, **source),
+                VolumeComponents.result, reads=self.components_source, first=True,
+                check=lambda tree: check_components_stats(tree["stats"]))      # (on the host by then: no extra synchronisation)
         if self.centreline is not None:
-            self._displays["centreline"] = (
-                lambda n, h, w: VolumeCentreline(n, h, w, device=self.device, **{**self._view_options(), **self.centreline}),
-                VolumeCentreline.result, False)
-        self._views, self._view_host = {}, {}      # by output key: the view, the page-locked copy of its result
+            self._displays["centreline"] = _Display(
+                lambda n, h, w, **source: VolumeCentreline(n, h, w, **{**shown, **self.centreline}, **source),
+                VolumeCentreline.result, reads=src)
+        # by output key: the view, the page-locked copy of its result; by source: the resident volume of the views that read it
+        self._views, self._view_host, self._residents = {}, {}, {}
         # host seconds of the last call (scripts/export_bench.py): waiting to get a slot back, copying into the input slots,
         # copying out of the output slots, the whole call
         self.stats = {"wait": 0.0, "stage_in": 0.0, "stage_out": 0.0, "total": 0.0}
@@ -1689,7 +1714,11 @@ class SeriesTranslator:
         self._stage(h, w)
         with torch.cuda.device(self.device):
             cur = torch.cuda.current_stream()
-            views = {key: self._view_for(key, n, h, w) for key in self._displays}
+            residents = {d.reads: self._kept(self._residents, d.reads, n, h, w, lambda: ResidentVolume(n, h, w, self.device))
+                         for d in self._displays.values() if d.reads is not None}
+            views = {key: self._kept(self._views, key, n, h, w, lambda: d.make(
+                n, h, w, **({} if d.reads is None else {"source": residents[d.reads]}))) for key, d in self._displays.items()}
+            streaming = [view for key, view in views.items() if self._displays[key].reads is None]
             in_free = [None] * SLOTS       # event: the slot's H2D copy has drained, the host may rewrite it
             pending = [None] * SLOTS       # (event, start, stop): the slot's D2H copy, not yet moved into the result
 
@@ -1732,12 +1761,14 @@ class SeriesTranslator:
                         planes["sub"], planes["sub_level"] = ops.subtract_slices(
                             planes["pix"], dev_hu, cta_is_hu=self.hu, median=self.sub_median, floor=self.sub_floor,
                             ct_range=self.sub_ct_range, wc=self.sub_window[0], ww=self.sub_window[1], want_level=self.level)
-                    src = planes["sub" if self.project_source == "sub" else "pix"]
-                    for key, view in views.items():
-                        if key == "vessels":
-                            view.update(planes["sub" if self.components_source == "sub" else "pix"], s)
-                        elif self.project_source != "vessels":      # (with "vessels" they are fed after the last chunk)
-                            view.update(src, s)
+                    # a source feeds its resident volume once, whatever number of views read it ("vessels" comes after the last chunk)
+                    sources = {"cta": planes["pix"], "sub": planes.get("sub")}
+                    for name, resident in residents.items():
+                        if name in sources:
+                            resident.update(sources[name], s)
+                    if self.project_source in sources:
+                        for view in streaming:
+                            view.update(sources[self.project_source], s)
                 computed = torch.cuda.Event()
                 computed.record(cur)
                 drain(slot)                          # the chunk that used this slot last: its D2H started two chunks ago
@@ -1753,18 +1784,19 @@ class SeriesTranslator:
             # drained, so that the copies run while the host drains (the reformats are one launch per table first: the whole
             # volume is on the device now).  An event per display: the host clones one display's planes while the next one's
             # are still being copied.
-            staged, trees = {}, {}
-            if "vessels" in views:
-                trees["vessels"] = self._displays["vessels"][1](views["vessels"])
-                if self.project_source == "vessels":
-                    # the cleaned volume to the other displays, device to device on this stream, in the chunks they are used to
-                    with torch.no_grad():
-                        for s, e, _ in plan_chunks(n, self.batch):
-                            for key, view in views.items():
-                                if key != "vessels":
-                                    view.update(trees["vessels"]["values"][s:e], s)
+            staged = {}
+            trees = {key: self._displays[key].result(view) for key, view in views.items() if self._displays[key].first}
+            if self.project_source == "vessels":
+                # the cleaned volume: the views on the whole volume read it where it is, the others get its slices in their chunks
+                cleaned, = (tree["values"] for tree in trees.values())
+                if "vessels" in residents:
+                    residents["vessels"].adopt(cleaned)
+                with torch.no_grad():
+                    for s, e, _ in plan_chunks(n, self.batch):
+                        for view in streaming:
+                            view.update(cleaned[s:e], s)
             for key, view in views.items():
-                tree = trees[key] if key in trees else self._displays[key][1](view)
+                tree = trees[key] if key in trees else self._displays[key].result(view)
                 host, copied = self._stage_view(key, tree), torch.cuda.Event()
                 copied.record(cur)
                 staged[key] = (host, copied)
@@ -1776,9 +1808,9 @@ class SeriesTranslator:
                 copied.synchronize()
                 stats["wait"] += clock() - t0
                 shown[key] = _tree_to(host, (lambda t: t.clone().numpy()) if is_np else (lambda t: t.clone()))
-                if key == "vessels":
-                    check_components_stats(shown[key]["stats"])      # on the host now: no extra synchronisation
-                if self._displays[key][2]:
+                if self._displays[key].check is not None:
+                    self._displays[key].check(shown[key])
+                if self._displays[key].angles:
                     angles = views[key].angles
                     shown[key]["angles"] = np.array(angles, dtype=np.float64) if is_np else torch.tensor(angles, dtype=torch.float64)
         # the forwards above ran fused conv + InstanceNorm launches: none may have given up (raises)
@@ -1788,20 +1820,22 @@ class SeriesTranslator:
         out.update(shown)
         return out
 
-    def _view_for(self, key, n, h, w):
-        """The view of display `key` for an (n, h, w) volume, kept between calls on volumes of one shape (and reset for the next)."""
-        view = self._views.get(key)
-        if view is None or (view.n, view.h, view.w) != (n, h, w):
-            view = self._views[key] = self._displays[key][0](n, h, w)
+    @staticmethod
+    def _kept(kept, key, n, h, w, make):
+        """`kept[key]`, a view or a resident volume, for an (n, h, w) volume: kept between calls on volumes of one shape (and reset
+        for the next), else made anew."""
+        item = kept.get(key)
+        if item is None or (item.n, item.h, item.w) != (n, h, w):
+            item = kept[key] = make()
         else:
-            view.reset()
-        return view
+            item.reset()
+        return item
 
     def _stage_view(self, key, tree):
         """Start the copies of a view's finished result into page-locked buffers, one per tensor of the tree (kept between calls
         while every tensor's place, shape and dtype stay as they are).  A view's device "angles" are not staged: the output's are
         made from the view's host list."""
-        if self._displays[key][2]:
+        if self._displays[key].angles:
             tree = {k: t for k, t in tree.items() if k != "angles"}
         dev, host = _tree_leaves(tree), self._view_host.get(key)
         if host is None or [(p, t.shape, t.dtype) for p, t in _tree_leaves(host)] != [(p, t.shape, t.dtype) for p, t in dev]:
@@ -1810,19 +1844,10 @@ class SeriesTranslator:
             buf.copy_(t, non_blocking=True)
         return host
 
-    def _view_options(self):
-        """The window and `hu` of the views that take them at construction."""
-        wc, ww = self._view_window()
-        return {"wc": wc, "ww": ww, "hu": self._view_hu()}
-
-    def _view_window(self):
-        """The window of the projections' and the rotation's levels: the subtraction's when that is what they show."""
-        return self.sub_window if self._view_source() == "sub" else self.window
-
-    def _view_hu(self):
-        """A subtraction value is a HU difference: 0 is the window's zero, whatever convention the synthesized pixels use."""
-        return True if self._view_source() == "sub" else self.hu
-
-    def _view_source(self):
-        """What the displays show: with "vessels" the cleaned copy of the components' own source."""
-        return self.components_source if self.project_source == "vessels" else self.project_source
+    def _shows(self, source):
+        """The window and `hu` of a display of `source`.  The subtraction has a window of its own, and its values are HU
+        differences: 0 is the window's zero, whatever convention the synthesized pixels use.  The cleaned volume "vessels" is shown
+        as the components' own source is."""
+        source = self.components_source if source == "vessels" else source
+        wc, ww = self.sub_window if source == "sub" else self.window
+        return {"wc": wc, "ww": ww, "hu": True if source == "sub" else self.hu}

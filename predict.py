@@ -232,6 +232,29 @@ def sts_options(parser, opts):
     return {"thick": {a: thick[a] for a in axes}, "step": {a: step[a] for a in axes}, "mode": opts.mip_mode, "axes": axes}
 
 
+def _band(parser, flag, text):
+    """"LO" or "LO,HI" -> (lo, hi) of a threshold band, hi = 32767 by default."""
+    try:
+        band = [int(v) for v in text.split(",")]
+    except ValueError:
+        parser.error("%s: whole numbers LO or LO,HI expected, got %r" % (flag, text))
+    band = band + [32767] if len(band) == 1 else band
+    if len(band) != 2 or not -32768 <= band[0] <= band[1] <= 32767:
+        parser.error("%s: -32768 <= LO <= HI <= 32767 expected, got %r" % (flag, text))
+    return tuple(band)
+
+
+def _voxels(parser, flag, texts):
+    """["Z,Y,X", ...] -> [(z, y, x), ...], whole numbers >= 0."""
+    try:
+        points = [tuple(int(v) for v in text.split(",")) for text in texts]
+    except ValueError:
+        parser.error("%s: whole numbers Z,Y,X expected, got %r" % (flag, texts))
+    if any(len(p) != 3 or min(p) < 0 for p in points):
+        parser.error("%s: three whole numbers Z,Y,X >= 0 expected, got %r" % (flag, texts))
+    return points
+
+
 def cc_options(parser, opts):
     """The `SeriesTranslator(components=...)` dict of --cc-output (None without it); bad values end in parser.error."""
     if opts.cc_output is None:
@@ -241,28 +264,14 @@ def cc_options(parser, opts):
         return None
     if opts.cc_threshold is None:
         parser.error("--cc-output needs --cc-threshold")
-    try:
-        band = [int(v) for v in opts.cc_threshold.split(",")]
-    except ValueError:
-        parser.error("--cc-threshold: whole numbers LO or LO,HI expected, got %r" % opts.cc_threshold)
-    band = band + [32767] if len(band) == 1 else band
-    if len(band) != 2 or not -32768 <= band[0] <= band[1] <= 32767:
-        parser.error("--cc-threshold: -32768 <= LO <= HI <= 32767 expected, got %r" % opts.cc_threshold)
     if opts.cc_min_voxels < 1 or not 0 <= opts.cc_largest <= 64:
         parser.error("--cc-min-voxels: at least 1 and --cc-largest: 0 .. 64 expected")
-    seeds = None
-    if opts.cc_seed is not None:
-        try:
-            seeds = [tuple(int(v) for v in text.split(",")) for text in opts.cc_seed]
-        except ValueError:
-            parser.error("--cc-seed: whole numbers Z,Y,X expected, got %r" % (opts.cc_seed,))
-        if any(len(p) != 3 or min(p) < 0 for p in seeds):
-            parser.error("--cc-seed: three whole numbers Z,Y,X >= 0 expected, got %r" % (opts.cc_seed,))
     if opts.cc_source == "sub" and opts.sub_output is None:
         parser.error("--cc-source sub needs --sub-output")
-    return {"threshold": tuple(band), "connectivity": opts.cc_connectivity, "min_voxels": opts.cc_min_voxels,
-            "largest": opts.cc_largest, "seeds": seeds, "background": opts.cc_despeckle, "level": opts.cc_level_dir is not None,
-            "labels": opts.cc_labels is not None, "top": 8}
+    return {"threshold": _band(parser, "--cc-threshold", opts.cc_threshold), "connectivity": opts.cc_connectivity,
+            "min_voxels": opts.cc_min_voxels, "largest": opts.cc_largest,
+            "seeds": None if opts.cc_seed is None else _voxels(parser, "--cc-seed", opts.cc_seed), "background": opts.cc_despeckle,
+            "level": opts.cc_level_dir is not None, "labels": opts.cc_labels is not None, "top": 8}
 
 
 def cl_options(parser, opts):
@@ -273,21 +282,15 @@ def cl_options(parser, opts):
         return None
     if opts.cl_start is None or opts.cl_end is None or opts.cl_threshold is None:
         parser.error("--cl-start, --cl-end and --cl-threshold need each other")
-    try:
-        band = [int(v) for v in opts.cl_threshold.split(",")]
-        points = [tuple(int(v) for v in text.split(",")) for text in [opts.cl_start] + opts.cl_end]
-    except ValueError:
-        parser.error("--cl-threshold: whole numbers LO or LO,HI, --cl-start / --cl-end: whole numbers Z,Y,X expected")
-    band = band + [32767] if len(band) == 1 else band
-    if len(band) != 2 or not -32768 <= band[0] <= band[1] <= 32767:
-        parser.error("--cl-threshold: -32768 <= LO <= HI <= 32767 expected, got %r" % opts.cl_threshold)
-    if any(len(p) != 3 or min(p) < 0 for p in points) or len(points) > 65:
-        parser.error("--cl-start / --cl-end: three whole numbers Z,Y,X >= 0 each, at most 64 ends, expected")
+    points = _voxels(parser, "--cl-start / --cl-end", [opts.cl_start] + opts.cl_end)
+    if len(points) > 65:
+        parser.error("--cl-end: at most 64 ends expected")
     if not 1 <= opts.cl_radius <= 32:
         parser.error("--cl-radius: 1 .. 32 expected")
     if not 0.25 <= opts.aspect < 16.0:
         parser.error("--aspect: 0.25 .. 16 expected with --cl-start")
-    return {"threshold": tuple(band), "start": points[0], "ends": points[1:], "radius": opts.cl_radius, "aspect": opts.aspect}
+    return {"threshold": _band(parser, "--cl-threshold", opts.cl_threshold), "start": points[0], "ends": points[1:],
+            "radius": opts.cl_radius, "aspect": opts.aspect}
 
 
 def parse_args(argv=None):
@@ -368,6 +371,17 @@ def reformat_tables(opts):
     return (tables or None), angles
 
 
+def write_pngs(where, pattern, planes, rows=None):
+    """One PNG per plane (uint8 [H, W]: mode "L"; [H, W, 3]: "RGB") into the directory `where`, made if need be, named by
+    `pattern` (of the plane's number, or the name of one plane); rows: the source row of every row of the picture."""
+    import numpy as np
+    from PIL import Image
+    os.makedirs(where, exist_ok=True)
+    for i, plane in enumerate(planes):
+        name = pattern % i if "%" in pattern else pattern
+        Image.fromarray(np.ascontiguousarray(plane if rows is None else plane[rows])).save(os.path.join(where, name))
+
+
 def main(argv=None):
     opts = parse_args(argv)
     if opts.slab is not None and opts.slab < 1:
@@ -384,7 +398,7 @@ def main(argv=None):
     with open(opts.config, "r") as stream:
         config = yaml.safe_load(stream)
     from cta_gan_amd import _lib, nets
-    from cta_gan_amd.infer import SeriesTranslator, view_angles
+    from cta_gan_amd.infer import SeriesTranslator, aspect_rows, view_angles
     from Model.HdGan import Generator
     _lib.load()
     mode = opts.dtype or DEFAULT_DTYPE
@@ -430,19 +444,14 @@ def main(argv=None):
                                  components=opts.cc, components_source=opts.cc_source, centreline=opts.cl)
     shown = "cued" if opts.depth_cue > 0 else "level"      # the plane the PNGs of the projections are written from
     out = translate(volume)
+    rows = aspect_rows(volume.shape[0], opts.aspect)      # of the coronal / sagittal / rotating PNGs: --aspect repeats their rows
     np.save(opts.output, out["pix"])
     if opts.level_dir is not None:
-        from PIL import Image
-        os.makedirs(opts.level_dir, exist_ok=True)
-        for i, plane in enumerate(out["level"]):
-            Image.fromarray(plane).save(os.path.join(opts.level_dir, "%06d.png" % i))      # uint8 [H, W]: mode "L"
+        write_pngs(opts.level_dir, "%06d.png", out["level"])
     if opts.sub_output is not None:
         np.save(opts.sub_output, out["sub"])
         if opts.sub_level_dir is not None:
-            from PIL import Image
-            os.makedirs(opts.sub_level_dir, exist_ok=True)
-            for i, plane in enumerate(out["sub_level"]):
-                Image.fromarray(plane).save(os.path.join(opts.sub_level_dir, "%06d.png" % i))
+            write_pngs(opts.sub_level_dir, "%06d.png", out["sub_level"])
         print("wrote the subtraction volume to %s" % opts.sub_output, flush=True)
     if opts.cc_output is not None:
         from cta_gan_amd.infer import root_voxel
@@ -451,10 +460,7 @@ def main(argv=None):
         if opts.cc_labels is not None:
             np.save(opts.cc_labels, ves["labels"])
         if opts.cc_level_dir is not None:
-            from PIL import Image
-            os.makedirs(opts.cc_level_dir, exist_ok=True)
-            for i, plane in enumerate(ves["level"]):
-                Image.fromarray(plane).save(os.path.join(opts.cc_level_dir, "%06d.png" % i))
+            write_pngs(opts.cc_level_dir, "%06d.png", ves["level"])
         roots = np.full((len(ves["top"]), 3), -1, dtype=np.int64)
         found = ves["top"][:, 0] >= 0
         if found.any():
@@ -464,15 +470,10 @@ def main(argv=None):
         print("components: %d found, %d kept, %d voxels kept (wrote %s)" % (ves["stats"][1], ves["stats"][3], ves["stats"][4],
                                                                             opts.cc_output), flush=True)
     if opts.mip_dir is not None:
-        from PIL import Image
-        from cta_gan_amd.infer import aspect_rows
-        os.makedirs(opts.mip_dir, exist_ok=True)
         proj = out["projections"]
-        for i, plane in enumerate(proj["axial"][shown]):
-            Image.fromarray(plane).save(os.path.join(opts.mip_dir, "axial_%03d.png" % i))
-        rows = aspect_rows(volume.shape[0], opts.aspect)
+        write_pngs(opts.mip_dir, "axial_%03d.png", proj["axial"][shown])
         for axis in ("coronal", "sagittal"):
-            Image.fromarray(np.ascontiguousarray(proj[axis][shown][rows])).save(os.path.join(opts.mip_dir, axis + ".png"))
+            write_pngs(opts.mip_dir, axis + ".png", [proj[axis][shown]], rows)
         arrays = {axis: proj[axis]["values"] for axis in proj}
         if opts.depth:
             arrays.update({axis + "_depth": proj[axis]["depth"] for axis in proj})
@@ -481,13 +482,8 @@ def main(argv=None):
         np.savez(os.path.join(opts.mip_dir, "projections.npz"), **arrays)
         print("wrote the %s projections to %s" % (opts.mip_mode, opts.mip_dir), flush=True)
     if opts.rot_dir is not None:
-        from PIL import Image
-        from cta_gan_amd.infer import aspect_rows
-        os.makedirs(opts.rot_dir, exist_ok=True)
         rot = out["rotation"]
-        rows = aspect_rows(volume.shape[0], opts.aspect)
-        for i, plane in enumerate(rot[shown]):
-            Image.fromarray(np.ascontiguousarray(plane[rows])).save(os.path.join(opts.rot_dir, "rot_%03d.png" % i))
+        write_pngs(opts.rot_dir, "rot_%03d.png", rot[shown], rows)
         arrays = {"values": rot["values"], "level": rot["level"], "angles": rot["angles"]}
         if opts.depth:
             arrays["depth"] = rot["depth"]
@@ -496,23 +492,14 @@ def main(argv=None):
         np.savez(os.path.join(opts.rot_dir, "rotation.npz"), **arrays)
         print("wrote %d views of the %s projection to %s" % (len(rot["angles"]), opts.mip_mode, opts.rot_dir), flush=True)
     if opts.vr_dir is not None:
-        from PIL import Image
-        from cta_gan_amd.infer import aspect_rows
-        os.makedirs(opts.vr_dir, exist_ok=True)
         ren = out["render"]
-        rows = aspect_rows(volume.shape[0], opts.aspect)
-        for i, frame in enumerate(ren["rgb"]):
-            Image.fromarray(np.ascontiguousarray(frame[rows])).save(      # uint8 [rows, D, 3]: mode "RGB"
-os.path.join(opts.vr_dir, "vr_%03d.png" % i))
+        write_pngs(opts.vr_dir, "vr_%03d.png", ren["rgb"], rows)      # uint8 [rows, D, 3]: mode "RGB"
         np.savez(os.path.join(opts.vr_dir, "render.npz"), rgb=ren["rgb"], opacity=ren["opacity"], depth=ren["depth"],
                  angles=ren["angles"], lut=vr_lut)
         print("wrote %d volume-rendered views (%s) to %s" % (len(ren["angles"]), opts.vr_preset, opts.vr_dir), flush=True)
     if opts.vr3d_dir is not None:
-        from PIL import Image
-        os.makedirs(opts.vr3d_dir, exist_ok=True)
         ren = out["render3d"]["vr3d"]
-        for i, frame in enumerate(ren["rgb"]):
-            Image.fromarray(np.ascontiguousarray(frame)).save(os.path.join(opts.vr3d_dir, "vr3d_%03d.png" % i))      # mode "RGB"
+        write_pngs(opts.vr3d_dir, "vr3d_%03d.png", ren["rgb"])      # mode "RGB"
         np.savez(os.path.join(opts.vr3d_dir, "render3d.npz"), rgb=ren["rgb"], opacity=ren["opacity"], depth=ren["depth"],
                  angles=np.array(view_angles(opts.vr_angles, opts.vr_span), dtype=np.float64), lut=vr3d_lut, lines=vr3d[0],
                  light=vr3d_light)
@@ -526,39 +513,24 @@ os.path.join(opts.vr_dir, "vr_%03d.png" % i))
                  counts=line["counts"], stats=line["stats"], **{"points_%d" % e: p for e, p in enumerate(line["points"])})
         print("centreline: %d path(s) of %s voxels from %s%s" % (len(line["counts"]), ", ".join(str(int(c)) for c in line["counts"]),
               opts.cl_start, "" if opts.cl_output is None else " (wrote %s)" % opts.cl_output), flush=True)
-        if opts.cpr_traced:
-            from PIL import Image
-            os.makedirs(opts.cpr_dir, exist_ok=True)
-            planes = line["cpr"][0]      # (of the first end; centreline.npz has every path)
-            for i, plane in enumerate(planes["level"]):
-                Image.fromarray(np.ascontiguousarray(plane)).save(os.path.join(opts.cpr_dir, "cpr_%03d.png" % i))
-            np.savez(os.path.join(opts.cpr_dir, "reformat.npz"), values=planes["values"], level=planes["level"],
-                     angles=np.array(opts.cl["cpr"]["angles"], dtype=np.float64))
-            print("wrote %d cpr reformat(s) along the traced centreline, %s sampling, to %s"
-                  % (len(planes["level"]), opts.reformat_sampling, opts.cpr_dir), flush=True)
-    for kind, where in (("mpr", opts.mpr_dir), ("tumble", opts.tumble_dir), ("cpr", None if opts.cpr_traced else opts.cpr_dir)):
+    if opts.cpr_traced:      # the curved reformat along the traced line of the first end (centreline.npz has every path)
+        reformat_angles["cpr"] = opts.cl["cpr"]["angles"]
+    for kind, where in (("mpr", opts.mpr_dir), ("tumble", opts.tumble_dir), ("cpr", opts.cpr_dir)):
         if where is None:
             continue
-        from PIL import Image
-        os.makedirs(where, exist_ok=True)
-        planes = out["reformat"][kind]
-        for i, plane in enumerate(planes["level"]):
-            Image.fromarray(np.ascontiguousarray(plane)).save(os.path.join(where, "%s_%03d.png" % (kind, i)))
+        traced = kind == "cpr" and opts.cpr_traced
+        planes = out["centreline"]["cpr"][0] if traced else out["reformat"][kind]
+        write_pngs(where, kind + "_%03d.png", planes["level"])
         arrays = {"values": planes["values"], "level": planes["level"]}
         if kind in reformat_angles:
             arrays["angles"] = np.array(reformat_angles[kind], dtype=np.float64)
         np.savez(os.path.join(where, "reformat.npz"), **arrays)
-        print("wrote %d %s reformat(s), %s sampling, to %s" % (len(planes["level"]), kind, opts.reformat_sampling, where), flush=True)
+        print("wrote %d %s reformat(s)%s, %s sampling, to %s" % (len(planes["level"]), kind, " along the traced centreline" if traced else "",
+                                                                opts.reformat_sampling, where), flush=True)
     if opts.sts_dir is not None:
-        from PIL import Image
-        from cta_gan_amd.infer import aspect_rows
-        os.makedirs(opts.sts_dir, exist_ok=True)
         slabs = out["slabs"]
-        rows = aspect_rows(volume.shape[0], opts.aspect)
         for axis, d in slabs.items():
-            for i, plane in enumerate(d["level"]):
-                plane = plane if axis == "axial" else np.ascontiguousarray(plane[rows])
-                Image.fromarray(plane).save(os.path.join(opts.sts_dir, "%s_%03d.png" % (axis, i)))
+            write_pngs(opts.sts_dir, axis + "_%03d.png", d["level"], None if axis == "axial" else rows)
         np.savez(os.path.join(opts.sts_dir, "slabs.npz"), **{axis: d["values"] for axis, d in slabs.items()})
         print("wrote the %s thin slabs (%s) to %s" % (opts.mip_mode, ", ".join("%s: %d" % (a, len(d["values"]))
                                                                              for a, d in slabs.items()), opts.sts_dir), flush=True)

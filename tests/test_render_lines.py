@@ -245,7 +245,7 @@ def test_volume_reformatter_is_refused_and_accepted_as_before():
     tables = {"tumble": lambda n, h, w: orbit_lines(n, h, w, [0.0], axis="x")}
     ref = VolumeReformatter(5, 13, 11, tables, mode="mean")
     made = tables["tumble"](5, 13, 11)
-    assert ref.volume is None and ref.tables is None and ref.device is None and (ref._seen == 0).all()
+    assert ref.volume is None and ref.tables is None and ref.device is None and (ref.source.seen == 0).all()
     assert ref.nbytes == 2 * 5 * 13 * 11 + (made[0].size // 9) * (36 + 3 * made.cols)
     with pytest.raises(ValueError, match="VolumeReformatter: n, h, w in 1 .. 4096 expected, got 5000 13 11"):
         VolumeReformatter(5000, 13, 11, tables)
@@ -261,12 +261,12 @@ def test_volume_reformatter_is_refused_and_accepted_as_before():
         with pytest.raises(RuntimeError, match="%s: every slice must have arrived exactly once: 5 of 5 missing, 0 more than once"
                            % type(view).__name__):
             view.result()
-        view._seen[:] = 1
-        view._seen[2] = 2
+        view.source.seen[:] = 1
+        view.source.seen[2] = 2
         with pytest.raises(RuntimeError, match="0 of 5 missing, 1 more than once"):
             view.result()
         view.reset()
-        assert (view._seen == 0).all()
+        assert (view.source.seen == 0).all()
 
 
 def test_series_translator_checks_render3d_in_its_constructor():

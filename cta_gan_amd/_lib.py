@@ -101,6 +101,7 @@ SIGNATURES = {
     "ctg_centreline_relax": "piiipiiiiiipppiiipp",
     "ctg_centreline_saturated": "plpp",
     "ctg_centreline_trace": "piiipiiiiiippiipppp",
+    "ctg_lumen_sections": "piiipiiiiiiiiippppp",
     "ctg_window_pairs": "ppppilipp",
     "ctg_maxpool3s2_fwd": "pipiiiiip",
     "ctg_lpips_layer": "pipiliippp",

@@ -826,23 +826,17 @@ def oblique_lines(n, h, w, normal, up=None, count=1, pitch=1.0, thick=1, rows=No
     return LineSet(np.stack([t for t, _ in sets]), sets[0][1], sets[0].cols)
 
 
-def curved_lines(n, h, w, centreline, angles=(0.0,), cols=65, depth=1, pitch=1.0, oversample=1, aspect=1.0):
-    """The straightened curved reformat along a centreline: -> `LineSet` (table int64 [A, R, 9], T = depth * oversample).
-    centreline: float [M >= 2, 3] in (z, y, x) voxel order.  It is resampled linearly at arc-length `pitch` (pixel units): R =
-    floor(length / pitch) + 1 rows p_r; the tangents are central differences of the resampled points (one-sided at the ends);
-    the frame (e1, e2) is carried along by parallel transport -- e1 is re-projected orthogonal to each new tangent and normalised,
-    e2 = tangent x e1 -- and starts from the x axis, or from the y axis where the first tangent is within 1e-6 of x.  Row r at
-    angle phi (degrees) samples p_r + (i - cu) (cos phi e1 + sin phi e2), cu = (cols-1)/2, and its slab of `depth` voxels runs
-    along -sin phi e1 + cos phi e2, centred on the line.  For a straight centreline along z through (y0, x0) with aspect 1, angle
-    0 reads vol[r, y0, x0 + i - cu]."""
-    who = "curved_lines"
+def _centreline_frames(who, centreline, pitch, aspect):
+    """What `curved_lines` and `lumen_lines` share: a centreline float [M >= 2, 3] in (z, y, x) voxel order -> (q [R, 3], the points
+    at arc length r pitch in (x, y, z) pixel units, R = floor(length / pitch) + 1; f1, f2 [R, 3], the parallel-transported frame
+    across the line at each; at [R], the arc lengths).  The tangents are central differences of the resampled points (one-sided at
+    the ends); e1 is re-projected orthogonal to each new tangent and normalised, e2 = tangent x e1; e1 starts from the x axis, or
+    from the y axis where the first tangent is within 1e-6 of x."""
     pts = np.asarray(centreline, dtype=np.float64)
     if pts.ndim != 2 or pts.shape[1] != 3 or pts.shape[0] < 2 or not np.isfinite(pts).all():
         raise ValueError("%s: a centreline of M >= 2 finite points (z, y, x) expected, got an array of shape %s" % (who, pts.shape))
-    angles = [float(v) for v in angles]
-    if not angles or not (float(pitch) > 0 and math.isfinite(float(pitch))):
-        raise ValueError("%s: at least one angle and pitch > 0 expected" % who)
-    n, h, w, _, cols, depth, s, aspect = _line_geometry(who, n, h, w, 1, cols, depth, oversample, aspect)
+    if not (float(pitch) > 0 and math.isfinite(float(pitch))):
+        raise ValueError("%s: pitch > 0 expected, got %r" % (who, pitch))
     p = pts[:, ::-1] * np.array([1.0, 1.0, aspect])      # (x, y, z) in pixel units
     seg = np.sqrt(((p[1:] - p[:-1]) ** 2).sum(axis=1))
     arc = np.concatenate([[0.0], np.cumsum(seg)])
@@ -862,6 +856,24 @@ def curved_lines(n, h, w, centreline, angles=(0.0,), cols=65, depth=1, pitch=1.0
         e1 = e1 - float(e1 @ tan[r]) * tan[r]
         e1 = e1 / math.sqrt(float(e1 @ e1))      # (a turn of 90 degrees between two rows would leave nothing: pitch too coarse)
         f1[r], f2[r] = e1, np.cross(tan[r], e1)
+    return q, f1, f2, at
+
+
+def curved_lines(n, h, w, centreline, angles=(0.0,), cols=65, depth=1, pitch=1.0, oversample=1, aspect=1.0):
+    """The straightened curved reformat along a centreline: -> `LineSet` (table int64 [A, R, 9], T = depth * oversample).
+    centreline: float [M >= 2, 3] in (z, y, x) voxel order.  It is resampled linearly at arc-length `pitch` (pixel units): R =
+    floor(length / pitch) + 1 rows p_r; the tangents are central differences of the resampled points (one-sided at the ends);
+    the frame (e1, e2) is carried along by parallel transport -- e1 is re-projected orthogonal to each new tangent and normalised,
+    e2 = tangent x e1 -- and starts from the x axis, or from the y axis where the first tangent is within 1e-6 of x.  Row r at
+    angle phi (degrees) samples p_r + (i - cu) (cos phi e1 + sin phi e2), cu = (cols-1)/2, and its slab of `depth` voxels runs
+    along -sin phi e1 + cos phi e2, centred on the line.  For a straight centreline along z through (y0, x0) with aspect 1, angle
+    0 reads vol[r, y0, x0 + i - cu]."""
+    who = "curved_lines"
+    angles = [float(v) for v in angles]
+    if not angles:
+        raise ValueError("%s: at least one angle expected" % who)
+    n, h, w, _, cols, depth, s, aspect = _line_geometry(who, n, h, w, 1, cols, depth, oversample, aspect)
+    q, f1, f2, _ = _centreline_frames(who, centreline, pitch, aspect)
     cu, ct = (cols - 1) / 2.0, (depth * s - 1) / (2.0 * s)
     tables = []
     for phi in angles:
@@ -872,9 +884,105 @@ def curved_lines(n, h, w, centreline, angles=(0.0,), cols=65, depth=1, pitch=1.0
     return LineSet(np.stack(tables), depth * s, cols)
 
 
+class LumenSet(tuple):
+    """What `lumen_lines` returns: the pair (table, T) like a `LineSet` -- an int64 table [R, rays, 9] for `ops.lumen_sections` and
+    the steps per ray -- that also remembers `.rays`, `.steps` (= T), `.oversample` and `.arc`, float64 [R]: the arc length of
+    every section along the centreline in pixel units.  `.cols` = rays: the table passes wherever a `LineSet` does."""
+
+    def __new__(cls, table, steps, rays, oversample, arc):
+        self = super().__new__(cls, (table, int(steps)))
+        self.rays = self.cols = int(rays)
+        self.steps, self.oversample = int(steps), int(oversample)
+        self.arc = np.asarray(arc, dtype=np.float64)
+        return self
+
+
+def lumen_lines(n, h, w, centreline, rays=32, reach=16.0, pitch=1.0, oversample=2, aspect=1.0):
+    """The ray fans that measure the lumen along a centreline: -> `LumenSet` (table int64 [R, rays, 9], T = floor(reach * oversample)
+    + 1).  The centreline, its resampling at arc length `pitch` and the frame (e1, e2) across it are those of `curved_lines`.
+    Section r has `rays` = 8, 16, 32 or 64 rays from the point p_r: ray j runs along cos(2 pi j / rays) e1 + sin(2 pi j / rays) e2
+    in steps of 1 / oversample pixel, k = 0 at the centre, out to `reach` pixels; 2 <= T <= 256.  Every row holds the centre as its
+    start, the ray's step in the k columns and 0 in the sample columns; `aspect` is inside the table like everywhere."""
+    who = "lumen_lines"
+    if isinstance(rays, bool) or rays not in ops.LUMEN_RAYS:
+        raise ValueError("%s: rays %r is not one of %s" % (who, rays, ops.LUMEN_RAYS))
+    n, h, w, _, _, _, s, aspect = _line_geometry(who, n, h, w, 1, 1, 1, oversample, aspect)
+    reach = float(reach)
+    steps = int(math.floor(reach * s + 1e-9)) + 1 if math.isfinite(reach) and reach > 0 else 0
+    if not 2 <= steps <= ops.LUMEN_MAX_STEPS:
+        raise ValueError("%s: floor(reach * oversample) + 1 = %d steps, 2 .. %d expected (reach %r, oversample %d)"
+                         % (who, steps, ops.LUMEN_MAX_STEPS, reach, s))
+    q, f1, f2, at = _centreline_frames(who, centreline, pitch, aspect)
+    table = np.empty((len(q), int(rays), 9), dtype=np.int64)
+    zero = np.zeros_like(q)
+    for j in range(int(rays)):
+        phi = 2.0 * math.pi * j / int(rays)
+        table[:, j] = _table(q, zero, math.cos(phi) * f1 + math.sin(phi) * f2, s, aspect)
+    return LumenSet(table, steps, rays, s, at)
+
+
+def lumen_profile(result, pixel_mm=1.0, oversample=None, arc=None):
+    """The measurements of a lumen result on the host, float64: result = {"radii", "cross", "sections", "centres"} (arrays or
+    tensors, as `VolumeLumen.result` returns them, which also carries "oversample" and "arc"; either may be given here instead)
+    -> {"area" [R] in mm^2: the polygon through the boundary points, sin(2 pi / K) / 2 * cross; "equivalent": 2 sqrt(area / pi);
+    "dmin", "dmax": the least and greatest chord through the centre; "mean": twice the mean radius; "arc": the position along the line
+    -- all in mm, a pixel being `pixel_mm` --; "valid" bool [R]: no open ray and the centre inside the band (a branch, a gap in the
+    contrast or the edge of the volume leaves rays open: the numbers of such a section are there but mean little)}."""
+    def host(v):
+        return np.asarray(v.cpu() if torch.is_tensor(v) else v)
+    radii, cross, sections = host(result["radii"]), host(result["cross"]), host(result["sections"])
+    if radii.ndim != 2 or radii.shape[1] not in ops.LUMEN_RAYS or cross.shape != radii.shape[:1] or sections.shape != (len(radii), 8):
+        raise ValueError("lumen_profile: radii [R, K], cross [R] and sections [R, 8] expected, got %s %s %s"
+                         % (radii.shape, cross.shape, sections.shape))
+    s = result.get("oversample") if oversample is None else oversample
+    at = result.get("arc") if arc is None else arc
+    s = int(host(s).reshape(-1)[0]) if s is not None else 0
+    pixel_mm = float(pixel_mm)
+    if s < 1 or not (pixel_mm > 0 and math.isfinite(pixel_mm)):
+        raise ValueError("lumen_profile: oversample >= 1 (in the result or given) and pixel_mm > 0 expected, got %r %r" % (s, pixel_mm))
+    k = radii.shape[1]
+    unit = pixel_mm / (256.0 * s)      # one unit of rho in mm
+    area = 0.5 * math.sin(2.0 * math.pi / k) * cross.astype(np.float64) * unit * unit
+    at = np.arange(len(radii), dtype=np.float64) if at is None else host(at).astype(np.float64)
+    if at.shape != (len(radii),):
+        raise ValueError("lumen_profile: arc [%d] expected, got %s" % (len(radii), at.shape))
+    return {"area": area, "equivalent": 2.0 * np.sqrt(area / math.pi), "dmin": sections[:, 1] * unit, "dmax": sections[:, 2] * unit,
+            "mean": sections[:, 0] * (2.0 * unit / k), "arc": at * pixel_mm,
+            "valid": (sections[:, 5] == 0) & (sections[:, 6] == 0)}
+
+
+def lumen_stenosis(profile, margin=5, reference=10, gap=5):
+    """The stenosis grade of a `lumen_profile`: the valid section of least equivalent diameter at least `margin` sections from
+    either end; the reference diameter and area are the mean of two medians, over the valid sections among the `reference` sections
+    that lie more than `gap` sections proximal of it and among those distal of it (the windows are cut at the ends of the line).
+    -> {"index", "diameter", "area": of the narrowest section; "reference_diameter", "reference_area"; "percent_diameter" = 100 (1 -
+    d / d_ref), "percent_area" likewise; "proximal", "distal": the indices of the valid sections used}.  ValueError when no valid
+    section lies inside the margins or a window holds no valid section.  The defaults are a first guess, not tuned on patient data."""
+    who = "lumen_stenosis"
+    margin, reference, gap = _int_in(who, "margin", margin, 0), _int_in(who, "reference", reference, 1), _int_in(who, "gap", gap, 0)
+    eq, area, valid = (np.asarray(profile[k]) for k in ("equivalent", "area", "valid"))
+    r = len(eq)
+    inner = np.zeros(r, dtype=bool)
+    inner[margin:r - margin if margin else r] = True
+    cand = np.flatnonzero(valid & inner)
+    if not len(cand):
+        raise ValueError("%s: no valid section lies %d or more sections from the ends" % (who, margin))
+    i = int(cand[np.argmin(eq[cand])])      # (the first on a tie)
+    index = np.arange(r)
+    prox = np.flatnonzero(valid & (index < i - gap) & (index >= i - gap - reference))
+    dist = np.flatnonzero(valid & (index > i + gap) & (index <= i + gap + reference))
+    if not len(prox) or not len(dist):
+        raise ValueError("%s: the %s reference window of section %d holds no valid section" % (who, "distal" if len(prox) else "proximal", i))
+    dref = 0.5 * (float(np.median(eq[prox])) + float(np.median(eq[dist])))
+    aref = 0.5 * (float(np.median(area[prox])) + float(np.median(area[dist])))
+    return {"index": i, "diameter": float(eq[i]), "area": float(area[i]), "reference_diameter": dref, "reference_area": aref,
+            "percent_diameter": 100.0 * (1.0 - float(eq[i]) / dref), "percent_area": 100.0 * (1.0 - float(area[i]) / aref),
+            "proximal": prox, "distal": dist}
+
+
 class ResidentVolume(_SeriesView):
     """An int16 volume [n, h, w] kept on the device for the views that read all of it (`VolumeReformatter`, `VolumeRenderer`,
-    `VolumeComponents`, `VolumeCentreline`): any number of them read one `ResidentVolume` (their `source=`).  `.volume`: the
+    `VolumeComponents`, `VolumeCentreline`, `VolumeLumen`): any number of them read one `ResidentVolume` (their `source=`).  `.volume`: the
     tensor, None until the first chunk; `.device`: None means the current device at the first chunk; `.seen`: how often every slice
     has arrived; `.nbytes` = 2 n h w.  `update(pix_chunk, n0)` copies a chunk in, in any order; `whole(who)` raises unless every
     slice has arrived exactly once since the last `reset()`, which forgets the arrivals and keeps the memory.  `adopt(tensor)`
@@ -994,6 +1102,30 @@ class _VolumeView(_SeriesView):
         values, level = ops.reformat_lines(self.volume, table, table.u, table.t, mode, fill=self.fill, wc=self.window[0], ww=self.window[1],
                                            hu=self.hu, sampling=sampling, want_level=self.want_level)
         return {"values": values, "level": level}
+
+    def _lumen_options(self, who, band, options, aspect):
+        """The lumen options of a constructor -> the dict with every default filled in, checked on the host as far as they can be
+        before a line exists: the band, the launch's options, and the geometry on a stand-in line."""
+        opts = {**LUMEN_DEFAULTS, **options}
+        opts["lo"], opts["hi"] = band
+        try:
+            steps = lumen_lines(self.n, self.h, self.w, np.array([[0.0, 0.0, 0.0], [0.0, 0.0, 1.0]]), aspect=aspect,
+                                **{k: opts[k] for k in LUMEN_GEOMETRY}).steps
+            ops.lumen_options(who, opts["rays"], steps, opts["lo"], opts["hi"], opts["sampling"], opts["edge"], opts["base"],
+                              opts["recentre"])
+        except RuntimeError as err:
+            raise ValueError(str(err)) from None
+        return opts
+
+    def _lumen(self, lines, opts, table=None):
+        """One `ops.lumen_sections` launch on the volume along the `LumenSet` lines -> the result tree of `VolumeLumen`."""
+        table = ops.LineTable(lines[0], lines.rays, lines.steps, self.device) if table is None else table
+        radii, cross, sections, centres = ops.lumen_sections(self.volume, table, lines.rays, lines.steps, opts["lo"], opts["hi"],
+                                                             sampling=opts["sampling"], edge=opts["edge"], base=opts["base"],
+                                                             recentre=opts["recentre"])
+        return {"radii": radii, "cross": cross, "sections": sections, "centres": centres,
+                "arc": torch.from_numpy(lines.arc).to(self.device),
+                "oversample": torch.tensor([lines.oversample], dtype=torch.int32, device=self.device)}
 
 
 class VolumeReformatter(_VolumeView):
@@ -1278,8 +1410,12 @@ def components_volume(volume, threshold, batch=64, device=None, **options):
 
 
 CENTRELINE_OPTIONS = ("threshold", "start", "ends", "radius", "aspect", "penalty", "max_points", "smooth", "cpr", "clearance",
-                      "rounds_per_call", "max_rounds", "fill", "wc", "ww", "hu", "level")
+                      "rounds_per_call", "max_rounds", "fill", "wc", "ww", "hu", "level", "lumen")
 CPR_OPTIONS = ("angles", "cols", "depth", "pitch", "sampling", "mode")
+LUMEN_GEOMETRY = ("rays", "reach", "pitch", "oversample")      # the options of `lumen_lines` a view passes on (aspect is its own)
+LUMEN_OPTIONS = ("threshold",) + LUMEN_GEOMETRY + ("sampling", "edge", "base", "recentre")
+LUMEN_DEFAULTS = {"rays": 32, "reach": 16.0, "pitch": 1.0, "oversample": 2, "sampling": "trilinear", "edge": "band", "base": None,
+                  "recentre": 0}
 
 
 def centreline_penalty(radius, far=1, near=64):
@@ -1339,7 +1475,10 @@ class VolumeCentreline(_VolumeView):
     clearance and the step lengths (`centreline_steps`); penalty: a uint16 table [R^2 + 1] (default `centreline_penalty(R)`);
     max_points: the longest path in voxels (default 4 (n + h + w)); smooth: the window of `smooth_centreline`.  cpr = a dict with
     any of angles, cols, depth, pitch (as `curved_lines`), sampling, mode (as `VolumeReformatter`) adds the curved reformat along
-    every end's smoothed path, one `ops.reformat_lines` launch per end on the resident volume, in the window (wc, ww) / `hu`. The
+    every end's smoothed path, one `ops.reformat_lines` launch per end on the resident volume, in the window (wc, ww) / `hu`;
+    lumen = a dict with any of threshold (default: the centreline's own band), rays, reach, pitch, oversample, sampling, edge, base,
+    recentre (as `VolumeLumen`) measures the lumen along every end's smoothed path, one `ops.lumen_sections` launch per end, and
+    adds "lumen": one result tree of `VolumeLumen` per end; without it nothing of that is allocated or launched.  The
     volume, `source=`, `update` and `reset` as `_VolumeView` has them; `result()` -> {"paths": int32 [E, max_points] (linear
     indices, end first, -1 beyond the count), "counts": int32 [E], "points": a list of float64 [M, 3] (z, y, x), start to end,
     smoothed, "clearance": uint16 [n, h, w] (clearance=True) or None, "stats": int32 [8] (`ops.CENTRELINE_STATS`), and with cpr
@@ -1353,7 +1492,7 @@ class VolumeCentreline(_VolumeView):
 
     def __init__(self, n, h, w, threshold, start, ends, radius=8, aspect=1.0, penalty=None, max_points=None, smooth=5, cpr=None,
                  clearance=False, rounds_per_call=16, max_rounds=4096, fill=None, wc=50.0, ww=400.0, hu=False, level=True, device=None,
-                 source=None):
+                 source=None, lumen=None):
         who = "VolumeCentreline"
         self._sides(who, n, h, w, linear=True)
         v = self.n * self.h * self.w
@@ -1383,6 +1522,12 @@ class VolumeCentreline(_VolumeView):
                 raise ValueError("%s: cpr: mode one of %s and sampling one of %s expected" % (who, PROJECTIONS, REFORMAT_SAMPLINGS))
             curved_lines(self.n, self.h, self.w, np.array([[0.0, 0.0, 0.0], [0.0, 0.0, 1.0]]), aspect=self.aspect,
                          **{k: self.cpr[k] for k in ("angles", "cols", "depth", "pitch")})      # (the options, checked now)
+        self.lumen = None
+        if lumen is not None:
+            if not isinstance(lumen, dict) or set(lumen) - set(LUMEN_OPTIONS):
+                raise ValueError("%s: lumen %r: a dict with any of %s expected" % (who, lumen, LUMEN_OPTIONS))
+            band = _band(who, lumen["threshold"]) if "threshold" in lumen else (self.lo, self.hi)
+            self.lumen = self._lumen_options(who, band, {k: v for k, v in lumen.items() if k != "threshold"}, self.aspect)
         self.want_clearance = bool(clearance)
         self._shown(wc, ww, hu, level, fill)
         tz, ty, tx = ops.CENTRELINE_TILE
@@ -1433,6 +1578,13 @@ class VolumeCentreline(_VolumeView):
                 lines = curved_lines(self.n, self.h, self.w, p, aspect=self.aspect, **{k: self.cpr[k] for k in ("angles", "cols", "depth", "pitch")})
                 out["cpr"].append(self._reformat(ops.LineTable(lines[0], lines.cols, lines[1], self.device), self.cpr["mode"],
                                                  self.cpr["sampling"]))
+        if self.lumen is not None:
+            out["lumen"] = []
+            for p in points:
+                if len(p) < 2:
+                    raise ValueError("%s: lumen: an end is the start itself: there is no line to measure along" % who)
+                out["lumen"].append(self._lumen(lumen_lines(self.n, self.h, self.w, p, aspect=self.aspect,
+                                                            **{k: self.lumen[k] for k in LUMEN_GEOMETRY}), self.lumen))
         return out
 
 
@@ -1443,6 +1595,55 @@ def centreline_volume(volume, threshold, start, ends, batch=64, device=None, **o
     kind."""
     return _view_of_volume("centreline_volume", volume, batch, device, whole=True,
                            make=lambda n, h, w, dev: VolumeCentreline(n, h, w, threshold, start, ends, device=dev, **options))
+
+
+class VolumeLumen(_VolumeView):
+    """The lumen profile along a centreline of an int16 volume [n, h, w] that arrives in chunks and stays on the device
+    (`ops.lumen_sections`, csrc/lumen.hip): at every position of the line the lumen's radius along a fan of rays across it, from
+    which `lumen_profile` takes area and diameters and `lumen_stenosis` the grade.  threshold: lo, or (lo, hi), the lumen's band of
+    stored values as `VolumeComponents` has it; points: the centreline, float [M >= 2, 3] in (z, y, x) voxel order (a path of
+    `VolumeCentreline`, smoothed); rays, reach, pitch, oversample, aspect as `lumen_lines`; sampling "trilinear" or "nearest";
+    edge "band" (the wall is where the value leaves the band) or "half" with `base` <= lo (the wall is half-way between the
+    section's own centre value and the background `base`, never below lo); recentre 0 .. 4: moves of every section's centre to the
+    middle of its own boundary before the measurement that counts.  The volume, `source=`, `update` and `reset` as `_VolumeView` has
+    them; `result()` makes one launch -> {"radii": int32 [R, rays] in 1 / (256 oversample) pixel, "cross": int64 [R], "sections":
+    int32 [R, 8] (`ops.LUMEN_SECTIONS`), "centres": int32 [R, 3] = (x, y, z) in 16.16, "arc": float64 [R] in pixels, "oversample":
+    int32 [1]} on the device: what `lumen_profile` takes.  A branch, a gap or the edge of the volume shows as open rays: such a section
+    is not valid.  `.lines`: the `LumenSet`.  `.nbytes`: the device memory held (the volume, unless it is a source's, and the table)
+    plus that of one result, known before the first chunk.  Exact integer arithmetic on the current stream: equal to numpy bit for
+    bit."""
+
+    def __init__(self, n, h, w, threshold, points, rays=32, reach=16.0, pitch=1.0, oversample=2, aspect=1.0, sampling="trilinear",
+                 edge="band", base=None, recentre=0, device=None, source=None):
+        who = "VolumeLumen"
+        self._sides(who, n, h, w)
+        self.options = self._lumen_options(who, _band(who, threshold), {"rays": rays, "reach": reach, "pitch": pitch,
+                                                                         "oversample": oversample, "sampling": sampling, "edge": edge,
+                                                                         "base": base, "recentre": recentre}, aspect)
+        self.lines = lumen_lines(self.n, self.h, self.w, points, rays=rays, reach=reach, pitch=pitch, oversample=oversample, aspect=aspect)
+        try:
+            self.table_host = ops.lumen_table_host(self.lines[0], self.lines.rays, self.lines.steps, self.options["recentre"])
+        except RuntimeError as err:
+            raise ValueError("%s: %s" % (who, err)) from None
+        sections = len(self.lines.arc)
+        self.nbytes = 2 * self.n * self.h * self.w + self.table_host.nbytes + sections * (4 * self.lines.rays + 8 + 32 + 12 + 8) + 4
+        self.table = None      # on the device from `_upload` on
+        self._reads(device, source)
+
+    def _upload(self):
+        self.table = ops.LineTable(self.table_host, self.lines.rays, self.lines.steps, self.device)
+
+    def result(self):
+        self._whole()
+        return self._lumen(self.lines, self.options, self.table)
+
+
+def lumen_volume(volume, threshold, points, batch=64, device=None, **options):
+    """The lumen view of a volume that already exists, the twin of `centreline_volume`: int16 [N, H, W], a host array / CPU tensor
+    (chunks of `batch` slices cross PCIe one after another) or a device tensor (read where it is when it is contiguous); threshold,
+    points and the options as `VolumeLumen`.  Returns what `VolumeLumen.result` returns, of the input's kind."""
+    return _view_of_volume("lumen_volume", volume, batch, device, whole=True,
+                           make=lambda n, h, w, dev: VolumeLumen(n, h, w, threshold, points, device=dev, **options))
 
 
 def subtract_volume(cta, ct_hu, cta_is_hu=False, median=True, floor=0, ct_range=(None, None), wc=150.0, ww=300.0, level=True,
@@ -1562,8 +1763,9 @@ class SeriesTranslator:
     the components' source, and after the last chunk the views on the whole volume read the cleaned tensor where it is and the
     others get its slices in chunks of `batch`.
     centreline = a dict of `VolumeCentreline` keyword arguments (threshold, start, ends, and any of radius, aspect, penalty,
-    max_points, smooth, cpr, clearance, rounds_per_call, max_rounds, fill, wc, ww, hu, level) adds "centreline": {"paths", "counts",
-    "points": a list of float64 [M, 3], "clearance", "stats", and with cpr "cpr": [{"values", "level"}]}, the vessel centreline from
+    max_points, smooth, cpr, clearance, rounds_per_call, max_rounds, fill, wc, ww, hu, level, lumen) adds "centreline": {"paths", "counts",
+    "points": a list of float64 [M, 3], "clearance", "stats", with cpr "cpr": [{"values", "level"}], and with lumen "lumen": [the
+    tree of `VolumeLumen` per end, for `lumen_profile` / `lumen_stenosis`]}, the vessel centreline from
     `start` to every end through the same source as the other displays (`project_source`), traced after the last chunk and copied
     back once; it waits for the relaxation on the host.
     reformat, render3d, components and centreline read the whole volume, which stays on the device: one `ResidentVolume` per source

@@ -2581,3 +2581,81 @@ def centreline_trace(clear, pen, steps, dist, ends, radius, max_points, stats=No
         _lib.check(lib.ctg_centreline_trace(_p(clear), n, h, w, _p(pen), radius, *steps, _p(dist), _p(ends), e, max_points, _p(paths),
                                             _p(counts), _p(stats), _stream()), "ctg_centreline_trace")
     return paths, counts
+
+
+# ---------------------------------------------------------------------------- lumen profile along a centreline (csrc/lumen.hip)
+LUMEN_RAYS = (8, 16, 32, 64)      # K: the rays of a section are the lanes of a wave, or of a half, quarter, eighth of one
+LUMEN_MAX_STEPS = 256             # T: the radius along a ray is at most 255 * 256
+LUMEN_MAX_RECENTRE = 4
+LUMEN_EDGES = {"band": 0, "half": 1}      # `edge` of ctg_lumen_sections
+LUMEN_SECTIONS = ("sum", "dmin", "dmax", "jmin", "jmax", "open", "outside", "lo")      # the columns of `sections`
+
+
+def lumen_table_check(host, steps, recentre):
+    """Raise unless, on every axis of every section of the int table [R, K, 9], |c0| + (1 + 2 recentre) (T-1) max_j |ck_j| < 2^31:
+    the condition under which no fixed-point sum of ctg_lumen_sections leaves int32, the recentred walks included.  Needs no GPU."""
+    import numpy as np
+    c = np.asarray(host).astype(np.int64)
+    reach = (1 + 2 * int(recentre)) * (int(steps) - 1) * np.abs(c[:, :, 2::3]).max(axis=1)
+    if (np.abs(c[:, :, 0::3]).max(axis=1) + reach >= 1 << 31).any():
+        raise RuntimeError("lumen_sections: line table out of range (|c0| + (1 + 2 recentre) (T-1) max |ck| < 2^31 for every section "
+                           "and axis)")
+
+
+def lumen_options(who, rays, steps, lo, hi=32767, sampling="trilinear", edge="band", base=None, recentre=0):
+    """The option checks of `lumen_sections`, for whoever wants them before a volume exists (`infer.VolumeLumen`): -> (rays, steps,
+    lo, hi, sampling, edge, base, recentre) as the launch takes them; base is None unless the edge is "half".  Needs no GPU."""
+    if isinstance(rays, bool) or rays not in LUMEN_RAYS:
+        raise RuntimeError("%s: rays %r is not one of %s" % (who, rays, LUMEN_RAYS))
+    steps = _components_int(who, "steps", steps, 2, LUMEN_MAX_STEPS)
+    lo, hi = _components_int(who, "lo", lo, -32768, 32767), _components_int(who, "hi", hi, -32768, 32767)
+    if lo > hi:
+        raise RuntimeError("%s: the threshold band (%d, %d) is empty" % (who, lo, hi))
+    if sampling not in REFORMAT_SAMPLINGS:
+        raise RuntimeError("%s: sampling %r is not one of %s" % (who, sampling, tuple(REFORMAT_SAMPLINGS)))
+    if edge not in LUMEN_EDGES:
+        raise RuntimeError("%s: edge %r is not one of %s" % (who, edge, tuple(LUMEN_EDGES)))
+    if edge == "half":
+        if base is None:
+            raise RuntimeError("%s: edge 'half' needs base, the background's value" % who)
+        base = _components_int(who, "base", base, -32768, lo)      # base <= lo, so the section's lower end never exceeds its centre
+    elif base is not None:
+        raise RuntimeError("%s: base belongs to edge 'half'" % who)
+    return int(rays), steps, lo, hi, sampling, edge, base, _components_int(who, "recentre", recentre, 0, LUMEN_MAX_RECENTRE)
+
+
+def lumen_table_host(lines, rays, steps, recentre):
+    """The host half of a lumen table: [R, rays, 9] integers -> the int32 copy `LineTable` takes, checked by `line_table_host` and
+    `lumen_table_check`.  Needs no GPU."""
+    host = line_table_host(lines, rays, steps)
+    if host.ndim != 3 or host.shape[1] != int(rays):
+        raise RuntimeError("lumen_sections: a table [R, %d, 9] expected, got %s" % (int(rays), tuple(host.shape)))
+    lumen_table_check(host, steps, recentre)
+    return host
+
+
+def lumen_sections(vol, lines, rays, steps, lo, hi=32767, sampling="trilinear", edge="band", base=None, recentre=0):
+    """The lumen's radius along `rays` rays of every cross-section of a centreline, one launch of ctg_lumen_sections: vol (N, H, W)
+    int16 on the GPU (a contiguous view is taken as it is); lines: the table [R, rays, 9] of `infer.lumen_lines` -- a `LineTable`
+    made with u = rays and t = steps, or a host table that is checked and uploaded by this call; rays 8, 16, 32 or 64; steps = T in
+    2 .. 256 per ray, the centre included; (lo, hi): the lumen's band of stored values; sampling "trilinear" or "nearest"; edge
+    "band" (a ray ends where the value leaves lo .. hi) or "half" (the lower end is max(lo, (centre value + base) >> 1): half-way to
+    a background `base` <= lo); recentre 0 .. 4 moves of the centre to twice the mean boundary point inside the launch.  Returns
+    (radii int32 [R, rays] in 1/256 step, cross int64 [R], sections int32 [R, 8] (`LUMEN_SECTIONS`), centres int32 [R, 3] = (x, y, z)
+    in 16.16) on the GPU; include/ctagan_hip.h has the rule.  Exact integer arithmetic: equal to numpy bit for bit."""
+    lib = _lib.load()
+    who = "lumen_sections"
+    _lines_volume(who, vol)
+    k, t, lo, hi, sampling, edge, base, recentre = lumen_options(who, rays, steps, lo, hi, sampling, edge, base, recentre)
+    x, table, (n, h, w, k, t) = _lines_args(who, vol, lines, k, t)
+    lumen_table_host(table.host, k, t, recentre)
+    r = table.shape[0]
+    with torch.cuda.device(vol.device):
+        radii = torch.empty((r, k), dtype=torch.int32, device=vol.device)
+        cross = torch.empty(r, dtype=torch.int64, device=vol.device)
+        sections = torch.empty((r, 8), dtype=torch.int32, device=vol.device)
+        centres = torch.empty((r, 3), dtype=torch.int32, device=vol.device)
+        _lib.check(lib.ctg_lumen_sections(_p(x), n, h, w, _p(table.dev), r, k, t, lo, hi, REFORMAT_SAMPLINGS[sampling], LUMEN_EDGES[edge],
+                                          0 if base is None else base, recentre, _p(radii), _p(cross), _p(sections), _p(centres),
+                                          _stream()), "ctg_lumen_sections")
+    return radii, cross, sections, centres

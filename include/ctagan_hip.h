@@ -736,6 +736,45 @@ int ctg_centreline_trace(const unsigned short* clear, int N, int H, int W, const
                          int s3, int s4, const unsigned* dist, const int* ends, int E, int max_points, int* paths, int* counts,
                          int* stats, void* stream);
 
+/* ---- series inference, the lumen profile along a centreline (added under ABI 15: purely additive, no existing signature or meaning
+ * moves, so the version stays 15): at every position of the line the lumen's radius along K rays of the cross-section, from which the
+ * host takes area, diameters and the stenosis grade.  cta_gan_amd/infer.py: lumen_lines, lumen_profile, lumen_stenosis, VolumeLumen,
+ * lumen_volume, VolumeCentreline(lumen=...), SeriesTranslator(centreline={..., "lumen": ...}); ops.lumen_sections.  The reference has
+ * no counterpart.
+ * ctg_lumen_sections: vol, N, H, W, the 16.16 positions, the "counted" rule and the value of a sample (sampling 0 = nearest, 1 =
+ *   trilinear) are exactly those of ctg_reformat_lines.  lines = int32 [R][K][9] on the device, 4-byte aligned, rows in the format of
+ *   ctg_reformat_lines; K = 8, 16, 32 or 64 rays per section, T = 2 .. 256 steps per ray.  Section r has the centre C = (x0, y0, z0) of
+ *   its row (r, 0), and ray j the step D_j = (xk, yk, zk) of row (r, j): sample k of ray j lies at C + k D_j.  Nothing else of a row is
+ *   read (the host writes the centre into every row and xu = yu = zu = 0).
+ *   One walk of a section: s0 = the value at C.  If C is not counted, s0 < lo or s0 > hi: outside = 1, lo_r = lo, every rho_j = 0 and no
+ *     ray is open.  Otherwise outside = 0 and lo_r = lo (edge 0, "band") or max(lo, (s0 + base) >> 1) (edge 1, "half": half-way between
+ *     the lumen's own density and a background `base` <= lo; arithmetic shift), so lo_r <= s0.  Ray j takes k = 1 .. T-1 in turn with
+ *     prev = the value at k-1 (s0 at k = 1) and v = the value at k, and stops at the first k where
+ *       the sample is not counted:   rho_j = 256 (k-1), and the ray is open;
+ *       else v < lo_r:               rho_j = 256 (k-1) + (256 (prev - lo_r)) / (prev - v);
+ *       else v > hi:                 rho_j = 256 (k-1) + (256 (hi - prev)) / (v - prev);
+ *     a ray that never stops has rho_j = 256 (T-1) and is open.  lo_r <= prev <= hi holds throughout, so every numerator is >= 0 and
+ *     below its denominator: C division is floor and the fraction lies in 0 .. 255.  rho is the lumen's radius along the ray in units of
+ *     1 / 256 step, at most 65280.
+ *   Recentring, `recentre` = 0 .. 4 times: after a walk with outside = 0 and no open ray the centre moves on each axis a by
+ *     (S_a + 64 K) >> (7 + log2 K), S_a = sum_j rho_j D_j[a] in int64, arithmetic shift -- twice the mean boundary point, rounded to
+ *     nearest, in the section's plane -- and the section is walked again from there; after any other walk the centre stays and the
+ *     section is finished.  What is stored is the last walk's.
+ *   Outputs, all on the device: radii int32 [R][K] = rho; cross int64 [R] (8-byte aligned) = sum_j rho_j rho_((j+1) mod K) (the polygon
+ *     through the boundary points has the area sin(2 pi / K) / 2 times that); centres int32 [R][3] = the last centre (x, y, z), 16.16 with
+ *     the + 0.5 inside like the table; sections int32 [R][8] = sum_j rho_j; dmin and dmax, the least and greatest chord rho_j +
+ *     rho_(j+K/2) over j < K/2; jmin and jmax, their rays, the lowest j on a tie; the number of open rays; outside; lo_r.
+ *   Every address is bounds-checked or clamped whatever the table holds; the sums are formed in unsigned arithmetic and read as int32, so
+ *     the caller keeps |c0| + (1 + 2 recentre) (T-1) max_j |ck_j| < 2^31 on every axis of every section (a move is at most
+ *     2 (T-1) max_j |ck_j|; ops.lumen_sections checks it on the host): beyond that the result is defined by the wrapped sums, still
+ *     without an access outside the volume.
+ *   Exact integer arithmetic: the same bits as numpy (tests/lumen_np.py).  One launch, no accumulator, no atomics.
+ *   CTG_EINVAL, nothing launched: a null pointer; N, H or W outside 1 .. 4096; R < 1 or R K above 2^31 - 1; K not 8, 16, 32 or 64; T
+ *   outside 2 .. 256; lo > hi or either outside int16; sampling or edge outside 0 .. 1; with edge 1 a base outside -32768 .. lo;
+ *   recentre outside 0 .. 4; vol not 2-byte aligned, lines, radii, sections or centres not 4-byte aligned, cross not 8-byte aligned. ---- */
+int ctg_lumen_sections(const short* vol, int N, int H, int W, const int* lines, int R, int K, int T, int lo, int hi, int sampling,
+                       int edge, int base, int recentre, int* radii, long long* cross, int* sections, int* centres, void* stream);
+
 /* ---- LPIPS (AlexNet, lpips 0.1) of the test() loops (ABI 14): `loss_fn_alex = lpips.LPIPS(net='alex')` (trainer/HdTrainer.py:26-28)
  * and its calls `loss_fn_alex.forward(torch.tensor(c), torch.tensor(b))` on the windowed and on the raw masked pair of every slice
  * (HdTrainer.py:504-513, 531-536, 1029-1031, 1054-1056; the twins in CycTrainer.py, p2pTrainer.py, RegTrainer.py).  The five

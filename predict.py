@@ -19,6 +19,8 @@
                       [--tumble-dir DIR [--tumble-angles 36] [--tumble-axis x|y|z]]
                       [--cpr-dir DIR --cpr-centreline pts.npy [--cpr-angles A] [--cpr-width U] [--cpr-thick T]]
                       [--cl-start Z,Y,X --cl-end Z,Y,X [--cl-end ...] --cl-threshold LO[,HI] [--cl-radius R] [--cl-output pts.npy]]
+                      [--lumen-output lumen.npz [--lumen-rays K] [--lumen-reach PX] [--lumen-oversample S]
+                       [--lumen-edge band|half --lumen-base HU] [--lumen-recentre I] [--pixel-mm MM]]
                       [--reformat-sampling nearest|trilinear]
                       [--cc-output vessels.npy --cc-threshold LO[,HI] [--cc-level-dir DIR] [--cc-connectivity 6|18|26]
                        [--cc-min-voxels M] [--cc-largest K] [--cc-seed Z,Y,X ...] [--cc-despeckle] [--cc-source cta|sub]
@@ -103,6 +105,15 @@ capped at --cl-radius R pixels (default 8); --aspect R scales z.  --cl-output pt
 [M, 3], (z, y, x), start to end) of the first end -- what --cpr-centreline reads -- and centreline.npz next to it (next to
 --output without it) paths, counts, stats and points_0, points_1, ... of every end; one line reports the lengths.  --cpr-dir
 without --cpr-centreline then makes the curved reformat along the traced line of the first end in the same run.
+--lumen-output lumen.npz (with --cl-start): the lumen measured along the traced line of every end in the same run
+(cta_gan_amd/infer.py: VolumeCentreline(lumen=...), lumen_profile, lumen_stenosis): --lumen-rays K = 8, 16, 32 or 64 rays across
+the vessel at every pixel of arc length, walked out to --lumen-reach pixels in steps of 1 / --lumen-oversample until the value
+leaves the band of --cl-threshold; --lumen-edge half puts the wall half-way between the section's own centre value and the
+background --lumen-base (a stored value, not above LO) instead; --lumen-recentre I = 0 .. 4 moves every section's centre to the
+middle of its own boundary first (without it the least diameter measures the click, not the vessel).  The file holds radii, cross,
+sections, centres and, with --pixel-mm MM (the in-plane pixel spacing, default 1), area, equivalent, dmin, dmax, mean, arc and
+valid of every end (suffix _0, _1, ...); one line per end reports the stenosis grade.  A branch leaves rays open: such sections
+are not valid and take no part in the grade.
 DICOM reading and writing are not part of this build.
 """
 import argparse
@@ -194,6 +205,14 @@ def build_parser():
     parser.add_argument("--cl-threshold", type=str, default=None, help="LO or LO,HI: the vessel's band (with --cl-start; as --cc-threshold)")
     parser.add_argument("--cl-radius", type=int, default=8, help="the clearance is capped at this many pixels, 1 .. 32 (with --cl-start)")
     parser.add_argument("--cl-output", type=str, default=None, help="write the smoothed centreline of the first end here (.npy, [M, 3])")
+    parser.add_argument("--lumen-output", type=str, default=None, help="write the lumen profile along every traced centreline here (.npz; with --cl-start)")
+    parser.add_argument("--lumen-rays", type=int, default=32, help="rays per cross-section: 8, 16, 32 or 64 (with --lumen-output)")
+    parser.add_argument("--lumen-reach", type=float, default=16.0, help="how far a ray is walked, in pixels (with --lumen-output)")
+    parser.add_argument("--lumen-oversample", type=int, default=2, help="steps per pixel along a ray (with --lumen-output)")
+    parser.add_argument("--lumen-edge", type=str, default="band", choices=["band", "half"], help="the wall: where the value leaves the band, or half-way to --lumen-base")
+    parser.add_argument("--lumen-base", type=int, default=None, help="the background's stored value (with --lumen-edge half)")
+    parser.add_argument("--lumen-recentre", type=int, default=2, help="recentring moves per section, 0 .. 4 (with --lumen-output)")
+    parser.add_argument("--pixel-mm", type=float, default=1.0, help="the in-plane pixel spacing in mm (with --lumen-output)")
     parser.add_argument("--dtype", choices=DTYPES, default=None, help="compute mode (default %s, as train.py)" % DEFAULT_DTYPE)
     return parser
 
@@ -277,8 +296,8 @@ def cc_options(parser, opts):
 def cl_options(parser, opts):
     """The `SeriesTranslator(centreline=...)` dict of --cl-start / --cl-end (None without them); bad values end in parser.error."""
     if opts.cl_start is None and opts.cl_end is None:
-        if opts.cl_threshold is not None or opts.cl_output is not None:
-            parser.error("--cl-threshold and --cl-output need --cl-start and --cl-end")
+        if opts.cl_threshold is not None or opts.cl_output is not None or opts.lumen_output is not None:
+            parser.error("--cl-threshold, --cl-output and --lumen-output need --cl-start and --cl-end")
         return None
     if opts.cl_start is None or opts.cl_end is None or opts.cl_threshold is None:
         parser.error("--cl-start, --cl-end and --cl-threshold need each other")
@@ -289,8 +308,18 @@ def cl_options(parser, opts):
         parser.error("--cl-radius: 1 .. 32 expected")
     if not 0.25 <= opts.aspect < 16.0:
         parser.error("--aspect: 0.25 .. 16 expected with --cl-start")
-    return {"threshold": _band(parser, "--cl-threshold", opts.cl_threshold), "start": points[0], "ends": points[1:],
-            "radius": opts.cl_radius, "aspect": opts.aspect}
+    out = {"threshold": _band(parser, "--cl-threshold", opts.cl_threshold), "start": points[0], "ends": points[1:],
+           "radius": opts.cl_radius, "aspect": opts.aspect}
+    if opts.lumen_output is not None:
+        steps = int(opts.lumen_reach * opts.lumen_oversample) + 1 if opts.lumen_oversample >= 1 and 0 < opts.lumen_reach < 1e6 else 0
+        if opts.lumen_rays not in (8, 16, 32, 64) or not 2 <= steps <= 256 or not 0 <= opts.lumen_recentre <= 4 or not opts.pixel_mm > 0:
+            parser.error("--lumen-rays: 8, 16, 32 or 64, --lumen-reach x --lumen-oversample: 1 .. 255 steps, --lumen-recentre: 0 .. 4 "
+                         "and --pixel-mm above 0 expected")
+        if (opts.lumen_edge == "half") != (opts.lumen_base is not None) or (opts.lumen_base is not None and opts.lumen_base > out["threshold"][0]):
+            parser.error("--lumen-edge half and --lumen-base need each other, and the base must not lie above the LO of --cl-threshold")
+        out["lumen"] = {"rays": opts.lumen_rays, "reach": opts.lumen_reach, "oversample": opts.lumen_oversample, "edge": opts.lumen_edge,
+                        "base": opts.lumen_base, "recentre": opts.lumen_recentre}
+    return out
 
 
 def parse_args(argv=None):
@@ -513,6 +542,22 @@ def main(argv=None):
                  counts=line["counts"], stats=line["stats"], **{"points_%d" % e: p for e, p in enumerate(line["points"])})
         print("centreline: %d path(s) of %s voxels from %s%s" % (len(line["counts"]), ", ".join(str(int(c)) for c in line["counts"]),
               opts.cl_start, "" if opts.cl_output is None else " (wrote %s)" % opts.cl_output), flush=True)
+    if opts.cl is not None and "lumen" in opts.cl:
+        from cta_gan_amd.infer import lumen_profile, lumen_stenosis
+        arrays = {}
+        for e, tree in enumerate(out["centreline"]["lumen"]):
+            prof = lumen_profile(tree, pixel_mm=opts.pixel_mm)
+            arrays.update({"%s_%d" % (k, e): v for k, v in list(tree.items()) + list(prof.items())})
+            try:
+                g = lumen_stenosis(prof)
+                print("lumen %d: %d of %d sections valid; narrowest at %.1f mm: diameter %.2f mm against a reference of %.2f mm: "
+                      "%.0f %% diameter stenosis, %.0f %% by area" % (e, int(prof["valid"].sum()), len(prof["valid"]), prof["arc"][g["index"]],
+                                                                     g["diameter"], g["reference_diameter"], g["percent_diameter"],
+                                                                     g["percent_area"]), flush=True)
+            except ValueError as err:
+                print("lumen %d: %d of %d sections valid; no stenosis grade: %s" % (e, int(prof["valid"].sum()), len(prof["valid"]), err), flush=True)
+        np.savez(opts.lumen_output, **arrays)
+        print("wrote the lumen profile of %d centreline(s) to %s" % (len(out["centreline"]["lumen"]), opts.lumen_output), flush=True)
     if opts.cpr_traced:      # the curved reformat along the traced line of the first end (centreline.npz has every path)
         reformat_angles["cpr"] = opts.cl["cpr"]["angles"]
     for kind, where in (("mpr", opts.mpr_dir), ("tumble", opts.tumble_dir), ("cpr", opts.cpr_dir)):
